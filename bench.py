@@ -1,10 +1,11 @@
 #!/usr/bin/env python
 """Benchmark of exprgrad's compiled-tensor hot path on MI355X (contract: DESIGN.md "Measurement").
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
       matmul M=N=K=4096 float32 (BASELINE.json configs[1], the config the metric is quoted on):
-      value = GFLOP/s; the same JSON line also carries the single-GPU numbers of the other
-      configs ("extra": dense-net train step, XOR train step, conv2) measured in the same run.
+      value = GFLOP/s.  A plain run sets up, warms up, times the K steps and prints the line; with
+      --full the same JSON line also carries the single-GPU numbers of the other configs ("extra":
+      dense-net train step, XOR train step, conv2, ...), CPU baselines and the secondary figures.
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
       data-parallel dense-net train step (configs[4]): batch 65536 per GPU ("weak" scaling,
       N = 8 is the 524288 global batch of the config), RCCL all-reduce of the parameter gradients
@@ -111,7 +112,19 @@ def parse():
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="N > 1 train workload: weak = 65536 samples per GPU (N = 8 is the config's 524288 global "
                          "batch); strong = the config's global batch of 524288 divided over the N GPUs (SURVEY.md §8d)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure: the cold-clock figure, the device clock and hwmon telemetry "
+                         "of the timed steps, per-step event minima, Model.call end to end, the other configs, sizes and "
+                         "precisions (extra.*), CPU baselines, conv2 gradients, and for N > 1 the one-GPU reference and the "
+                         "exchange timings.  A plain run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="matmul workload: write C of the last timed step to DIR/c.npy (float32; the whole product up to "
+                         "DUMP_BYTES, else a fixed, seeded sample of its rows, the same rows in every run)")
+    args = ap.parse_args()
+    workload = args.workload if args.workload != "auto" else "matmul" if args.gpus == 1 else "train"
+    if args.dump_outputs and workload != "matmul":
+        ap.error("--dump-outputs: the matmul workload only")
+    return args
 
 
 DEPENDENT_LAUNCH_US = 1.5   # boundary between two dependent launches inside a captured graph (MI355X_MICROARCH.md)
@@ -120,7 +133,29 @@ DEPENDENT_LAUNCH_US = 1.5   # boundary between two dependent launches inside a c
 SPINUP_S = float(os.environ.get("EG_BENCH_SPINUP_S", "0.2"))
 
 EVENTS_NOTE = ("kernel_ms_avg = one HIP event pair around the K timed steps / K, on the stream the kernels run on; "
-               "kernel_ms_min = shortest step of a second, untimed pass of K steps with an event pair each")
+               "kernel_ms_min = shortest step of a second, untimed pass of K steps with an event pair each (--full)")
+
+
+def kernel_ms_min(ev_min):
+    return {} if ev_min is None else {"kernel_ms_min": round(ev_min, 4)}
+
+
+# --dump-outputs: at most this many bytes per array; a larger output is written as a fixed, seeded sample of its rows
+DUMP_BYTES = 32 * 2 ** 20
+
+
+def output_sample(torch, t):
+    """A device tensor as --dump-outputs writes it, with a note of what that is: the whole tensor up to DUMP_BYTES, else
+    the rows a fixed seed picks (the same rows in every run of the same shape), gathered on the device."""
+    import numpy as np
+    if t.numel() * t.element_size() <= DUMP_BYTES:
+        return t.cpu().numpy(), {"shape": list(t.shape), "rows": "all"}
+    rows = t.reshape(t.shape[0], -1)
+    k = max(1, DUMP_BYTES // (rows.shape[1] * t.element_size()))
+    pick = np.sort(np.random.default_rng(0).choice(rows.shape[0], size=k, replace=False))
+    sample = rows.index_select(0, torch.as_tensor(pick, device=t.device)).cpu().numpy()
+    return sample, {"shape": list(t.shape), "rows": f"{k} of {rows.shape[0]}, numpy.random.default_rng(0).choice(rows, {k}, "
+                                                   "replace=False), ascending"}
 
 
 def clock_fields(telemetry, achieved_tflops, clock=None):
@@ -297,10 +332,11 @@ class Timer:
     """K steps bracketed by barrier + synchronize on both sides; max over ranks; per-step HIP
     events on the stream the kernels are launched on (torch's current stream == the context's)."""
 
-    def __init__(self, torch, dist, world, stream, telemetry=None, clock=None):
+    def __init__(self, torch, dist, world, stream, telemetry=None, clock=None, per_step_events=True):
         self.torch, self.dist, self.world, self.stream = torch, dist, world, stream
         self.telemetry, self.last_telemetry = telemetry, None
         self.clock, self.last_clock = clock, None
+        self.per_step_events = per_step_events   # the untimed pass behind the timed steps that gives kernel_ms_min
 
     def sync(self):
         self.torch.cuda.synchronize()
@@ -321,7 +357,8 @@ class Timer:
         self.sync()
         return time.perf_counter() - t0
 
-    def run(self, step, steps, warmup):
+    def run(self, step, steps, warmup, after_timed=None):
+        """after_timed(): called once the timed steps have finished, before any further step runs."""
         torch = self.torch
         # Untimed preparation, like the kernel builds that happen on the first call: keep the device
         # busy for ~0.2 s so the timed region runs at the sustained clock (tools/gemm_series.py: the
@@ -378,6 +415,8 @@ class Timer:
             self.clock.end()
         self.sync()
         elapsed = time.perf_counter() - t0
+        if after_timed is not None:
+            after_timed()
         if self.telemetry:
             self.last_telemetry = self.telemetry.stop()
         self.last_clock = None
@@ -396,11 +435,12 @@ class Timer:
             except Exception as exc:  # noqa: BLE001 - a secondary figure
                 self.last_clock = {"error": repr(exc)}
         bracket_ms = starts[0].elapsed_time(ends[0])
-        for i in range(steps):
-            starts[i].record(self.stream)
-            step()
-            ends[i].record(self.stream)
-        self.sync()
+        if self.per_step_events:
+            for i in range(steps):
+                starts[i].record(self.stream)
+                step()
+                ends[i].record(self.stream)
+            self.sync()
         gc.enable()
         if os.environ.get("EG_BENCH_DEBUG"):
             host = [round((b - a) * 1e6) for a, b in zip([t0] + marks[:-1], marks)]
@@ -409,8 +449,8 @@ class Timer:
             t = torch.tensor([elapsed], device="cuda", dtype=torch.float64)
             self.dist.all_reduce(t, op=self.dist.ReduceOp.MAX)
             elapsed = float(t.item())
-        ev = sorted(s.elapsed_time(e) for s, e in zip(starts, ends))
-        return elapsed, bracket_ms / steps, ev[0]
+        ev_min = min(s.elapsed_time(e) for s, e in zip(starts, ends)) if self.per_step_events else None
+        return elapsed, bracket_ms / steps, ev_min
 
 
 # ------------------------------------------------------------------------------ CPU baselines
@@ -582,30 +622,23 @@ def run_matmul(args, env):
     flops = 2.0 * n * n * n
     ops.sgemm(ctx, n, n, n, a, n, b, n, c, n)          # first call: module load, workspace
     timer.sync()
-    time.sleep(0.25)                                    # idle: the clocks fall back, as they are when a process starts
-    cold_s = timer.run_cold(lambda: ops.sgemm(ctx, n, n, n, a, n, b, n, c, n), args.steps, args.warmup)
-    elapsed, ev_avg, ev_min = timer.run(lambda: ops.sgemm(ctx, n, n, n, a, n, b, n, c, n), args.steps, args.warmup)
+    cold_s = None
+    if args.full:
+        time.sleep(0.25)                                # idle: the clocks fall back, as they are when a process starts
+        cold_s = timer.run_cold(lambda: ops.sgemm(ctx, n, n, n, a, n, b, n, c, n), args.steps, args.warmup)
+
+    def keep_outputs():                                 # C of the last timed step, before anything launches again
+        env["outputs"]["c"], env["outputs_note"]["c"] = output_sample(torch, c)
+    elapsed, ev_avg, ev_min = timer.run(lambda: ops.sgemm(ctx, n, n, n, a, n, b, n, c, n), args.steps, args.warmup,
+                                        after_timed=keep_outputs if args.dump_outputs else None)
     # ONE clock for `value` and the roofline fraction: the wall time of the K timed steps (barrier + synchronize on both
     # sides).  HIP events are reported next to it (kernel_ms_avg / kernel_ms_min, frac_by_events; EVENTS_NOTE).
     achieved = flops * args.steps / elapsed / 1e12
     achieved_events = flops / (ev_avg * 1e-3) / 1e12
-    # what the reference's benchmark times (matmul_gpu.nim:35-46): model.call with host tensors — 128 MiB
-    # host->device, the product, 64 MiB device->host per call.  Reported next to the kernel figure, never as `value`.
-    end_to_end = None
-    try:
-        end_to_end = _matmul_end_to_end(args, env, a, b, c, ctx, n, flops)
-    except Exception as exc:  # noqa: BLE001 - a secondary figure
-        end_to_end = {"error": repr(exc)}
-    return {
-        "end_to_end": end_to_end,
+    line = {
         "metric": "GFLOP/s matmul 4096^3 f32 (1 GPU)" if n == 4096 else f"GFLOP/s matmul {n}^3 f32",
         "value": round(flops * args.steps * env["world"] / elapsed / 1e9, 1), "unit": "GFLOP/s",
         "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-        "value_cold": {"value": round(flops * args.steps * env["world"] / cold_s / 1e9, 1), "unit": "GFLOP/s",
-                       "ms_per_step": round(cold_s / args.steps * 1e3, 4),
-                       "frac": round(flops * args.steps / cold_s / 1e12 / F32_MFMA_PEAK_TFLOPS, 4),
-                       "note": "the literal --warmup W / --steps K figure from an idle device (no spin-up in front): the "
-                               "first ~20 ms after idle run inside the clock ramp"},
         "config": {"workload": f"matmul M=N=K={n} float32 (BASELINE configs[1]): C = A*B through eg_sgemm "
                                "(MFMA + LDS tiled HIP kernel), A, B ~ U[0,1) resident in HBM",
                    "parallelism": "single" if env["world"] == 1 else f"{env['world']} independent replicas",
@@ -617,10 +650,23 @@ def run_matmul(args, env):
                      **(traffic_fields("matmul4096") if n == 4096 else {"traffic": None}),
                      "kernel": "eg::gemm::gemm_f32_mfma_kernel<256,256,32,128,64,NN,DMA> (skewed waves, 32-deep k-tiles)", "flops_per_launch": flops,
                      "clock": "wall time of the timed steps (the clock `value` uses)",
-                     "kernel_ms_avg": round(ev_avg, 4), "kernel_ms_min": round(ev_min, 4), "events": EVENTS_NOTE,
+                     "kernel_ms_avg": round(ev_avg, 4), **kernel_ms_min(ev_min), "events": EVENTS_NOTE,
                      "frac_by_events": round(achieved_events / F32_MFMA_PEAK_TFLOPS, 4)},
         "spinup_steps": timer.last_spin, "telemetry": timer.last_telemetry,
     }
+    if args.full:
+        line["value_cold"] = {"value": round(flops * args.steps * env["world"] / cold_s / 1e9, 1), "unit": "GFLOP/s",
+                              "ms_per_step": round(cold_s / args.steps * 1e3, 4),
+                              "frac": round(flops * args.steps / cold_s / 1e12 / F32_MFMA_PEAK_TFLOPS, 4),
+                              "note": "the literal --warmup W / --steps K figure from an idle device (no spin-up in front): the "
+                                      "first ~20 ms after idle run inside the clock ramp"}
+        # what the reference's benchmark times (matmul_gpu.nim:35-46): model.call with host tensors — 128 MiB
+        # host->device, the product, 64 MiB device->host per call.  Reported next to the kernel figure, never as `value`.
+        try:
+            line["end_to_end"] = _matmul_end_to_end(args, env, a, b, c, ctx, n, flops)
+        except Exception as exc:  # noqa: BLE001 - a secondary figure
+            line["end_to_end"] = {"error": repr(exc)}
+    return line
 
 
 def run_matmul_sizes(args, env):
@@ -915,7 +961,7 @@ def run_train(args, env):
     model, dp, x, y = build_dense(env, batch)
     inputs = [("x", x), ("y", y)]
     single = None
-    if world > 1:
+    if world > 1 and args.full:
         # the same step on this GPU's shard without the gradient exchange, in the same run: the
         # 1-GPU point of the scaling series (the N = 1 invocation reports matmul as its primary metric)
         eng = dp.engine
@@ -938,7 +984,7 @@ def run_train(args, env):
     elapsed, ev_avg, ev_min = env["timer"].run(step, args.steps, args.warmup)
     telemetry, device_clock = env["timer"].last_telemetry, env["timer"].last_clock
     exchange = None
-    if world > 1:
+    if world > 1 and args.full:
         # One run decides whether exchanging the early gradients under the last long contraction pays: the same step
         # with the split allowed and forbidden, and the bare all-reduce of the bucket, each over min(steps, 20) steps
         # AFTER the timed region (value / ms_per_step above are the default configuration's).
@@ -987,7 +1033,7 @@ def run_train(args, env):
                      **(traffic_fields("train") if batch == DENSE["batch"] else {"traffic": None}),
                      "kernel": "whole train step on one GPU (5 contractions dominate: gemm_f32_mfma_kernel)",
                      "flops_per_launch": step_flops, "clock": "wall time of the timed steps (the clock `value` uses)",
-                     "kernel_ms_avg": round(ev_avg, 4), "kernel_ms_min": round(ev_min, 4), "events": EVENTS_NOTE,
+                     "kernel_ms_avg": round(ev_avg, 4), **kernel_ms_min(ev_min), "events": EVENTS_NOTE,
                      "frac_by_events": round(achieved_events / F32_MFMA_PEAK_TFLOPS, 4)},
         "spinup_steps": env["timer"].last_spin, "telemetry": telemetry,
     }
@@ -1081,15 +1127,17 @@ def run_conv2(args, env):
     flops = 2.0 * N * (H - FH + 1) * (W - FW + 1) * F * FH * FW * C
     telemetry, device_clock = env["timer"].last_telemetry, env["timer"].last_clock
     achieved = flops * steps / elapsed / 1e12                          # the clock `value` uses (see run_matmul)
-    # the two gradients derive makes of conv2 (same FLOP count each), for the record
-    gout = torch.rand(out.shape, device="cuda", generator=gen) - 0.5
-    gflt, gimg = torch.empty_like(flt), torch.empty_like(img)
-    _, gf_avg, _ = env["timer"].run(
-        lambda: ops.conv2_nhwc_grad_filter(ctx, N, H, W, C, F, FH, FW, img, gout, gflt), steps, args.warmup)
-    _, gi_avg, _ = env["timer"].run(
-        lambda: ops.conv2_nhwc_grad_image(ctx, N, H, W, C, F, FH, FW, flt, gout, gimg), steps, args.warmup)
-    backward = {"grad_filter_ms": round(gf_avg, 4), "grad_filter_tflops": round(flops / (gf_avg * 1e-3) / 1e12, 2),
-                "grad_image_ms": round(gi_avg, 4), "grad_image_tflops": round(flops / (gi_avg * 1e-3) / 1e12, 2)}
+    backward = None
+    if args.full:
+        # the two gradients derive makes of conv2 (same FLOP count each), for the record
+        gout = torch.rand(out.shape, device="cuda", generator=gen) - 0.5
+        gflt, gimg = torch.empty_like(flt), torch.empty_like(img)
+        _, gf_avg, _ = env["timer"].run(
+            lambda: ops.conv2_nhwc_grad_filter(ctx, N, H, W, C, F, FH, FW, img, gout, gflt), steps, args.warmup)
+        _, gi_avg, _ = env["timer"].run(
+            lambda: ops.conv2_nhwc_grad_image(ctx, N, H, W, C, F, FH, FW, flt, gout, gimg), steps, args.warmup)
+        backward = {"grad_filter_ms": round(gf_avg, 4), "grad_filter_tflops": round(flops / (gf_avg * 1e-3) / 1e12, 2),
+                    "grad_image_ms": round(gi_avg, 4), "grad_image_tflops": round(flops / (gi_avg * 1e-3) / 1e12, 2)}
     return {"telemetry": telemetry, "metric": "GFLOP/s conv2 3x3 256x256x64->64 f32", "value": round(flops * steps / elapsed / 1e9, 1),
             "unit": "GFLOP/s", "ms_per_step": round(elapsed / steps * 1e3, 4),
             "config": {"workload": f"benchmarks/conv2 3x3, 1x256x256x64 -> 64 filters float32 NHWC (BASELINE configs[3]) through "
@@ -1323,8 +1371,10 @@ def main():
     # N > 1: the C ABI's own RCCL group unless --torch-dp; the one-GPU test mode has no second device for RCCL
     native = world > 1 and not args.torch_dp and not one_gpu
     env = {"torch": torch, "ops": ops, "ctx": ctx, "world": world, "rank": rank, "native_dp": native,
-           "timer": Timer(torch, dist, world, stream, Telemetry(torch, local_rank) if rank == 0 else None)}
-    if rank == 0 and world == 1 and os.environ.get("EG_BENCH_NO_DEVICE_CLOCK") != "1":
+           "timer": Timer(torch, dist, world, stream, Telemetry(torch, local_rank) if rank == 0 and args.full else None,
+                          per_step_events=args.full),
+           "outputs": {}, "outputs_note": {}}
+    if args.full and rank == 0 and world == 1 and os.environ.get("EG_BENCH_NO_DEVICE_CLOCK") != "1":
         try:
             env["timer"].clock = DeviceClock(ctx, local_rank)
         except Exception as exc:  # noqa: BLE001 - a secondary figure
@@ -1352,7 +1402,7 @@ def main():
     line = {**{k: line[k] for k in ("metric", "value", "unit")}, **base,
             **{k: v for k, v in line.items() if k not in ("metric", "value", "unit")}}
 
-    if world > 1 and workload == "train" and not args.no_extra:
+    if world > 1 and workload == "train" and args.full and not args.no_extra:
         # secondary figure; never allowed to take the primary line down with it (every rank runs it:
         # it contains collectives)
         try:
@@ -1360,7 +1410,7 @@ def main():
             line["extra"] = {"xor": run_xor_dp(small, env)}
         except Exception as exc:  # noqa: BLE001
             line["extra"] = {"xor": {"error": repr(exc)}}
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         if not args.no_extra and args.workload == "auto":
             # single-GPU numbers of the other BASELINE configs, same run (reference point for the
             # 1 -> N scaling of the data-parallel step: compare extra.train.value with the --gpus N value)
@@ -1420,6 +1470,12 @@ def main():
                     line["cpu_baseline"] = cpu_baseline_train(model.source_text)
             except Exception as exc:  # noqa: BLE001 - report, keep the measured line
                 line["cpu_baseline"] = {"error": repr(exc)}
+    if rank == 0 and args.dump_outputs:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, array in env["outputs"].items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), array)
+        line["outputs"] = {"dir": args.dump_outputs, **env["outputs_note"]}
     if rank == 0:
         try:  # which compiler built the generated kernels of this run (csrc/rtc.cpp)
             import ctypes

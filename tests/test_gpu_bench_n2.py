@@ -24,7 +24,7 @@ def test_bench_two_ranks_on_one_gpu(scaling):
     else:
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                "--master-port", "29518", os.path.join(ROOT, "bench.py"), "--gpus", "2"]
-    cmd += ["--steps", "4", "--warmup", "1", "--batch", "4096", "--scaling", scaling, "--no-extra"]
+    cmd += ["--steps", "4", "--warmup", "1", "--batch", "4096", "--scaling", scaling, "--no-extra", "--full"]
     out = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

@@ -1,8 +1,9 @@
 mkdir -p gpurun_out/r06c
-run() { env "$@" python bench.py --workload train --no-cpu-baseline --steps 40 --warmup 10 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('bench', d['ms_per_step'], d['roofline'].get('kernel_ms_avg'), d['roofline'].get('kernel_ms_min'))"; }
+REPO=$(cd "$(dirname "$0")/.." && pwd)
+run() { env "$@" python bench.py --full --workload train --no-cpu-baseline --steps 40 --warmup 10 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('bench', d['ms_per_step'], d['roofline'].get('kernel_ms_avg'), d['roofline'].get('kernel_ms_min'))"; }
 run X=1
 out=gpurun_out/gap_trace; rm -rf $out; mkdir -p $out
-(cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --output-format csv -d $GRAFT_REPO_ROOT/$out -o t -- python $GRAFT_REPO_ROOT/bench.py --workload train --no-cpu-baseline --steps 40 --warmup 10 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('bench under rocprofv3', d['ms_per_step'], d['roofline'].get('kernel_ms_avg'), d['roofline'].get('kernel_ms_min'))")
+(cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --output-format csv -d $REPO/$out -o t -- python $REPO/bench.py --full --workload train --no-cpu-baseline --steps 40 --warmup 10 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('bench under rocprofv3', d['ms_per_step'], d['roofline'].get('kernel_ms_avg'), d['roofline'].get('kernel_ms_min'))")
 f=$(find $out -name "*kernel_trace.csv" | head -1)
 python - "$f" <<'PY'
 import csv,sys,statistics

@@ -11,7 +11,7 @@ cd /tmp && export TMPDIR=/tmp
 # (no device-clock probe under the profiler: a --pmc pass may serialise dispatches across queues, and the probe wave waits for
 #  markers on the main stream; it would only give up after its 8 s guard)
 export EG_BENCH_NO_DEVICE_CLOCK=1
-CMD="python $REPO/bench.py --no-cpu-baseline --no-end-to-end $*"
+CMD="python $REPO/bench.py --full --no-cpu-baseline --no-end-to-end $*"
 # what the byte counts describe: bench.py flags roofline.traffic as stale when the sources differ from these
 (cd $REPO && python -c "import bench; print(bench.source_fingerprint())") > $OUT/source_fingerprint.txt
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- $CMD > $OUT/bench_trace.log 2>&1

@@ -1,6 +1,6 @@
 #!/bin/bash
 # The four profiled workloads of a round, condensed on the GPU box (the raw rocprofv3 output stays there):
-#   gpurun -- tools/profile_all.sh r06     ->  gpurun_out/summ/{r06_matmul,r06_train,r06_xor,r06_conv2,r06_hbm}, traffic.json, bench line
+#   tools/profile_all.sh r06  ->  the summaries {r06_matmul,r06_train,r06_xor,r06_conv2,r06_hbm} and traffic.json; the bench --full line in profiles/r06_bench_n1.json
 TAG=${1:-r02}
 REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 cd $REPO
@@ -16,5 +16,5 @@ python tools/summarize_profile.py gpurun_out/prof_${TAG}_conv2 gpurun_out/summ/$
 python tools/summarize_profile.py gpurun_out/prof_${TAG}_hbm gpurun_out/summ/${TAG}_hbm --note "bandwidth-bound library kernels (bench.py --workload hbm): 65536 x 512 float32 operands, four operand sets in rotation"
 rm -rf gpurun_out/prof_${TAG}_*
 cp gpurun_out/summ/traffic.json profiles/traffic.json      # (the box's copy: the bench line below reads it)
-python bench.py > gpurun_out/summ/${TAG}_bench_n1.json 2> gpurun_out/summ/bench_stderr.log
-tail -c 600 gpurun_out/summ/${TAG}_bench_n1.json
+python bench.py --full > profiles/${TAG}_bench_n1.json
+tail -c 600 profiles/${TAG}_bench_n1.json

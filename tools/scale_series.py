@@ -31,7 +31,7 @@ def visible_gpus():
 
 def run_point(n, scaling, steps, warmup, out_dir, extra):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--workload", "train", "--steps", str(steps),
-           "--warmup", str(warmup), "--scaling", scaling, "--no-extra"] + extra
+           "--warmup", str(warmup), "--scaling", scaling, "--no-extra", "--full"] + extra
     if n > 1:
         cmd.append("--no-cpu-baseline")
     log = os.path.join(out_dir, f"{scaling}_n{n}.log")
