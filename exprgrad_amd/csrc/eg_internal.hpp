@@ -68,6 +68,10 @@ struct eg_ctx {
   std::vector<hipEvent_t> pipe_events;  // batch pipeline (host/plan_pipeline.cpp): per-stage, per-half dependencies between the lanes
   eg::HostStager* stager = nullptr;  // created by the first large host copy
   float* ones = nullptr;             // {1,1,1,1, 1,0,0,0}: source of a contraction's virtual row of ones (GemmArgs::ones)
+  // split-bf16 product (kernels/gemm_split_bf16.hip): the word the split pass sets to split_epoch when an operand does not
+  // split exactly, and the value the current call gave it (advanced per call)
+  unsigned* split_flag = nullptr;
+  unsigned split_epoch = 0;
   int compute_units = 256;
   std::string arch;
   // kernels a library call specialises at run time (hiprtc) and keeps: by name

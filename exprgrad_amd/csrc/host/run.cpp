@@ -45,7 +45,7 @@ int run_launch(eg_model* m, TargetState& ts, Plan& plan, Launch& L) {
         rc = eg_colsum(ctx, L.K, L.N, tensor_ptr(m, ts, plan, L.b_tensor), tensor_ptr(m, ts, plan, L.ones_tensor), 0);
         if (rc) return rc;
       }
-      return eg_sgemm(ctx, L.trans_a, L.trans_b, L.M, L.N, L.K, tensor_ptr(m, ts, plan, L.a_tensor), L.lda,
+      return eg::gemm::sgemm_exact(ctx, L.trans_a, L.trans_b, L.M, L.N, L.K, tensor_ptr(m, ts, plan, L.a_tensor), L.lda,
                       tensor_ptr(m, ts, plan, L.b_tensor), L.ldb, tensor_ptr(m, ts, plan, L.c_tensor), L.ldc,
                       L.accumulate, L.bias_tensor ? tensor_ptr(m, ts, plan, L.bias_tensor) : nullptr);
     case StepKind::GemmFused: {
@@ -65,7 +65,7 @@ int run_launch(eg_model* m, TargetState& ts, Plan& plan, Launch& L) {
       const bool must_fuse = pe.pred_write || !pe.pred_reads.empty() || pe.row_product || !pe.store_c;
       if (f.splits > 1 && must_fuse) f.splits = 1;
       if (f.splits > 1) {
-        rc = eg_sgemm(ctx, L.trans_a, L.trans_b, L.M, L.N, L.K, tensor_ptr(m, ts, plan, L.a_tensor), L.lda,
+        rc = eg::gemm::sgemm_exact(ctx, L.trans_a, L.trans_b, L.M, L.N, L.K, tensor_ptr(m, ts, plan, L.a_tensor), L.lda,
                       tensor_ptr(m, ts, plan, L.b_tensor), L.ldb, tensor_ptr(m, ts, plan, L.c_tensor), L.ldc, 0, bias);
         if (rc) return rc;
         return run_launch(m, ts, plan, pe.consumer);
@@ -566,7 +566,7 @@ int run_launch_sliced(eg_model* m, TargetState& ts, Plan& plan, Launch& L, const
       float* C = tensor_ptr(m, ts, plan, L.c_tensor);
       const float* bias = L.bias_tensor ? tensor_ptr(m, ts, plan, L.bias_tensor) : nullptr;
       if (L.slice_mode == 1)  // rows of the batch: A(m, k) = A[m * lda + k]
-        return eg_sgemm(ctx, L.trans_a, L.trans_b, sl.rows, L.N, L.K, A + sl.row0 * L.lda, L.lda, B, L.ldb, C + sl.row0 * L.ldc,
+        return eg::gemm::sgemm_exact(ctx, L.trans_a, L.trans_b, sl.rows, L.N, L.K, A + sl.row0 * L.lda, L.lda, B, L.ldb, C + sl.row0 * L.ldc,
                         L.ldc, L.accumulate, bias);
       // the batch is K: A(k, m) = A[k * lda + m], B(k, n) = B[k * ldb + n]; the second half adds to the first
       const int accumulate = L.accumulate || sl.second;
@@ -579,7 +579,7 @@ int run_launch_sliced(eg_model* m, TargetState& ts, Plan& plan, Launch& L, const
         rc = eg_colsum(ctx, sl.rows, L.N, B, tensor_ptr(m, ts, plan, L.ones_tensor), sl.second ? 1 : 0);
         if (rc) return rc;
       }
-      return eg_sgemm(ctx, L.trans_a, L.trans_b, L.M, L.N, sl.rows, A, L.lda, B, L.ldb, C, L.ldc, accumulate, bias);
+      return eg::gemm::sgemm_exact(ctx, L.trans_a, L.trans_b, L.M, L.N, sl.rows, A, L.lda, B, L.ldb, C, L.ldc, accumulate, bias);
     }
     case StepKind::GemmFused: {
       PlanEpilogue& pe = *plan.epilogues[L.epilogue];

@@ -9,6 +9,7 @@
 // tile shape, split-K, vector/edge variant, launch, deterministic second pass.
 #include "gemm_skinny.hpp"
 #include "gemm_f32_pair.hpp"
+#include "gemm_fused.hpp"
 
 #include <algorithm>
 #include <cstdio>
@@ -934,9 +935,12 @@ int gemm_small_pair(eg_ctx* ctx, const SmallGemm& g0, const SmallGemm& g1) {
 }
 }  // namespace eg
 
-extern "C" int eg_sgemm(eg_ctx* ctx, int trans_a, int trans_b, int64_t M, int64_t N, int64_t K, const float* A,
-                        int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int accumulate,
-                        const float* bias) {
+namespace eg {
+namespace gemm {
+// The exact f32 product (v_mfma_f32_32x32x2_f32: a k-ordered fmaf chain per element).  Everything inside the library
+// (model plans, convolutions) calls this; only the public eg_sgemm may take the split-bf16 path first.
+int sgemm_exact(eg_ctx* ctx, int trans_a, int trans_b, long M, long N, long K, const float* A, long lda, const float* B, long ldb,
+                float* C, long ldc, int accumulate, const float* bias, const unsigned* run_if, unsigned run_if_val) {
   EG_REQUIRE(ctx, EG_ERR_INVALID, "eg_sgemm: ctx is NULL");
   EG_REQUIRE(M >= 0 && N >= 0 && K >= 0, EG_ERR_INVALID, "eg_sgemm: negative extent");
   if (M == 0 || N == 0) return EG_OK;
@@ -983,6 +987,8 @@ extern "C" int eg_sgemm(eg_ctx* ctx, int trans_a, int trans_b, int64_t M, int64_
   args.ldb = ldb;
   args.ldc = ldc;
   args.accumulate = accumulate;
+  args.run_if = run_if;
+  args.run_if_val = run_if_val;
   // 16-byte global loads need every row start and every chunk 16-byte aligned and whole.
   const long a_contig = a_kc ? K : M, b_contig = b_kc ? K : N;
   // (the LDS-DMA loaders address a tile with 32-bit byte offsets from its origin: 256 rows x ld x 4 bytes < 2^31)
@@ -990,6 +996,36 @@ extern "C" int eg_sgemm(eg_ctx* ctx, int trans_a, int trans_b, int64_t M, int64_
   const bool vec_b = (ldb % 4 == 0) && (b_contig % 4 == 0) && (B == nullptr || aligned16(B)) && ldb < (1L << 21);
   constexpr bool no_mixed = false;
   return run_gemm(ctx, a_kc, b_kc, args, /*conv=*/0, vec_a && vec_b, vec_a && !vec_b && !no_mixed);
+}
+
+// Does sgemm_exact run this product as ONE launch of the whole-tile 256 x 256 kernel (no k-slices, no tail slices, no
+// second pass)?  Only such a launch can stand behind the split-bf16 product as its device-side fallback: GemmArgs::run_if
+// gates gemm_block, not the reduce kernels.
+bool exact_single_launch(eg_ctx* ctx, int trans_a, int trans_b, long M, long N, long K, const float* A, long lda, const float* B,
+                         long ldb) {
+  if (M % 256 != 0 || N % 256 != 0 || K % 32 != 0 || K < 2048) return false;
+  const long a_contig = trans_a ? M : K, b_contig = trans_b ? K : N;
+  const bool vec_a = lda % 4 == 0 && a_contig % 4 == 0 && aligned16(A) && lda < (1L << 21);
+  const bool vec_b = ldb % 4 == 0 && b_contig % 4 == 0 && aligned16(B) && ldb < (1L << 21);
+  if (!vec_a || !vec_b) return false;
+  const long tiles = (M / 256) * (N / 256), slots = ctx->compute_units;
+  if ((M / 32) * (N / 32) <= 3 * slots) return false;  // the 32 x 32 eight-wave kernel's range (run_gemm)
+  if (tiles > slots && tiles % slots != 0 && (tiles % slots) * 2 <= slots) return false;  // tail slices
+  int bm = 0, bn = 0, splits = 0;
+  choose_tile(ctx, M, N, K, bm, bn, splits, true, true);
+  return bm == 256 && bn == 256 && splits <= 1;
+}
+}  // namespace gemm
+}  // namespace eg
+
+extern "C" int eg_sgemm(eg_ctx* ctx, int trans_a, int trans_b, int64_t M, int64_t N, int64_t K, const float* A,
+                        int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int accumulate,
+                        const float* bias) {
+  // large products whose operands split exactly run on the bf16 matrix cores (gemm_split_bf16.hip); the rest, and
+  // every product under EG_NO_SPLIT_GEMM=1, take the exact f32 path
+  const int rc = eg::gemm::sgemm_split(ctx, trans_a, trans_b, M, N, K, A, lda, B, ldb, C, ldc, accumulate, bias);
+  if (rc != EG_ERR_UNSUPPORTED) return rc;
+  return eg::gemm::sgemm_exact(ctx, trans_a, trans_b, M, N, K, A, lda, B, ldb, C, ldc, accumulate, bias);
 }
 
 // C[0..M) = op(A) * op(B) and C[M] = column sums of op(B) in ONE contraction: A gets a virtual last row
@@ -1057,7 +1093,7 @@ extern "C" int eg_conv2_nhwc(eg_ctx* ctx, int64_t N, int64_t H, int64_t W, int64
   int rc = eg::set_device(ctx);
   if (rc) return rc;
   if (FH == 1 && FW == 1 && C > 0)  // a 1x1 filter bank is a plain contraction over the channels: out[P,F] = img[P,C] * flt[F,C]^T
-    return eg_sgemm(ctx, 0, 1, N * H * W, F, C, img, C, flt, C, out, F, accumulate, nullptr);
+    return eg::gemm::sgemm_exact(ctx, 0, 1, N * H * W, F, C, img, C, flt, C, out, F, accumulate, nullptr);
   if (C > 0) {  // a few million multiply-adds in all (a batch-32 step of a small network): one thread per output element
     bool launched = false;
     rc = eg::conv2_tiny_forward_try(ctx, N, H, W, C, F, FH, FW, img, flt, out, accumulate, &launched);
@@ -1177,7 +1213,7 @@ extern "C" int eg_conv2_nhwc_grad_filter(eg_ctx* ctx, int64_t N, int64_t H, int6
   }
   EG_REQUIRE(img && gout, EG_ERR_INVALID, "eg_conv2_nhwc_grad_filter: NULL tensor");
   if (FH == 1 && FW == 1)  // plain contraction: gflt[F,C] = gout[P,F]^T * img[P,C]
-    return eg_sgemm(ctx, 1, 0, F, C, P, gout, F, img, C, gflt, C, accumulate, nullptr);
+    return eg::gemm::sgemm_exact(ctx, 1, 0, F, C, P, gout, F, img, C, gflt, C, accumulate, nullptr);
   {  // a few million multiply-adds in all: blocks of pixels, every output element per block, slabs folded in a fixed order
     bool launched = false;
     rc = eg::conv2_tiny_grad_filter_try(ctx, N, H, W, C, F, FH, FW, img, gout, gflt, accumulate, &launched);
@@ -1244,7 +1280,7 @@ extern "C" int eg_conv2_nhwc_grad_image(eg_ctx* ctx, int64_t N, int64_t H, int64
   }
   EG_REQUIRE(flt && gout, EG_ERR_INVALID, "eg_conv2_nhwc_grad_image: NULL tensor");
   if (FH == 1 && FW == 1)  // plain contraction: gimg[P,C] = gout[P,F] * flt[F,C]
-    return eg_sgemm(ctx, 0, 0, N * H * W, C, F, gout, F, flt, C, gimg, C, accumulate, nullptr);
+    return eg::gemm::sgemm_exact(ctx, 0, 0, N * H * W, C, F, gout, F, flt, C, gimg, C, accumulate, nullptr);
   {  // a few million multiply-adds in all: one thread per image element, no flipped bank, no padded gradient
     bool launched = false;
     rc = eg::conv2_tiny_grad_image_try(ctx, N, H, W, C, F, FH, FW, flt, gout, gimg, accumulate, &launched);
@@ -1301,7 +1337,6 @@ extern "C" int eg_conv2_nhwc_grad_image(eg_ctx* ctx, int64_t N, int64_t H, int64
 }
 
 // ---- contraction with a generated epilogue (gemm_fused.hpp) ----------------------------------------
-#include "gemm_fused.hpp"
 
 namespace {
 const char* const kGemmHeaderText =

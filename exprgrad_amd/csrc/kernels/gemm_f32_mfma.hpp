@@ -93,6 +93,11 @@ struct GemmArgs {
   int x_rows;
   // EG_GEMM_TRACE=1 (detector): four cycle stamps per wave — entry, in front of the k loop, behind it, behind the epilogue
   long long* trace;
+  // Device-side fallback of the split-bf16 product (gemm_split_bf16.hip): when run_if is set the blocks return at entry
+  // unless *run_if == run_if_val, i.e. the launch runs only when the split pass found an operand it cannot split exactly.
+  // nullptr on every other launch.
+  const unsigned* run_if;
+  unsigned run_if_val;
 };
 
 // Epilogue functor of the library kernels: plain store.  A generated epilogue (ACTIVE = true)
@@ -1070,6 +1075,7 @@ __device__ __forceinline__ void gemm_block(const GemmArgs& a) {
   const int wave = tid >> 6;
   const int wm0 = (wave / WAVES_N) * WM;
   const int wn0 = (wave % WAVES_N) * WN;
+  if (a.run_if && *(volatile const unsigned*)a.run_if != a.run_if_val) return;  // block-uniform, ahead of every barrier
   if (a.prio) __builtin_amdgcn_s_setprio(3);
   // (nothing of the trace stays live across the k loop: the pointer is re-read from the kernel arguments at every stamp —
   // kept in registers it cost the extra-row kernel, which has none to spare, 10 - 15 us)

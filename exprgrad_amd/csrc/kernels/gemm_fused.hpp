@@ -28,7 +28,7 @@ struct FusedLaunch {
   int narrow_k = 0;
   unsigned narrow_grid = 0;
   long matrix_k_per_split = 0;   // GemmArgs::k_per_split of the matrix tile (the streaming kernel reads its rows per block there)
-  alignas(8) unsigned char args[320];  // the kernel's GemmArgs (opaque to host-only translation units)
+  alignas(8) unsigned char args[336];  // the kernel's GemmArgs (opaque to host-only translation units)
   unsigned args_size = 0;
   unsigned waves = 0;   // per block (EG_GEMM_TRACE)
 };
@@ -38,6 +38,15 @@ constexpr int MAX_EPILOGUE_OPERANDS = 6;
 // except for the epilogue operands.
 int plan_fused(eg_ctx* ctx, int trans_a, int trans_b, long M, long N, long K, const float* A, long lda, const float* B,
                long ldb, float* C, long ldc, const float* bias, FusedLaunch& out);
+
+// The exact f32 product behind eg_sgemm (gemm_f32_mfma.hip); run_if: GemmArgs::run_if (nullptr: always runs).
+int sgemm_exact(eg_ctx* ctx, int trans_a, int trans_b, long M, long N, long K, const float* A, long lda, const float* B, long ldb,
+                float* C, long ldc, int accumulate, const float* bias, const unsigned* run_if = nullptr, unsigned run_if_val = 0);
+bool exact_single_launch(eg_ctx* ctx, int trans_a, int trans_b, long M, long N, long K, const float* A, long lda, const float* B,
+                         long ldb);
+// eg_sgemm's split-bf16 path (gemm_split_bf16.hip): EG_ERR_UNSUPPORTED, before any launch, when it does not apply.
+int sgemm_split(eg_ctx* ctx, int trans_a, int trans_b, long M, long N, long K, const float* A, long lda, const float* B, long ldb,
+                float* C, long ldc, int accumulate, const float* bias);
 
 // Weight gradient + bias gradient in one contraction (gemm_f32_mfma.hip): C[M + 1, N] = [op(A); 1] * op(B).
 bool ones_row_supported(int trans_a, int trans_b, long M, long N, long K, const float* A, long lda, const float* B, long ldb);

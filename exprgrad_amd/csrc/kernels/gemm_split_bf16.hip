@@ -1,0 +1,352 @@
+// Large f32 products of the public eg_sgemm on the bf16 matrix cores, by an exact three-way split of the operands.
+//
+// Every f32 operand element is cut into three bf16 pieces x = x0 + x1 + x2, each the round-to-nearest bf16 of the
+// remainder before it (x0 = bf16(x), x1 = bf16(x - x0), x2 = bf16(x - x0 - x1)).  For a normal x whose pieces stay
+// normal the three hold its 24 significand bits exactly.  The product then keeps the six terms down to 2^-16 of |ab|:
+//   a.b = a0b0 + (a0b1 + a1b0) + (a0b2 + a1b1 + a2b0)      (dropped: a1b2, a2b1, a2b2 <= ~2^-23 |ab|, signs random)
+// Each bf16 x bf16 product is exact in f32.  v_mfma_f32_32x32x16_bf16 does a 32x32x16 block in 32 cycles; the same
+// block costs 8 x 64 cycles on v_mfma_f32_32x32x2_f32, so the six terms take 2.67x fewer matrix cycles.
+//
+// Two launches, then the exact kernel behind them as a device-side fallback:
+//   1. split_planes_kernel: op(A) and op(B) of any layout and leading dimension -> three bf16 planes each, k-contiguous
+//      in 16-deep k-tiles ([plane][k / 16][row][16]: the 8 KiB a 256-row tile needs per plane and k-tile are one
+//      contiguous piece).  An element that does not split exactly (Inf, NaN, f32 subnormal, a piece that underflows,
+//      a value that rounds to Inf) sets the context's flag word to this call's epoch.
+//   2. split_gemm_kernel: 256 x 256 tiles, eight waves of 128 x 64, LDS-DMA stages of one 16-deep k-tile (3 planes x
+//      512 rows x 32 bytes = 48 KiB), three stages, one barrier per k-tile.  Returns at entry when the flag is set.
+//   3. the exact f32 kernel (sgemm_exact with GemmArgs::run_if): returns at entry unless the flag is set.
+// Only shapes whose exact product is one whole-tile launch qualify (exact_single_launch), so the fallback is one launch.
+#include <algorithm>
+#include <cfloat>
+
+#include "gemm_fused.hpp"
+#include "../eg_internal.hpp"
+#include "../switches.hpp"
+
+namespace {
+
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+// ---- 1. the split pass ------------------------------------------------------------------------------------------------
+
+// op(X) is R x K: X[r * ld + k] when k-contiguous (kc), X[k * ld + r] otherwise.  R % 32 == 0, K % 32 == 0.
+struct SplitOperand {
+  const float* src;
+  long ld;
+  long R;
+  int kc;
+  __bf16* dst;  // 3 planes of R * K
+};
+
+// A unit is 8 consecutive k of one row: 32 bytes in, 16 bytes out per plane.  The 64 units of a wave cover 16 rows x 4
+// units when k-contiguous (4 x 128-byte reads; 2 x 512-byte plane rows out) and 32 rows x 2 units otherwise (each of the
+// 8 loads reads 2 x 128 bytes of two k-rows; 1 KiB plane rows out).
+__device__ __forceinline__ void unit_coords(const SplitOperand& o, long K, long u, long& r, long& chunk) {
+  const long cpr = K / 8, t = u >> 6;
+  const int l = (int)(u & 63);
+  if (o.kc) {
+    const long per = cpr / 4;
+    r = (t / per) * 16 + (l >> 2);
+    chunk = (t % per) * 4 + (l & 3);
+  } else {
+    const long per = cpr / 2;
+    r = (t / per) * 32 + (l >> 1);
+    chunk = (t % per) * 2 + (l & 1);
+  }
+}
+
+__device__ __forceinline__ void load_unit(const SplitOperand& o, long r, long chunk, float (&x)[8]) {
+  if (o.kc) {
+    const f32x4* p = reinterpret_cast<const f32x4*>(o.src + r * o.ld + chunk * 8);
+    const f32x4 v0 = __builtin_nontemporal_load(p), v1 = __builtin_nontemporal_load(p + 1);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      x[j] = v0[j];
+      x[4 + j] = v1[j];
+    }
+  } else {
+    const float* p = o.src + chunk * 8 * o.ld + r;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) x[j] = __builtin_nontemporal_load(p + j * o.ld);
+  }
+}
+
+// x = x0 + x1 + x2 exactly, or `bad`.  The casts are v_cvt_pk_bf16_f32 (round to nearest even; NaN stays NaN).  Both
+// subtractions are exact while nothing underflows or overflows, so the split is exact iff the last remainder is x2.
+__device__ __forceinline__ void split_unit(const SplitOperand& o, long K, long r, long chunk, const float (&x)[8], bool& bad) {
+  bf16x8 h0, h1, h2;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const float v = x[j];
+    const __bf16 b0 = (__bf16)v;
+    const float r1 = v - (float)b0;
+    const __bf16 b1 = (__bf16)r1;
+    const float f1 = (float)b1;
+    const float r2 = r1 - f1;
+    const __bf16 b2 = (__bf16)r2;
+    const float f2 = (float)b2;
+    bad |= !(r2 == f2);                                         // Inf, NaN, a value that rounds to Inf
+    bad |= v != 0.f && __builtin_fabsf(v) < FLT_MIN;           // f32 subnormal
+    bad |= (f1 != 0.f && __builtin_fabsf(f1) < FLT_MIN) || (f2 != 0.f && __builtin_fabsf(f2) < FLT_MIN);  // a piece underflows
+    h0[j] = b0;
+    h1[j] = b1;
+    h2[j] = b2;
+  }
+  const long plane = o.R * K;
+  bf16x8* d = reinterpret_cast<bf16x8*>(o.dst + ((chunk >> 1) * o.R + r) * 16 + (chunk & 1) * 8);
+  const long ps = plane / 8;  // plane stride in 16-byte units
+  d[0] = h0;
+  d[ps] = h1;
+  d[2 * ps] = h2;
+}
+
+constexpr int SPLIT_NT = 256;
+constexpr int SPLIT_U = 2;  // units per thread in flight
+
+// Units [0, units_a) are op(A)'s, the rest op(B)'s.  A block owns one contiguous chunk (a multiple of SPLIT_NT * SPLIT_U,
+// so a wave's 64 units never straddle the two operands: units_a is a multiple of 64).
+__global__ __launch_bounds__(SPLIT_NT) void split_planes_kernel(SplitOperand a, SplitOperand b, long K, long units_a, long units,
+                                                              unsigned* flag, unsigned epoch) {
+  constexpr long STEP = (long)SPLIT_NT * SPLIT_U;
+  const long per = ((units + gridDim.x - 1) / gridDim.x + STEP - 1) / STEP * STEP;
+  const long lo = (long)blockIdx.x * per, hi = lo + per < units ? lo + per : units;
+  bool bad = false;
+  for (long base = lo; base < hi; base += STEP) {
+    float x[SPLIT_U][8];
+    long r[SPLIT_U], c[SPLIT_U];
+#pragma unroll
+    for (int i = 0; i < SPLIT_U; ++i) {
+      const long u = base + i * SPLIT_NT + threadIdx.x;
+      if (u >= hi) continue;
+      const bool in_a = u < units_a;
+      unit_coords(in_a ? a : b, K, in_a ? u : u - units_a, r[i], c[i]);
+      load_unit(in_a ? a : b, r[i], c[i], x[i]);
+    }
+#pragma unroll
+    for (int i = 0; i < SPLIT_U; ++i) {
+      const long u = base + i * SPLIT_NT + threadIdx.x;
+      if (u >= hi) continue;
+      split_unit(u < units_a ? a : b, K, r[i], c[i], x[i], bad);
+    }
+  }
+  if (__builtin_expect(bad, 0)) *(volatile unsigned*)flag = epoch;
+}
+
+// ---- 2. the product ---------------------------------------------------------------------------------------------------
+
+constexpr int BM = 256, BN = 256, WM = 128, WN = 64, NT = 512;
+constexpr int STAGES = 3;
+constexpr int PLANE_BYTES = BM * 16 * 2;                  // one plane of one operand for one 16-deep k-tile: 8 KiB
+constexpr int STAGE_BYTES = 6 * PLANE_BYTES;               // A planes 0..2, then B planes 0..2: 48 KiB
+constexpr int LOADS = STAGE_BYTES / (NT * 16);             // 16-byte LDS-DMA pieces per thread and stage: 6
+
+struct SplitGemmArgs {
+  const __bf16* pa;  // op(A) planes, M * K each
+  const __bf16* pb;  // op(B) planes, N * K each
+  float* C;
+  const float* bias;
+  long M, N, K, ldc;
+  int tiles_m, tiles_n;
+  int accumulate;
+  const unsigned* flag;
+  unsigned epoch;
+};
+
+// Tile order of the exact kernel (gemm_f32_mfma.hpp xcd_remap / tile_origin): every XCD gets a contiguous range of
+// block ids, and those walk groups of 8 tile rows column-major, so co-resident tiles share panels inside one L2.
+__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
+  constexpr int NXCD = 8;
+  const int q = nwg / NXCD, r = nwg % NXCD;
+  const int xcd = bid % NXCD, local = bid / NXCD;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + local;
+}
+__device__ __forceinline__ void tile_origin(int wgid, int tiles_m, int tiles_n, long& m_blk, long& n_blk) {
+  constexpr int GROUP = 8;
+  const int per_group = GROUP * tiles_n;
+  const int first_m = (wgid / per_group) * GROUP;
+  const int gsize = min(tiles_m - first_m, GROUP);
+  const int in_group = wgid % per_group;
+  m_blk = (long)(first_m + in_group % gsize) * BM;
+  n_blk = (long)(in_group / gsize) * BN;
+}
+
+__device__ __forceinline__ const void* uniform_ptr(const void* p) {
+  const unsigned long v = reinterpret_cast<unsigned long>(p);
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+  return reinterpret_cast<const void*>(((unsigned long)hi << 32) | lo);
+}
+
+__global__ __launch_bounds__(NT) void split_gemm_kernel(SplitGemmArgs a) {
+  if (*(volatile const unsigned*)a.flag == a.epoch) return;  // an operand did not split: the exact kernel behind runs
+  __shared__ __attribute__((aligned(16))) unsigned char lds[STAGES * STAGE_BYTES];
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wr = wave >> 2, wc = wave & 3;  // 2 x 4 waves of 128 x 64
+  long m_blk, n_blk;
+  tile_origin(xcd_remap(blockIdx.x, gridDim.x), a.tiles_m, a.tiles_n, m_blk, n_blk);
+
+  // buffer descriptors of the block's row panels: operand origin + first row; k-tile and plane go in the scalar offset
+  const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<void*>(uniform_ptr(a.pa + m_blk * 16)), (short)0, -1, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<void*>(uniform_ptr(a.pb + n_blk * 16)), (short)0, -1, 0x00020000);
+  const unsigned a_plane = (unsigned)(a.M * a.K * 2), b_plane = (unsigned)(a.N * a.K * 2);
+  const unsigned a_ktile = (unsigned)(a.M * 32), b_ktile = (unsigned)(a.N * 32);
+  const unsigned voff = (unsigned)tid * 16;
+
+  // a wave's 1 KiB of each 8 KiB piece: LDS destination = wave base + lane * 16 (lane-linear, like the global source)
+  auto issue = [&](int kt, int s) {
+    unsigned char* st = lds + s * STAGE_BYTES + wave * 1024;
+#pragma unroll
+    for (int i = 0; i < LOADS; ++i) {
+      __attribute__((address_space(3))) void* dst = (__attribute__((address_space(3))) void*)(st + i * PLANE_BYTES);
+      if (i < 3)
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, dst, 16, voff, (unsigned)i * a_plane + (unsigned)kt * a_ktile, 0, 0);
+      else
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, dst, 16, voff, (unsigned)(i - 3) * b_plane + (unsigned)kt * b_ktile, 0, 0);
+    }
+  };
+
+  f32x16 acc[4][2];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+  // fragment of lane l: row (l & 31) of its 32-row block, k = 8 (l >> 5) .. + 7 — 16 bytes at row * 32 + (l >> 5) * 16,
+  // so a wave's ds_read_b128 reads 1 KiB in a row (no bank conflicts, no swizzle)
+  const int a_off = (wr * WM + (lane & 31)) * 32 + (lane >> 5) * 16;
+  const int b_off = 3 * PLANE_BYTES + (wc * WN + (lane & 31)) * 32 + (lane >> 5) * 16;
+
+  const int KT = (int)(a.K / 16);
+  issue(0, 0);
+  if (KT > 1) issue(1, 1);
+  int s = 0;
+  for (int kt = 0; kt < KT; ++kt) {
+    // this wave's pieces of k-tile kt have landed (those of kt + 1 may still fly); the barrier makes every wave's visible
+    // and says every wave is done reading k-tile kt - 1, whose stage the next issue refills
+    if (kt + 1 < KT) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    if (kt + 2 < KT) issue(kt + 2, s == 0 ? 2 : s - 1);
+    const unsigned char* st = lds + s * STAGE_BYTES;
+    bf16x8 fa[3][4], fb[3][2];
+    // read in the order the terms use them: the 2^-16 terms first (a2 b0, a1 b1, a0 b2), then 2^-8, then a0 b0
+#pragma unroll
+    for (int j = 0; j < 2; ++j) fb[0][j] = *reinterpret_cast<const bf16x8*>(st + b_off + j * 1024);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) fa[2][i] = *reinterpret_cast<const bf16x8*>(st + 2 * PLANE_BYTES + a_off + i * 1024);
+#pragma unroll
+    for (int j = 0; j < 2; ++j) fb[1][j] = *reinterpret_cast<const bf16x8*>(st + PLANE_BYTES + b_off + j * 1024);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) fa[1][i] = *reinterpret_cast<const bf16x8*>(st + PLANE_BYTES + a_off + i * 1024);
+#pragma unroll
+    for (int j = 0; j < 2; ++j) fb[2][j] = *reinterpret_cast<const bf16x8*>(st + 2 * PLANE_BYTES + b_off + j * 1024);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) fa[0][i] = *reinterpret_cast<const bf16x8*>(st + a_off + i * 1024);
+    constexpr int TERMS[6][2] = {{2, 0}, {1, 1}, {0, 2}, {1, 0}, {0, 1}, {0, 0}};
+#pragma unroll
+    for (int t = 0; t < 6; ++t)
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[TERMS[t][0]][i], fb[TERMS[t][1]][j], acc[i][j], 0, 0, 0);
+    s = s == STAGES - 1 ? 0 : s + 1;
+  }
+
+  // C/D map of the 32x32 forms: column lane & 31, row (r & 3) + 8 (r >> 2) + 4 (lane >> 5).  M, N are whole tiles.
+  const long row0 = m_blk + wr * WM + 4 * (lane >> 5), col0 = n_blk + wc * WN + (lane & 31);
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const long col = col0 + j * 32;
+    const float bv = a.bias ? a.bias[col] : 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        float* c = a.C + (row0 + i * 32 + (r & 3) + 8 * (r >> 2)) * a.ldc + col;
+        float v = acc[i][j][r];
+        if (a.accumulate) v = *c + v;
+        if (a.bias) v = v + bv;
+        *c = v;
+      }
+  }
+}
+
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// Largest plane set (6 (M + N) K bytes) the context's workspace grows to for it: 4096^3 needs 192 MiB.
+constexpr size_t kPlaneCap = 1ull << 30;
+
+}  // namespace
+
+namespace eg {
+namespace gemm {
+
+int sgemm_split(eg_ctx* ctx, int trans_a, int trans_b, long M, long N, long K, const float* A, long lda, const float* B, long ldb,
+                float* C, long ldc, int accumulate, const float* bias) {
+  // anything the exact entry would refuse or that does not qualify goes there untouched
+  if (!ctx || !A || !B || !C || M <= 0 || N <= 0 || K <= 0) return EG_ERR_UNSUPPORTED;
+  if (lda < (trans_a ? M : K) || ldb < (trans_b ? K : N) || ldc < N) return EG_ERR_UNSUPPORTED;
+  if (eg::sw::on("EG_NO_SPLIT_GEMM")) return EG_ERR_UNSUPPORTED;
+  // Shape gate: whole 256 x 256 tiles that fill the chip at least once (smaller products keep the exact path: none of
+  // them is bound by matrix cycles the way a full round is), and an exact product that is one launch (the fallback).
+  if (M % BM != 0 || N % BN != 0 || K % 32 != 0) return EG_ERR_UNSUPPORTED;
+  if ((M / BM) * (N / BN) < ctx->compute_units) return EG_ERR_UNSUPPORTED;
+  const size_t plane_bytes = 6 * (size_t)(M + N) * (size_t)K;
+  // (the product kernel's buffer offsets are 32-bit: three planes of one operand below 2^31 bytes)
+  if (plane_bytes > kPlaneCap || 6 * (size_t)std::max(M, N) * (size_t)K >= (1ull << 31)) return EG_ERR_UNSUPPORTED;
+  if (!aligned16(A) || !aligned16(B) || (!trans_a && lda % 4 != 0) || (trans_b && ldb % 4 != 0)) return EG_ERR_UNSUPPORTED;
+  if (!exact_single_launch(ctx, trans_a, trans_b, M, N, K, A, lda, B, ldb)) return EG_ERR_UNSUPPORTED;
+
+  int rc = eg::set_device(ctx);
+  if (rc) return rc;
+  if (!ctx->split_flag) {
+    EG_HIP_CHECK(hipMalloc((void**)&ctx->split_flag, sizeof(unsigned)));
+    EG_HIP_CHECK(hipMemset(ctx->split_flag, 0, sizeof(unsigned)));
+  }
+  rc = eg::ensure_workspace(ctx, plane_bytes);
+  if (rc) return rc;
+  if (++ctx->split_epoch == 0) ctx->split_epoch = 1;  // 0 is the flag's initial value
+  const unsigned epoch = ctx->split_epoch;
+
+  __bf16* pa = static_cast<__bf16*>(ctx->workspace);
+  __bf16* pb = pa + 3 * (size_t)M * K;
+  const SplitOperand oa = {A, lda, M, trans_a ? 0 : 1, pa};
+  const SplitOperand ob = {B, ldb, N, trans_b ? 1 : 0, pb};
+  const long units_a = M * K / 8, units = (M + N) * K / 8;
+  long blocks = (units + SPLIT_NT * SPLIT_U - 1) / (SPLIT_NT * SPLIT_U);
+  if (blocks > 8L * ctx->compute_units) blocks = 8L * ctx->compute_units;
+  hipLaunchKernelGGL(split_planes_kernel, dim3((unsigned)blocks), dim3(SPLIT_NT), 0, ctx->stream, oa, ob, K, units_a, units,
+                     ctx->split_flag, epoch);
+  EG_HIP_CHECK(hipGetLastError());
+
+  SplitGemmArgs g = {};
+  g.pa = pa;
+  g.pb = pb;
+  g.C = C;
+  g.bias = bias;
+  g.M = M;
+  g.N = N;
+  g.K = K;
+  g.ldc = ldc;
+  g.tiles_m = (int)(M / BM);
+  g.tiles_n = (int)(N / BN);
+  g.accumulate = accumulate;
+  g.flag = ctx->split_flag;
+  g.epoch = epoch;
+  hipLaunchKernelGGL(split_gemm_kernel, dim3((unsigned)(g.tiles_m * g.tiles_n)), dim3(NT), 0, ctx->stream, g);
+  EG_HIP_CHECK(hipGetLastError());
+
+  // the exact product, run only when the split pass set the flag
+  return sgemm_exact(ctx, trans_a, trans_b, M, N, K, A, lda, B, ldb, C, ldc, accumulate, bias, ctx->split_flag, epoch);
+}
+
+}  // namespace gemm
+}  // namespace eg

@@ -266,6 +266,7 @@ int eg_ctx_destroy(eg_ctx* ctx) {
   if (ctx->side_stream) hipStreamDestroy(ctx->side_stream);
   eg::host_stager_free(ctx->stager);
   if (ctx->ones) hipFree(ctx->ones);
+  if (ctx->split_flag) hipFree(ctx->split_flag);
   for (auto& kv : ctx->jit) delete kv.second;  // eg_kernel: the code object goes with it
   if (ctx->owns_stream && ctx->stream) hipStreamDestroy(ctx->stream);
   delete ctx;

@@ -144,7 +144,12 @@ int eg_kernel_launch(eg_kernel* kernel, int dims, const int64_t* groups, const i
  * Covers matmul (base.nim:27-28), dense forward with its bias kernel folded in
  * (dnn.nim:19-24), and the two derived gradient contractions of passes.nim:519-549:
  *   gradA[y,it] += g[y,x]*B[it,x]  -> trans_b = 1      gradB[it,x] += A[y,it]*g[y,x] -> trans_a = 1
- * bias may be NULL. */
+ * bias may be NULL.
+ * Large products (M, N multiples of 256 with at least one 256 x 256 tile per CU, K a multiple of 32 and >= 2048) run
+ * as six bf16 matrix-core terms of an exact three-way operand split (kernels/gemm_split_bf16.hip): not bit-identical
+ * to the exact f32 path, with an error against float64 no larger than its own.  An operand with
+ * Inf, NaN, an f32 subnormal or a value that does not split exactly makes the call run the exact path instead, decided
+ * on the device.  EG_NO_SPLIT_GEMM=1 keeps every product on the exact path.  Model plans always use the exact path. */
 int eg_sgemm(eg_ctx* ctx, int trans_a, int trans_b, int64_t M, int64_t N, int64_t K,
              const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc,
              int accumulate, const float* bias);
