@@ -4,16 +4,19 @@
 // remainder before it (x0 = bf16(x), x1 = bf16(x - x0), x2 = bf16(x - x0 - x1)).  For a normal x whose pieces stay
 // normal the three hold its 24 significand bits exactly.  The product then keeps the six terms down to 2^-16 of |ab|:
 //   a.b = a0b0 + (a0b1 + a1b0) + (a0b2 + a1b1 + a2b0)      (dropped: a1b2, a2b1, a2b2 <= ~2^-23 |ab|, signs random)
-// Each bf16 x bf16 product is exact in f32.  v_mfma_f32_32x32x16_bf16 does a 32x32x16 block in 32 cycles; the same
-// block costs 8 x 64 cycles on v_mfma_f32_32x32x2_f32, so the six terms take 2.67x fewer matrix cycles.
+// Each bf16 x bf16 product is exact in f32.  One v_mfma_f32_16x16x32_bf16 (16 cycles) takes two terms of a 16 x 16 x 16
+// block, so the six terms are three instructions, 48 cycles; the block costs 4 x 32 cycles on v_mfma_f32_16x16x4_f32, so
+// the split takes 2.67x fewer matrix cycles.  (The 16x16x32 shape holds a higher clock under load than 32x32x16 at the
+// same cycles per FLOP.)
 //
 // Two launches, then the exact kernel behind them as a device-side fallback:
 //   1. split_planes_kernel: op(A) and op(B) of any layout and leading dimension -> three bf16 planes each, k-contiguous
 //      in 16-deep k-tiles ([plane][k / 16][row][16]: the 8 KiB a 256-row tile needs per plane and k-tile are one
 //      contiguous piece).  An element that does not split exactly (Inf, NaN, f32 subnormal, a piece that underflows,
 //      a value that rounds to Inf) sets the context's flag word to this call's epoch.
-//   2. split_gemm_kernel: 256 x 256 tiles, eight waves of 128 x 64, LDS-DMA stages of one 16-deep k-tile (3 planes x
-//      512 rows x 32 bytes = 48 KiB), three stages, one barrier per k-tile.  Returns at entry when the flag is set.
+//   2. split_gemm_kernel: 256 x 256 tiles, eight waves of 128 x 64 (8 x 4 blocks of 16 x 16), LDS-DMA stages of one
+//      16-deep k-tile (3 planes x 512 rows x 32 bytes = 48 KiB), three stages, one barrier per k-tile, C written through
+//      LDS as 16-byte row pieces.  Returns at entry when the flag is set.
 //   3. the exact f32 kernel (sgemm_exact with GemmArgs::run_if): returns at entry unless the flag is set.
 // Only shapes whose exact product is one whole-tile launch qualify (exact_single_launch), so the fallback is one launch.
 #include <algorithm>
@@ -26,7 +29,6 @@
 namespace {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // ---- 1. the split pass ------------------------------------------------------------------------------------------------
@@ -209,18 +211,24 @@ __global__ __launch_bounds__(NT) void split_gemm_kernel(SplitGemmArgs a) {
     }
   };
 
-  f32x16 acc[4][2];
+  f32x4 acc[8][4];
 #pragma unroll
-  for (int i = 0; i < 4; ++i)
+  for (int i = 0; i < 8; ++i)
 #pragma unroll
-    for (int j = 0; j < 2; ++j)
+    for (int j = 0; j < 4; ++j)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+      for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.f;
 
-  // fragment of lane l: row (l & 31) of its 32-row block, k = 8 (l >> 5) .. + 7 — 16 bytes at row * 32 + (l >> 5) * 16,
-  // so a wave's ds_read_b128 reads 1 KiB in a row (no bank conflicts, no swizzle)
-  const int a_off = (wr * WM + (lane & 31)) * 32 + (lane >> 5) * 16;
-  const int b_off = 3 * PLANE_BYTES + (wc * WN + (lane & 31)) * 32 + (lane >> 5) * 16;
+  // v_mfma_f32_16x16x32_bf16: lane l holds row (l & 15) of its 16-row block at k = 8 (l >> 4) .. + 7.  The k of a 16-deep
+  // k-tile sit in lane groups 0-1, and groups 2-3 take the same k of another plane: one MFMA sums two terms.  So the
+  // lane's plane is picked by sel = l >> 5 and its half of the 32-byte row by (l >> 4) & 1; per 16 x 16 block
+  //   [a0 | a1] x [b2 | b1] = a0b2 + a1b1,   [a0 | a1] x [b1 | b0] = a0b1 + a1b0,   [a0 | a2] x [b0 | b0] = a0b0 + a2b0.
+  // The 16 lanes of each ds_read_b128 bank group hit 16 distinct 16-byte bank quads (no conflicts, no swizzle).
+  const int sel = lane >> 5;
+  const int a_row = (wr * WM + (lane & 15)) * 32 + ((lane >> 4) & 1) * 16;
+  const int b_row = 3 * PLANE_BYTES + (wc * WN + (lane & 15)) * 32 + ((lane >> 4) & 1) * 16;
+  const int a01_off = a_row + sel * PLANE_BYTES, a02_off = a_row + 2 * sel * PLANE_BYTES;
+  const int b21_off = b_row + (2 - sel) * PLANE_BYTES, b10_off = b_row + (1 - sel) * PLANE_BYTES, b00_off = b_row;
 
   const int KT = (int)(a.K / 16);
   issue(0, 0);
@@ -235,47 +243,57 @@ __global__ __launch_bounds__(NT) void split_gemm_kernel(SplitGemmArgs a) {
     asm volatile("" ::: "memory");
     if (kt + 2 < KT) issue(kt + 2, s == 0 ? 2 : s - 1);
     const unsigned char* st = lds + s * STAGE_BYTES;
-    bf16x8 fa[3][4], fb[3][2];
-    // read in the order the terms use them: the 2^-16 terms first (a2 b0, a1 b1, a0 b2), then 2^-8, then a0 b0
+    bf16x8 fb21[4], fb10[4], fb00[4];
 #pragma unroll
-    for (int j = 0; j < 2; ++j) fb[0][j] = *reinterpret_cast<const bf16x8*>(st + b_off + j * 1024);
+    for (int j = 0; j < 4; ++j) {
+      fb21[j] = *reinterpret_cast<const bf16x8*>(st + b21_off + j * 512);
+      fb10[j] = *reinterpret_cast<const bf16x8*>(st + b10_off + j * 512);
+      fb00[j] = *reinterpret_cast<const bf16x8*>(st + b00_off + j * 512);
+    }
+    // per block the 2^-16 pair first, then the 2^-8 pair, then a0b0 with a2b0
 #pragma unroll
-    for (int i = 0; i < 4; ++i) fa[2][i] = *reinterpret_cast<const bf16x8*>(st + 2 * PLANE_BYTES + a_off + i * 1024);
+    for (int i = 0; i < 8; ++i) {
+      const bf16x8 fa01 = *reinterpret_cast<const bf16x8*>(st + a01_off + i * 512);
+      const bf16x8 fa02 = *reinterpret_cast<const bf16x8*>(st + a02_off + i * 512);
 #pragma unroll
-    for (int j = 0; j < 2; ++j) fb[1][j] = *reinterpret_cast<const bf16x8*>(st + PLANE_BYTES + b_off + j * 1024);
+      for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa01, fb21[j], acc[i][j], 0, 0, 0);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) fa[1][i] = *reinterpret_cast<const bf16x8*>(st + PLANE_BYTES + a_off + i * 1024);
+      for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa01, fb10[j], acc[i][j], 0, 0, 0);
 #pragma unroll
-    for (int j = 0; j < 2; ++j) fb[2][j] = *reinterpret_cast<const bf16x8*>(st + 2 * PLANE_BYTES + b_off + j * 1024);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) fa[0][i] = *reinterpret_cast<const bf16x8*>(st + a_off + i * 1024);
-    constexpr int TERMS[6][2] = {{2, 0}, {1, 1}, {0, 2}, {1, 0}, {0, 1}, {0, 0}};
-#pragma unroll
-    for (int t = 0; t < 6; ++t)
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[TERMS[t][0]][i], fb[TERMS[t][1]][j], acc[i][j], 0, 0, 0);
+      for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa02, fb00[j], acc[i][j], 0, 0, 0);
+    }
     s = s == STAGES - 1 ? 0 : s + 1;
   }
 
-  // C/D map of the 32x32 forms: column lane & 31, row (r & 3) + 8 (r >> 2) + 4 (lane >> 5).  M, N are whole tiles.
-  const long row0 = m_blk + wr * WM + 4 * (lane >> 5), col0 = n_blk + wc * WN + (lane & 31);
+  // The sub-tile leaves through LDS as 16-byte row pieces (the 16x16 C/D map, column lane & 15 and row 4 (lane >> 4) + r,
+  // would store 64-byte pieces).  Each wave parks half of its 128 x 64 sub-tile at a time in a 16 KiB region of its own
+  // ([row][64] floats; 2-way on the b32 writes, which costs nothing, none on the b128 reads) and writes it back as
+  // 4 rows x 256 bytes per instruction.  The barrier: every wave is done reading the last k-tile's stage.
+  __syncthreads();
+  float* park = reinterpret_cast<float*>(lds) + wave * 64 * WN;
+  const int prow = lane >> 4, pc4 = (lane & 15) * 4;
+  const long col = n_blk + wc * WN + pc4;
+  f32x4 b4 = {0.f, 0.f, 0.f, 0.f};
+  if (a.bias) b4 = *reinterpret_cast<const f32x4*>(a.bias + col);
 #pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const long col = col0 + j * 32;
-    const float bv = a.bias ? a.bias[col] : 0.f;
+  for (int h = 0; h < 2; ++h) {
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        float* c = a.C + (row0 + i * 32 + (r & 3) + 8 * (r >> 2)) * a.ldc + col;
-        float v = acc[i][j][r];
-        if (a.accumulate) v = *c + v;
-        if (a.bias) v = v + bv;
-        *c = v;
-      }
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) park[(i * 16 + 4 * prow + r) * WN + j * 16 + (lane & 15)] = acc[4 * h + i][j][r];
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // (one wave: its LDS accesses complete in order)
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      const int row = 4 * q + prow;
+      f32x4 v = *reinterpret_cast<const f32x4*>(park + row * WN + pc4);
+      f32x4* c = reinterpret_cast<f32x4*>(a.C + (m_blk + wr * WM + h * 64 + row) * a.ldc + col);
+      if (a.accumulate) v = *c + v;
+      if (a.bias) v = v + b4;
+      *c = v;
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   }
 }
 
@@ -303,6 +321,7 @@ int sgemm_split(eg_ctx* ctx, int trans_a, int trans_b, long M, long N, long K, c
   // (the product kernel's buffer offsets are 32-bit: three planes of one operand below 2^31 bytes)
   if (plane_bytes > kPlaneCap || 6 * (size_t)std::max(M, N) * (size_t)K >= (1ull << 31)) return EG_ERR_UNSUPPORTED;
   if (!aligned16(A) || !aligned16(B) || (!trans_a && lda % 4 != 0) || (trans_b && ldb % 4 != 0)) return EG_ERR_UNSUPPORTED;
+  if (!aligned16(C) || ldc % 4 != 0 || (bias && !aligned16(bias))) return EG_ERR_UNSUPPORTED;  // 16-byte C row pieces
   if (!exact_single_launch(ctx, trans_a, trans_b, M, N, K, A, lda, B, ldb)) return EG_ERR_UNSUPPORTED;
 
   int rc = eg::set_device(ctx);
