@@ -42,8 +42,9 @@ int plan_fused(eg_ctx* ctx, int trans_a, int trans_b, long M, long N, long K, co
 // The exact f32 product behind eg_sgemm (gemm_f32_mfma.hip); run_if: GemmArgs::run_if (nullptr: always runs).
 int sgemm_exact(eg_ctx* ctx, int trans_a, int trans_b, long M, long N, long K, const float* A, long lda, const float* B, long ldb,
                 float* C, long ldc, int accumulate, const float* bias, const unsigned* run_if = nullptr, unsigned run_if_val = 0);
+// Does sgemm_exact run this product as one whole-tile launch (gemm_plan.hpp, exact_single_launch)?
 bool exact_single_launch(eg_ctx* ctx, int trans_a, int trans_b, long M, long N, long K, const float* A, long lda, const float* B,
-                         long ldb);
+                         long ldb, const float* C, long ldc, const float* bias);
 // eg_sgemm's split-bf16 path (gemm_split_bf16.hip): EG_ERR_UNSUPPORTED, before any launch, when it does not apply.
 int sgemm_split(eg_ctx* ctx, int trans_a, int trans_b, long M, long N, long K, const float* A, long lda, const float* B, long ldb,
                 float* C, long ldc, int accumulate, const float* bias);

@@ -1,0 +1,108 @@
+// Host-side planning of the f32 contraction (gemm_f32_mfma.hip): which kernel runs a product, on which tile, with how
+// many k-slices, which second pass and how much workspace.  Plain C++ (no HIP): the launch code turns a GemmPlan into
+// kernel launches, and tests/test_gemm_plan_cpu.py checks plans without a GPU.
+#pragma once
+
+namespace eg {
+namespace gemm {
+
+constexpr int BK = 16;   // k-tile depth of the four-wave kernel unless a route says otherwise
+
+// One contraction C[M, N] (+)= op(A) * op(B) (+ bias) as the planner sees it: extents, layouts and alignment facts.
+struct GemmProblem {
+  long M = 0, N = 0, K = 0;
+  bool a_kc = true, b_kc = false;   // operand k-contiguous (A row-major untransposed, B transposed)
+  long lda = 0, ldb = 0, ldc = 0;
+  bool a_aligned = true, b_aligned = true, c_aligned = true;   // 16-byte aligned base pointers
+  bool has_bias = false, bias_aligned = true;
+  bool ones_row = false;   // A has a virtual last row of ones (GemmArgs::ones_row)
+  int conv = 0;            // 0: plain; 1: forward implicit-GEMM gather of A; 2: filter gradient (B gathered)
+  bool vec_ok = false, a_vec_only = false;   // both operands / only A qualify for 16-byte loads (operand_vec)
+  bool piece = false;      // a piece of a remainder split: planned without the small and skinny kernels
+  int cus = 256;
+};
+
+// The switches the planner reads, filled by the caller (the planner reads no environment variable).
+struct GemmSwitches {
+  bool no_small = false, no_skinny = false;                     // EG_NO_SMALL_GEMM, EG_NO_SKINNY_GEMM
+  bool no_pair = false, no_t96 = false, no_streamk = false;     // EG_GEMM_NO_PAIR / _NO_T96 / _NO_STREAMK
+  bool no_xrow = false, no_bk32 = false, no_wide_store = false; // EG_GEMM_NO_XROW / _NO_BK32 / _NO_WIDE_STORE
+  bool no_skew = false, old_tile_model = false, small_bk32 = false;   // EG_GEMM_NO_SKEW / _OLD_TILE_MODEL / _SMALL_BK32
+  bool debug_tile = false, trace = false;                       // EG_DEBUG_TILE, EG_GEMM_TRACE
+  bool force_tile = false, force_splits = false, streamk_blocks = false;   // EG_GEMM_FORCE_TILE / _FORCE_SPLITS,
+  int force_bm = 0, force_bn = 0, force_splits_n = 0;                     // EG_STREAMK_BLOCKS_PER_CU are set, to
+  long streamk_blocks_per_cu = 0;                                         // "bm,bn" / n / n
+  double streamk_min_ratio = 24.0;                              // EG_STREAMK_MIN_RATIO
+};
+
+// Routes in the order they are tried (plan_gemm explains each).  Remainder: the pieces in GemmPlan::parts, each
+// planned and run on its own.
+enum class Route { Small, Skinny, Kw8, T96, StreamK, Remainder, ExtraRows, Bk32, Pair, Generic };
+enum class Second { None, SplitReduce, TailReduce, StreamKFixup, Tree };   // Tree: slab sum, or the tree column sum
+
+// Waves of the four-wave kernel's tiles: each wave owns a WM x WN block; MINB blocks per CU.
+struct TileWaves {
+  int wm, wn, minb;
+};
+constexpr TileWaves tile_waves(int bm, int bn) {
+  return bn == 32                ? TileWaves{32, 32, 4}
+         : bn == 64 && bm == 256 ? TileWaves{64, 32, 2}
+         : bn == 64 && bm == 64  ? TileWaves{32, 32, 4}
+         : bn == 64              ? TileWaves{64, 32, 4}
+         : bn == 128             ? TileWaves{64, 64, 4}
+                                 : TileWaves{128, 64, 1};
+}
+
+struct GemmPlan {
+  Route route = Route::Generic;
+  int bm = 0, bn = 0, kb = BK;
+  TileWaves waves = {};
+  int vec = 4;           // Generic: 4 (16-byte loads), 41 (A 16-byte, B scalar; 128 x 32 only), 1 (scalar)
+  bool edge = false;     // the clamped form for ragged tiles (Kw8 / Pair: also for a K that ends inside a k-tile)
+  // GemmArgs fields
+  int tiles_m = 0, tiles_n = 0, splits = 1;
+  long k_per_split = 0;
+  int edge_splits = 0;
+  long k_per_split_edge = 0;
+  int tail_tiles = 0, tail_splits = 0;
+  long tail_k_per_split = 0;
+  int x_rows = 0;
+  bool wide_store = false, no_skew = false;
+  bool nt_store = true;  // wide stores of whole tiles are nontemporal: no launch reads its output again (4096^3: 137.1 -> 139.0 TFLOP/s)
+  bool prio = true;      // raise the issue priority when launched on the side lane
+  long grid = 0;   // main launch: grid x block threads
+  int block = 0;
+  // second pass (SplitReduce / Tree fold `splits` slabs; the last tile row's edge_splits slabs)
+  Second second = Second::None;
+  long workspace_floats = 0; // slabs; a Tree pass adds the column sum's scratch behind them
+  int nparts = 0;            // Remainder: the pieces
+  struct { long row0, col0, M, N; } parts[3] = {};
+};
+
+// 16-byte global loads of an operand need every row start and every chunk 16-byte aligned and whole (contig: the
+// extent along its contiguous axis).  The LDS-DMA loaders address a tile with 32-bit byte offsets from its origin:
+// 256 rows x ld x 4 bytes < 2^31.
+inline bool operand_vec(long ld, long contig, bool aligned) { return ld % 4 == 0 && contig % 4 == 0 && aligned && ld < (1L << 21); }
+
+// The one-wave-per-output kernel's range (without EG_NO_SMALL_GEMM).
+bool small_suits(long M, long N, long K);
+
+// Tile shape and split count for an M x N x K contraction on `cus` compute units.
+void choose_tile(long M, long N, long K, int cus, const GemmSwitches& sw, int& bm, int& bn, int& splits, bool vec = true,
+                 bool plain = true);
+
+// The generic tile of a product: choose_tile (its time model told whether the operands are 16-byte: model_vec), the
+// tile's waves and the load variant of 16-deep k-tiles.  plan_gemm starts from it; fused launches run it as it is.
+GemmPlan generic_tile(const GemmProblem& p, const GemmSwitches& sw, bool model_vec);
+
+// Whole tiles leave through LDS as 16-byte stores (GemmArgs::wide_store).
+bool wide_store_ok(const GemmProblem& p, const GemmSwitches& sw, bool to_partial, bool fused = false);
+
+GemmPlan plan_gemm(const GemmProblem& p, const GemmSwitches& sw);
+
+// Is the plan ONE launch of the whole-tile 256 x 256 kernel (no k-slices, tail slices or second pass)?  Only such a launch
+// can stand behind the split-bf16 product as its fallback: GemmArgs::run_if gates the tile kernel, not the reduce kernels.
+bool exact_single_launch(const GemmPlan& p);
+
+}  // namespace gemm
+}  // namespace eg

@@ -313,16 +313,16 @@ int sgemm_split(eg_ctx* ctx, int trans_a, int trans_b, long M, long N, long K, c
   if (!ctx || !A || !B || !C || M <= 0 || N <= 0 || K <= 0) return EG_ERR_UNSUPPORTED;
   if (lda < (trans_a ? M : K) || ldb < (trans_b ? K : N) || ldc < N) return EG_ERR_UNSUPPORTED;
   if (eg::sw::on("EG_NO_SPLIT_GEMM")) return EG_ERR_UNSUPPORTED;
-  // Shape gate: whole 256 x 256 tiles that fill the chip at least once (smaller products keep the exact path: none of
-  // them is bound by matrix cycles the way a full round is), and an exact product that is one launch (the fallback).
-  if (M % BM != 0 || N % BN != 0 || K % 32 != 0) return EG_ERR_UNSUPPORTED;
+  // Shape gate: whole 256 x 256 tiles that fill the chip at least once and K >= 2048 (smaller products keep the exact path:
+  // none of them is bound by matrix cycles the way a full round is), and an exact product that is one launch (the fallback).
+  if (M % BM != 0 || N % BN != 0 || K % 32 != 0 || K < 2048) return EG_ERR_UNSUPPORTED;
   if ((M / BM) * (N / BN) < ctx->compute_units) return EG_ERR_UNSUPPORTED;
   const size_t plane_bytes = 6 * (size_t)(M + N) * (size_t)K;
   // (the product kernel's buffer offsets are 32-bit: three planes of one operand below 2^31 bytes)
   if (plane_bytes > kPlaneCap || 6 * (size_t)std::max(M, N) * (size_t)K >= (1ull << 31)) return EG_ERR_UNSUPPORTED;
   if (!aligned16(A) || !aligned16(B) || (!trans_a && lda % 4 != 0) || (trans_b && ldb % 4 != 0)) return EG_ERR_UNSUPPORTED;
   if (!aligned16(C) || ldc % 4 != 0 || (bias && !aligned16(bias))) return EG_ERR_UNSUPPORTED;  // 16-byte C row pieces
-  if (!exact_single_launch(ctx, trans_a, trans_b, M, N, K, A, lda, B, ldb)) return EG_ERR_UNSUPPORTED;
+  if (!exact_single_launch(ctx, trans_a, trans_b, M, N, K, A, lda, B, ldb, C, ldc, bias)) return EG_ERR_UNSUPPORTED;
 
   int rc = eg::set_device(ctx);
   if (rc) return rc;

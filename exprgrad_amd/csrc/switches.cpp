@@ -129,7 +129,9 @@ struct Cache {
       set[i] = 1;
     }
     loaded = true;
+    ++generation;
   }
+  unsigned generation = 0;
 };
 Cache& cache() {
   static Cache c;
@@ -151,6 +153,13 @@ const char* raw(const char* name) {
     return nullptr;
   }
   return c.set[it->second] ? c.value[it->second].c_str() : nullptr;
+}
+
+unsigned generation() {
+  Cache& c = cache();
+  std::lock_guard<std::mutex> lock(c.mu);
+  if (!c.loaded) c.load();
+  return c.generation;
 }
 
 void reload() {

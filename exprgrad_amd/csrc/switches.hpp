@@ -31,6 +31,8 @@ inline double real(const char* name, double dflt) {
   return e ? atof(e) : dflt;
 }
 void reload();
+// Bumped by every (re)load of the table: code that keeps values derived from switches reads them again when it changes.
+unsigned generation();
 
 }  // namespace sw
 }  // namespace eg

@@ -371,7 +371,7 @@ def test_tail_tiles_are_cut_along_k(gpu_ctx, case):
     # skinny outputs next to the wide-tile model's boundary
     (8192, 128, 512, False, False, False, False), (100, 8192, 512, False, False, True, True), (65, 65, 5000, True, False, False, False)])
 def test_mid_size_and_remainder_contractions(gpu_ctx, case):
-    """The tile / slice choices of the calibrated time model (gemm_f32_mfma.hip: wide_tile_time) and the
+    """The tile / slice choices of the calibrated time model (kernels/gemm_plan.cpp: wide_tile_time) and the
     remainder split of large ragged outputs, against a float64 product; two runs bit-identical."""
     M, N, K, ta, tb, acc, bias = case
     rng = np.random.default_rng(7 * M + 3 * N + K)
