@@ -280,6 +280,18 @@ const char* eg_model_launch_text(eg_model* m, const char* target) {
         if (L.tail_launch >= 0) os << " | which goes on with launch " << L.tail_launch << " when a range holds both";
         break;
       }
+      case StepKind::WideRows: {
+        const PlanRowGroup& pg = *plan.row_groups[L.row_group];
+        os << "wide-row-fused " << pg.g.name << " W=" << pg.g.W << " " << pg.g.kernel_index.size() << " kernels (";
+        for (size_t ki = 0; ki < pg.g.kernel_index.size(); ++ki) {
+          const int wt = ts.target->all[pg.g.kernel_index[ki]].write.tensor;
+          const std::string& nm = m->prog.tensors[wt].name;
+          os << (ki ? ", " : "") << (nm.empty() || nm == "-" ? "t" + std::to_string(wt) : nm);
+        }
+        os << "), one wave per sample, grid " << pg.nblocks << " x 256";
+        if (pg.g.red_total > 0) os << " | " << pg.red_tensors.size() << " batch sums folded by row_finalize";
+        break;
+      }
       case StepKind::SampleFused: {
         const PlanSampleGroup& sg = *plan.sample_group;
         os << "sample-fused " << sg.g.kernel_index.size() << " kernels, one block per sample (" << sg.g.B << " blocks)";

@@ -48,7 +48,8 @@ struct ConvMatch {
   enum Role { Forward, GradImage, GradFilter } role = Forward;
 };
 
-enum class StepKind { Gemm, Conv, ConvGradImage, ConvGradFilter, Seed, GenericA, GenericB, RowFused, SmallFused, GemmFused, SampleFused };
+// WideRows: a row group with one wave per sample (rowfuse.hpp); Launch::row_group indexes Plan::row_groups as for RowFused
+enum class StepKind { Gemm, Conv, ConvGradImage, ConvGradFilter, Seed, GenericA, GenericB, RowFused, SmallFused, GemmFused, SampleFused, WideRows };
 
 struct Generic {
   GenericSource src;

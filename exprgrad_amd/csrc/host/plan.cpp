@@ -373,7 +373,7 @@ int make_plan(eg_model* m, TargetState& ts, Plan& plan) {
       if (p == 0 || group_of[p - 1] != group_of[p]) {  // first kernel of the group: one launch for all
         Launch L;
         L.lowered = (int)p;
-        L.kind = StepKind::RowFused;
+        L.kind = plan.row_groups[group_of[p]]->g.W > 0 ? StepKind::WideRows : StepKind::RowFused;
         L.row_group = group_of[p];
         L.accumulate = false;
         plan.launches.push_back(L);

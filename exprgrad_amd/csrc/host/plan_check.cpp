@@ -94,6 +94,7 @@ void launch_io(eg_model* m, TargetState& ts, const Plan& plan, const Launch& L, 
       wr(L.consumer >= 0 ? L.c_tensor : k.write.tensor, L.accumulate);
       break;
     }
+    case StepKind::WideRows:   // the same roles (rowfuse.hpp): [B] tensors are rows of one float
     case StepKind::RowFused: {
       const PlanRowGroup& pg = *plan.row_groups[L.row_group];
       for (auto& kv : pg.g.tensors) {
@@ -179,6 +180,7 @@ int check_plan(eg_model* m, TargetState& ts, Plan& plan) {
     };
     for (const Launch& L : plan.launches) {
       switch (L.kind) {
+        case StepKind::WideRows:
         case StepKind::RowFused:
           for (int ki : plan.row_groups[L.row_group]->g.kernel_index) mark(pos_of_all.count(ki) ? pos_of_all[ki] : -1);
           break;

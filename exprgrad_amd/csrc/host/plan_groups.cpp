@@ -39,7 +39,7 @@ int fuse_row_tails(eg_model* m, TargetState& ts, Plan& plan, const std::vector<K
   for (int i = 0; i + 1 < (int)plan.launches.size(); ++i) {
     Launch& R = plan.launches[i];
     Launch& S = plan.launches[i + 1];
-    if (R.kind != StepKind::RowFused || S.kind != StepKind::SmallFused) continue;
+    if (R.kind != StepKind::RowFused || S.kind != StepKind::SmallFused) continue;   // (StepKind::WideRows: no tail, its fold is row_finalize)
     PlanRowGroup& pg = *plan.row_groups[R.row_group];
     if (!pg.g.in_kernel_finalize || pg.tail_group >= 0 || in_overlap(i) || in_overlap(i + 1)) continue;
     PlanSmallGroup& sg = *plan.small_groups[S.row_group];
@@ -437,6 +437,167 @@ int form_sample_group(eg_model* m, TargetState& ts, Plan& plan, const std::vecto
   return EG_OK;
 }
 
+// Wide row groups (rowfuse.hpp, "one wave per sample"): among the kernels the thread-per-sample analysis refused, runs of
+// wide row kernels over one width W in 65 .. 4096.  Decided from the shapes alone.  A group's launch is StepKind::WideRows:
+// it shares PlanRowGroup, the partial rows and row_finalize with the thread-per-sample groups, and takes no part in row
+// tails, deferred folds or the batch pipeline.
+static int form_wide_groups(eg_model* m, TargetState& ts, Plan& plan, const std::vector<KernelInfo>& infos,
+                            const std::map<int, int>& first_writer, std::vector<int>& group_of, long B) {
+  Target& t = *ts.target;
+  const Shapes& shapes = plan.shapes;
+  const int n = (int)t.live.size();
+  // the tensor of an inlined producer exists in no memory: a member reads it from a member's registers or not at all
+  std::set<int> inlined;
+  for (int p = 0; p < n; ++p)
+    if (ts.lowered[p].inlined) inlined.insert(t.all[t.live[p]].write.tensor);
+  auto gemm_result = [&](int tensor, int before) {
+    for (int s = 0; s < before; ++s)
+      if (ts.lowered[s].kind == StepKind::Gemm && !ts.lowered[s].absorbed && t.all[t.live[s]].write.tensor == tensor) return true;
+    return false;
+  };
+  constexpr long RED_MAX = 2 * WIDE_MAX_W + 64;  // floats of a partial row; four of them in LDS (at most 130 KB)
+  int p = 0;
+  while (p < n) {
+    const long W = group_of[p] == -1 ? wide_width_of(t.all[t.live[p]], shapes, B) : 0;
+    if (W < WIDE_MIN_W || W > WIDE_MAX_W) {
+      ++p;
+      continue;
+    }
+    std::unique_ptr<PlanRowGroup> pg(new PlanRowGroup());
+    RowGroup& g = pg->g;
+    g.B = B;
+    g.W = W;
+    const long NJ = (W + 63) / 64;
+    int q = p;
+    while (q < n && group_of[q] == -1 && !(q != p && q == t.first_update) && !(p < t.first_update && q >= t.first_update && t.first_update >= 0)) {
+      const Kernel& k = t.all[t.live[q]];
+      const WideKernelInfo wi = analyse_wide_kernel(m->prog, k, infos[t.live[q]], shapes, B, W);
+      if (!wi.ok) break;
+      // a bias folded into a library contraction is not available on its own
+      if (ts.lowered[q].absorbed && !ts.lowered[q].inlined) break;
+      // an elementwise map over a contraction's result is that contraction's epilogue candidate (plan_epilogue.cpp): a
+      // group does not begin by taking it away
+      if (q == p && wi.kind == WideKernelInfo::Map) {
+        bool consumer = false;
+        for (auto& rd : k.reads) consumer = consumer || gemm_result(rd.tensor, q);
+        if (consumer) break;
+      }
+      std::map<int, RowGroupTensor> roles = g.tensors;
+      bool ok = true;
+      const int yreg = wi.row_loop >= 0 ? k.loops[wi.row_loop].reg : 0;
+      auto touch = [&](const Op& op, bool write) {
+        auto it = roles.find(op.tensor);
+        RowGroupTensor gt;
+        if (it != roles.end()) gt = it->second;
+        gt.tensor = op.tensor;
+        bool row = false;
+        for (auto& d : op.dims) row = row || (yreg && d.factor_of(yreg));
+        if (it != roles.end() && row != (gt.role == RowGroupTensor::RowLocal || gt.role == RowGroupTensor::RowExternal)) ok = false;
+        if (row) {
+          gt.inner = prod(shapes.at(op.tensor)) / B;
+          if (write) gt.role = RowGroupTensor::RowLocal;
+          else if (it == roles.end()) gt.role = RowGroupTensor::RowExternal;
+          if (!write && it == roles.end() && inlined.count(op.tensor)) ok = false;  // (its producer is not a member)
+        } else {
+          gt.inner = prod(shapes.at(op.tensor));
+          if (write) {
+            const RowGroupTensor::Role want = wi.seed ? RowGroupTensor::SmallLocal : RowGroupTensor::Reduction;
+            if (it != roles.end() && gt.role != want) ok = false;  // (read earlier in the group)
+            gt.role = want;
+          } else {
+            if (it != roles.end() && gt.role == RowGroupTensor::Reduction) ok = false;  // needs the grid-wide total
+            if (it == roles.end()) gt.role = RowGroupTensor::SmallExternal;
+          }
+        }
+        roles[op.tensor] = gt;
+      };
+      for (auto& rd : k.reads) touch(rd, false);
+      touch(k.write, true);
+      if (ok && wi.seed) {
+        // lane-local recomputation only: the tensor must not exist outside the group
+        const int wt = k.write.tensor;
+        auto fw = first_writer.find(wt);
+        if (fw == first_writer.end() || fw->second != q || wt == t.output) ok = false;
+      }
+      long state = 0, reds = 0;
+      int segs = 0;
+      for (auto& kv : roles) {
+        const RowGroupTensor& gt = kv.second;
+        // per-lane state: [B, W] rows and per-column accumulators; a [B] value or the seed is one value per wave
+        if (gt.role == RowGroupTensor::RowLocal && gt.inner == W) state += NJ;
+        if (gt.role == RowGroupTensor::Reduction) {
+          state += gt.inner == W ? NJ : 1;
+          reds += gt.inner;
+          ++segs;
+        }
+      }
+      if (state > WIDE_STATE_MAX || reds > RED_MAX || segs > 16) ok = false;
+      if (!ok) break;
+      g.tensors = roles;
+      g.kernel_index.push_back(t.live[q]);
+      g.wide.push_back(wi);
+      ++q;
+    }
+    int row_kernels = 0;
+    for (auto& wi : g.wide)
+      if (!wi.seed) ++row_kernels;
+    auto written_outside_before = [&](int tensor) {
+      for (int s = 0; s < p; ++s)
+        if (t.all[t.live[s]].write.tensor == tensor) return true;
+      return false;
+    };
+    auto used_after = [&](int tensor) {
+      if (tensor == t.output) return true;
+      for (int s = q; s < n; ++s) {
+        const Kernel& k = t.all[t.live[s]];
+        if (k.write.tensor == tensor) return true;
+        for (auto& rd : k.reads)
+          if (rd.tensor == tensor) return true;
+      }
+      return false;
+    };
+    bool usable = q - p >= 2 && row_kernels >= 2;
+    for (auto& kv : g.tensors)  // a lane-local seed somebody outside the group wants
+      if (kv.second.role == RowGroupTensor::SmallLocal && (used_after(kv.first) || written_outside_before(kv.first))) usable = false;
+    if (!usable) {
+      p = std::max(q, p + 1);
+      continue;
+    }
+    long red_off = 0;
+    for (auto& kv : g.tensors) {
+      RowGroupTensor& gt = kv.second;
+      if (gt.role == RowGroupTensor::RowLocal) {
+        gt.load_first = written_outside_before(kv.first);
+        // (the readers of an inlined producer's tensor recompute it: it is stored nowhere)
+        gt.store = used_after(kv.first) && !inlined.count(kv.first);
+      } else if (gt.role == RowGroupTensor::Reduction) {
+        const TK kind = m->prog.tensors[kv.first].kind;
+        gt.accumulate = kind != TK::Result || written_outside_before(kv.first);
+        gt.red_offset = red_off;
+        red_off += gt.inner;
+        pg->red_tensors.push_back(kv.first);
+      }
+    }
+    g.red_total = red_off;
+    char name[64];
+    snprintf(name, sizeof(name), "eg_wrows%d", m->kernel_serial++);
+    g.name = name;
+    pg->nblocks = (int)((B + 255) / 256);  // the grid of a row group; a block's four waves share its 256 samples
+    int rc = generate_wide_group(m->prog, t.all, infos, shapes, g);
+    if (rc) return rc;
+    plan.pending.push_back({g.name, g.source, &pg->handle});
+    if (g.red_total > 0) {
+      EG_HIP_CHECK(hipSetDevice(m->ctx->device));
+      EG_HIP_CHECK(hipMalloc((void**)&pg->partial, (size_t)pg->nblocks * g.red_stride() * sizeof(float)));
+    }
+    const int gi = (int)plan.row_groups.size();
+    for (int s = p; s < q; ++s) group_of[s] = gi;
+    plan.row_groups.push_back(std::move(pg));
+    p = q;
+  }
+  return EG_OK;
+}
+
 // Partition the live kernel list into row groups (rowfuse.hpp) and build their kernels.
 // group_of[p] = index into plan.row_groups, or -1 for kernels that keep their own launch.
 int form_row_groups(eg_model* m, TargetState& ts, Plan& plan, const std::vector<KernelInfo>& infos,
@@ -652,6 +813,10 @@ int form_row_groups(eg_model* m, TargetState& ts, Plan& plan, const std::vector<
     for (int s = p; s < q; ++s) group_of[s] = gi;
     plan.row_groups.push_back(std::move(pg));
     p = q;
+  }
+  {
+    int rc = form_wide_groups(m, ts, plan, infos, first_writer, group_of, B);
+    if (rc) return rc;
   }
   // ---- small-kernel groups among what is left (encoded as -2 - index in group_of)
   p = 0;

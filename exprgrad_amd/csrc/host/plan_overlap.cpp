@@ -110,7 +110,7 @@ void plan_overlap(eg_model* m, TargetState& ts, Plan& plan) {
       for (int r = first - 1; !keep_tail && r >= 0 && r >= first - 3; --r) {
         const Launch& R = plan.launches[r];
         if (r + 1 == plan.n_backward) break;
-        if (R.kind != StepKind::RowFused) continue;
+        if (R.kind != StepKind::RowFused) continue;   // (StepKind::WideRows has no in-kernel fold to defer)
         const PlanRowGroup& pg = *plan.row_groups[R.row_group];
         if (pg.g.single_block || pg.g.red_total <= 0 || pg.tail_group >= 0 || !pg.g.in_kernel_finalize) break;
         std::set<int> totals;

@@ -41,6 +41,37 @@ struct RowKernelInfo {
 RowKernelInfo analyse_row_kernel(const Program& prog, const Kernel& k, const KernelInfo& info, const Shapes& shapes,
                                  long B);
 
+// ---- wide rows: one WAVE per sample ----------------------------------------------------------------
+// Rows of 65 .. 4096 floats (a classification head with 100 or 1000 classes) do not fit one thread's registers.  The same
+// chain — softmax.sums, softmax, the loss gradient, softmax's three gradient kernels, the bias gradient — runs as one
+// generated kernel in which a wave owns a sample: lane l holds the columns x = l + 64 j, j = 0 .. ceil(W / 64) - 1, so
+// that every load of a wave is 256 contiguous bytes, and a [B, W] intermediate is ceil(W / 64) registers per lane.
+// A kernel is a wide row kernel for batch B and width W when
+//   * it has one loop y over 0 .. B that indexes dimension 0, bare, of every [B, W] and [B] tensor it touches, and y is
+//     not used as a value;
+//   * it has at most one other loop x over 0 .. W, which indexes dimension 1, bare, of [B, W] tensors and dimension 0 of
+//     [W] tensors (a bias, a bias gradient), and is not used as a value;
+//   * or it is a raw `{it}` map over B * W elements of [B, W] tensors (it = y * W + x);
+//   * every other tensor it touches has one element.
+// The write decides the kind: [B, W] is a row-local map, [B] a reduction over the row, [W] a reduction over the batch per
+// column, one element a reduction over both.  The gradLoss seed is a member like in the thread-per-sample groups.
+// Two inner iterators (a contraction inside a row) do not qualify.  float32 programs only, as every fusion group.
+struct WideKernelInfo {
+  bool ok = false;
+  int row_loop = -1;  // index into k.loops of y (or of the raw iterator)
+  int col_loop = -1;  // index into k.loops of x (-1: none)
+  bool raw = false;
+  bool seed = false;
+  enum Kind { Map, RowRed, ColRed, AllRed } kind = Map;
+};
+constexpr long WIDE_MIN_W = 65, WIDE_MAX_W = 4096;
+// floats of group state one lane may hold: ceil(W / 64) per [B, W] tensor written in the group and per [W] batch sum
+// (a [B] value or the seed is one value per wave and not counted); the generated kernels must not spill
+constexpr long WIDE_STATE_MAX = 128;
+// the width a wide group starting with `k` would have: dimension 1 of the first [B, W] tensor it touches (0: none)
+long wide_width_of(const Kernel& k, const Shapes& shapes, long B);
+WideKernelInfo analyse_wide_kernel(const Program& prog, const Kernel& k, const KernelInfo& info, const Shapes& shapes, long B, long W);
+
 struct RowGroupTensor {
   int tensor = 0;
   enum Role { RowLocal, RowExternal, SmallExternal, SmallLocal, Reduction } role = RowExternal;
@@ -77,6 +108,9 @@ struct RowGroup {
   long grid_blocks = 0;
   std::vector<int> tail_kernels;   // indices into target.all, in execution order
   std::vector<int> tail_ptr_args;  // tensor ids of the tail kernels, in pointer-argument order
+  // Wide groups ("one wave per sample", below): W > 0, and `wide` holds the members' analysis instead of `infos`.
+  long W = 0;
+  std::vector<WideKernelInfo> wide;
 };
 
 // Emit the fused kernel.  Arguments of the generated kernel:
@@ -84,6 +118,18 @@ struct RowGroup {
 //    or in_kernel_finalize][, unsigned* counter, long MODE, float* u<ids>...: in_kernel_finalize])
 int generate_row_group(const Program& prog, const std::vector<Kernel>& all, const std::vector<KernelInfo>& infos,
                        const Shapes& shapes, RowGroup& group);
+
+// Emit a wide group's kernel (group.W > 0, group.wide filled in; tensor roles as above with inner = W for [B, W] and [W]
+// tensors and inner = 1 for [B] tensors and single elements).  256 threads, four waves, each wave walks samples with a grid
+// stride.  Lanes beyond a row's end (the last j when W is no multiple of 64) run the same instructions on column `lane`
+// of their own row — a load that is always in bounds, so the body has no branch and a sample's loads are issued together
+// (guarded bodies cost a memory round trip per member: 176 against 65 us at 65 536 x 100) — and their values are neither
+// summed nor stored.  Row reductions: every lane adds its terms in ascending j, then the eg_xor_lane butterfly leaves the total in
+// all lanes (a fixed order: two runs give the same bits).  Batch reductions: per-lane accumulators over the wave's
+// samples, the block's four waves folded through LDS into one partial row, row_finalize_kernel behind the launch.
+// Arguments of the generated kernel: (float* partial, float* / const float* t<ids>..., long B, float grad_scale, long epoch).
+int generate_wide_group(const Program& prog, const std::vector<Kernel>& all, const std::vector<KernelInfo>& infos,
+                        const Shapes& shapes, RowGroup& group);
 
 // ---- small-kernel fusion -------------------------------------------------------------------------
 // Consecutive kernels that touch only small tensors (the optimizer updates: gradientDescent's

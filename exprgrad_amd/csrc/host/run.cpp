@@ -181,6 +181,7 @@ int run_launch(eg_model* m, TargetState& ts, Plan& plan, Launch& L) {
       if (rc) return rc;
       return eg::colsum_with_scratch(ctx, sg.g.B, sg.g.slab_floats, sg.slab, dst, 0, static_cast<float*>(ctx->workspace));
     }
+    case StepKind::WideRows:   // (never single_block / in_kernel_finalize: partial rows, then row_finalize)
     case StepKind::RowFused: {
       PlanRowGroup& pg = *plan.row_groups[L.row_group];
       std::vector<float*> ptrs;
@@ -750,6 +751,7 @@ int plan_exchange(eg_model* m, TargetState& ts, Plan& plan, ExchangePlan& ex) {
   for (int i = 0; i < plan.n_backward; ++i) {
     const Launch& L = plan.launches[i];
     switch (L.kind) {
+      case StepKind::WideRows:
       case StepKind::RowFused:
         for (int tid : plan.row_groups[L.row_group]->red_tensors) note(tid, i);
         for (auto& kv : plan.row_groups[L.row_group]->g.tensors)

@@ -236,7 +236,13 @@ int eg_fill_uniform_f64(eg_ctx* ctx, int64_t n, double lo, double hi, const uint
  *
  * eg_model_compile does what newModel does for a CompileGpu target (model.nim:232-251):
  * autodiff + dead-kernel elimination, pattern-match every kernel to a library kernel or
- * generate HIP source for it, hiprtc-build, allocate parameters. */
+ * generate HIP source for it, hiprtc-build, allocate parameters.
+ *
+ * Per-sample chains (softmax.sums / softmax / loss gradient / softmax's gradient kernels / bias
+ * gradient, raw elementwise maps between them) are fused per input shape: rows of at most 64
+ * floats run as one thread per sample (`eg_rows<i>`), rows of 65 .. 4096 floats as one wave per
+ * sample (`eg_wrows<i>`); wider rows, and float64 programs, keep one launch per kernel.
+ * eg_model_launch_text shows what a target's last run used. */
 int eg_model_compile(eg_ctx* ctx, const char* program_text, eg_model** out);
 int eg_model_free(eg_model* model);
 
