@@ -152,6 +152,7 @@ struct SplitGemmArgs {
   long M, N, K, ldc;
   int tiles_m, tiles_n;
   int accumulate;
+  int skew;  // 0: every wave runs the k loop in phase (EG_GEMM_NO_SKEW=1); 1: the waves of a SIMD take different roles
   const unsigned* flag;
   unsigned epoch;
 };
@@ -180,35 +181,75 @@ __device__ __forceinline__ const void* uniform_ptr(const void* p) {
   return reinterpret_cast<const void*>(((unsigned long)hi << 32) | lo);
 }
 
+// What a wave does in one period of the k loop (between two barriers), as bits of a wave-uniform word.  In phase
+// (EG_GEMM_NO_SKEW=1) every wave is LOAD_OWN | READ_TOP: its own six LDS-DMA pieces and its fragment reads stand between
+// the barrier and its first MFMA.  Two waves that share a SIMD would then do all of that at the same moment with nobody
+// multiplying, so by default the partners of a SIMD take different roles:
+//   early wave (READ_AHEAD):  enters period kt with the B fragments and the first A fragments of k-tile kt in registers,
+//                             multiplies at once, and behind its last MFMA reads the same fragments of k-tile kt + 1.
+//   late wave  (LOAD_OWN | LOAD_PARTNER | READ_TOP):  issues all twelve pieces of k-tile kt + 2, reads its fragments of
+//                             k-tile kt and multiplies; all of its front runs under the early wave's MFMAs, and the early
+//                             wave's trailing reads under its own.
+// Same MFMAs on the same accumulators in the same order in every role: C does not depend on the roles.
+constexpr int ROLE_LOAD_OWN = 1, ROLE_LOAD_PARTNER = 2, ROLE_READ_TOP = 4, ROLE_READ_AHEAD = 8;
+// Waves w and w ^ PARTNER share a SIMD: w and w + 4 (measured both ways, profiles/split_skew_ab.txt: with the roles
+// split by parity the step was slower than in phase).  Waves 4 - 7 are the late ones: in phase they already reach their
+// first MFMA ~500 cycles behind their partners (profiles/split_skew_stamps.txt).
+constexpr int PARTNER = 4;
+
+#ifdef EG_SPLIT_GEMM_STAMPS
+// Diagnostic build only (-DEG_SPLIT_GEMM_STAMPS): per block and wave the cycles from barrier release to the first MFMA,
+// of the MFMA section, and from the last MFMA to the next barrier release, summed over the k loop, and the period count.
+// Read the shares, never this build's run time.  eg_debug_split_stamps copies the buffer out.
+constexpr int STAMP_BLOCKS = 1024;
+__device__ unsigned long long g_split_stamps[STAMP_BLOCKS][8][4];
+#define EG_STAMP(t)                                                                  \
+  do {                                                                               \
+    __builtin_amdgcn_sched_barrier(0);                                               \
+    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory"); \
+    __builtin_amdgcn_sched_barrier(0);                                               \
+  } while (0)
+#else
+#define EG_STAMP(t) \
+  do {              \
+  } while (0)
+#endif
+
 __global__ __launch_bounds__(NT) void split_gemm_kernel(SplitGemmArgs a) {
   if (*(volatile const unsigned*)a.flag == a.epoch) return;  // an operand did not split: the exact kernel behind runs
   __shared__ __attribute__((aligned(16))) unsigned char lds[STAGES * STAGE_BYTES];
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wave >> 2, wc = wave & 3;  // 2 x 4 waves of 128 x 64
   long m_blk, n_blk;
   tile_origin(xcd_remap(blockIdx.x, gridDim.x), a.tiles_m, a.tiles_n, m_blk, n_blk);
 
-  // buffer descriptors of the block's row panels: operand origin + first row; k-tile and plane go in the scalar offset
+  // buffer descriptors of the block's row panels: operand origin + first row; k-tile, plane and wave go in the scalar offset
   const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<void*>(uniform_ptr(a.pa + m_blk * 16)), (short)0, -1, 0x00020000);
   const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<void*>(uniform_ptr(a.pb + n_blk * 16)), (short)0, -1, 0x00020000);
   const unsigned a_plane = (unsigned)(a.M * a.K * 2), b_plane = (unsigned)(a.N * a.K * 2);
   const unsigned a_ktile = (unsigned)(a.M * 32), b_ktile = (unsigned)(a.N * 32);
-  const unsigned voff = (unsigned)tid * 16;
+  const unsigned voff = (unsigned)lane * 16;
 
-  // a wave's 1 KiB of each 8 KiB piece: LDS destination = wave base + lane * 16 (lane-linear, like the global source)
-  auto issue = [&](int kt, int s) {
-    unsigned char* st = lds + s * STAGE_BYTES + wave * 1024;
+  // wave w's 1 KiB of each 8 KiB piece: LDS destination = w's base + lane * 16 (lane-linear, like the global source), so
+  // any wave can load any wave's share
+  auto pieces = [&](int kt, int s, int w) {
+    unsigned char* st = lds + s * STAGE_BYTES + w * 1024;
+    const unsigned at = (unsigned)kt * a_ktile + (unsigned)w * 1024, bt = (unsigned)kt * b_ktile + (unsigned)w * 1024;
 #pragma unroll
     for (int i = 0; i < LOADS; ++i) {
       __attribute__((address_space(3))) void* dst = (__attribute__((address_space(3))) void*)(st + i * PLANE_BYTES);
       if (i < 3)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, dst, 16, voff, (unsigned)i * a_plane + (unsigned)kt * a_ktile, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, dst, 16, voff, (unsigned)i * a_plane + at, 0, 0);
       else
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, dst, 16, voff, (unsigned)(i - 3) * b_plane + (unsigned)kt * b_ktile, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, dst, 16, voff, (unsigned)(i - 3) * b_plane + bt, 0, 0);
     }
+  };
+  auto issue = [&](int kt, int s, int r) {
+    if (r & ROLE_LOAD_OWN) pieces(kt, s, wave);
+    if (r & ROLE_LOAD_PARTNER) pieces(kt, s, wave ^ PARTNER);
   };
 
   f32x4 acc[8][4];
@@ -230,40 +271,104 @@ __global__ __launch_bounds__(NT) void split_gemm_kernel(SplitGemmArgs a) {
   const int a01_off = a_row + sel * PLANE_BYTES, a02_off = a_row + 2 * sel * PLANE_BYTES;
   const int b21_off = b_row + (2 - sel) * PLANE_BYTES, b10_off = b_row + (1 - sel) * PLANE_BYTES, b00_off = b_row;
 
-  const int KT = (int)(a.K / 16);
-  issue(0, 0);
-  if (KT > 1) issue(1, 1);
-  int s = 0;
-  for (int kt = 0; kt < KT; ++kt) {
-    // this wave's pieces of k-tile kt have landed (those of kt + 1 may still fly); the barrier makes every wave's visible
-    // and says every wave is done reading k-tile kt - 1, whose stage the next issue refills
-    if (kt + 1 < KT) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    if (kt + 2 < KT) issue(kt + 2, s == 0 ? 2 : s - 1);
-    const unsigned char* st = lds + s * STAGE_BYTES;
-    bf16x8 fb21[4], fb10[4], fb00[4];
+  // the fragments a period starts from: all of B and the first of A (the other seven A fragments are read between the MFMAs)
+  bf16x8 fb21[4], fb10[4], fb00[4], fa01, fa02;
+  auto read_head = [&](const unsigned char* st) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       fb21[j] = *reinterpret_cast<const bf16x8*>(st + b21_off + j * 512);
       fb10[j] = *reinterpret_cast<const bf16x8*>(st + b10_off + j * 512);
       fb00[j] = *reinterpret_cast<const bf16x8*>(st + b00_off + j * 512);
     }
+    fa01 = *reinterpret_cast<const bf16x8*>(st + a01_off);
+    fa02 = *reinterpret_cast<const bf16x8*>(st + a02_off);
+  };
+#pragma unroll
+  for (int j = 0; j < 4; ++j) fb21[j] = fb10[j] = fb00[j] = bf16x8{};
+  fa01 = fa02 = bf16x8{};
+
+  const int skew = a.skew;
+  const int role = !skew ? ROLE_LOAD_OWN | ROLE_READ_TOP
+                         : (wave & PARTNER) ? ROLE_LOAD_OWN | ROLE_LOAD_PARTNER | ROLE_READ_TOP : ROLE_READ_AHEAD;
+  const int KT = (int)(a.K / 16);
+  issue(0, 0, role);
+  if (KT > 1) issue(1, 1, role);
+  if (skew) {
+    // the early waves start from k-tile 0's fragments: the loaders' pieces of it have landed (twelve of k-tile 1 may fly)
+    if (KT > 1) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    if (role & ROLE_READ_AHEAD) read_head(lds);
+  }
+#ifdef EG_SPLIT_GEMM_STAMPS
+  unsigned long long t0 = 0, t1 = 0, t2 = 0, front = 0, body = 0, back = 0;
+#endif
+  int s = 0;
+  for (int kt = 0; kt < KT; ++kt) {
+    // In phase: this wave's pieces of k-tile kt have landed (those of kt + 1 may still fly).  Staggered: a loader's pieces
+    // of k-tile kt + 1, issued a period ago, have landed (k-tile kt landed a period earlier still; the other waves have
+    // nothing outstanding).  The barrier makes every wave's visible and says that every wave is done reading k-tile
+    // kt - 1, whose stage the next issue refills.  So behind barrier kt k-tile kt may be read in phase, and k-tiles kt
+    // and kt + 1 when staggered: a read is always at least one barrier behind the wait that retired its pieces.
+    if (!skew && kt + 1 < KT) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+#ifdef EG_SPLIT_GEMM_STAMPS
+    EG_STAMP(t0);
+    if (kt) back += t0 - t2;
+#endif
+    // the role, made opaque in every period: ONE loop body with scalar branches around the issue and the two read sites
+    // (as a loop invariant the compiler would write a loop per role)
+    int r = role;
+    asm volatile("" : "+s"(r));
+    if (kt + 2 < KT) issue(kt + 2, s == 0 ? 2 : s - 1, r);
+    const unsigned char* st = lds + s * STAGE_BYTES;
+    if (r & ROLE_READ_TOP) read_head(st);
+    EG_STAMP(t1);
     // per block the 2^-16 pair first, then the 2^-8 pair, then a0b0 with a2b0
+    // The A fragments of block row i + 1 are read in front of block row i's twelve MFMAs and waited for behind them.  The
+    // fences keep them there: left alone the scheduler sinks each read to its first use, and a wave that has the matrix
+    // pipe to itself (its partner is in its front or at the barrier) then stands for an LDS latency per block row
+    // (stamped: 1840 cycles per 96 MFMAs of 16).
+    bf16x8 c01 = fa01, c02 = fa02;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
-      const bf16x8 fa01 = *reinterpret_cast<const bf16x8*>(st + a01_off + i * 512);
-      const bf16x8 fa02 = *reinterpret_cast<const bf16x8*>(st + a02_off + i * 512);
+      bf16x8 n01 = c01, n02 = c02;
+      __builtin_amdgcn_sched_barrier(0);
+      if (i + 1 < 8) {
+        n01 = *reinterpret_cast<const bf16x8*>(st + a01_off + (i + 1) * 512);
+        n02 = *reinterpret_cast<const bf16x8*>(st + a02_off + (i + 1) * 512);
+      }
+      __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa01, fb21[j], acc[i][j], 0, 0, 0);
+      for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(c01, fb21[j], acc[i][j], 0, 0, 0);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa01, fb10[j], acc[i][j], 0, 0, 0);
+      for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(c01, fb10[j], acc[i][j], 0, 0, 0);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa02, fb00[j], acc[i][j], 0, 0, 0);
+      for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(c02, fb00[j], acc[i][j], 0, 0, 0);
+      c01 = n01;
+      c02 = n02;
     }
+    EG_STAMP(t2);
+#ifdef EG_SPLIT_GEMM_STAMPS
+    front += t1 - t0;
+    body += t2 - t1;
+#endif
     s = s == STAGES - 1 ? 0 : s + 1;
+    // k-tile kt + 1 landed before barrier kt (above); its stage is refilled behind barrier kt + 2 at the earliest
+    if ((r & ROLE_READ_AHEAD) && kt + 1 < KT) read_head(lds + s * STAGE_BYTES);
   }
+#ifdef EG_SPLIT_GEMM_STAMPS
+  if (lane == 0 && blockIdx.x < STAMP_BLOCKS) {
+    unsigned long long* o = g_split_stamps[blockIdx.x][wave];
+    o[0] = front;
+    o[1] = body;
+    o[2] = back;
+    o[3] = (unsigned long long)KT;
+  }
+#endif
 
   // The sub-tile leaves through LDS as 16-byte row pieces (the 16x16 C/D map, column lane & 15 and row 4 (lane >> 4) + r,
   // would store 64-byte pieces).  Each wave parks half of its 128 x 64 sub-tile at a time in a 16 KiB region of its own
@@ -358,6 +463,7 @@ int sgemm_split(eg_ctx* ctx, int trans_a, int trans_b, long M, long N, long K, c
   g.tiles_m = (int)(M / BM);
   g.tiles_n = (int)(N / BN);
   g.accumulate = accumulate;
+  g.skew = eg::sw::present("EG_GEMM_NO_SKEW") ? 0 : 1;
   g.flag = ctx->split_flag;
   g.epoch = epoch;
   hipLaunchKernelGGL(split_gemm_kernel, dim3((unsigned)(g.tiles_m * g.tiles_n)), dim3(NT), 0, ctx->stream, g);
@@ -369,3 +475,13 @@ int sgemm_split(eg_ctx* ctx, int trans_a, int trans_b, long M, long N, long K, c
 
 }  // namespace gemm
 }  // namespace eg
+
+#ifdef EG_SPLIT_GEMM_STAMPS
+// Diagnostic build only: the stamp sums of the last product launch, [block][wave][front, MFMA section, back, periods].
+extern "C" int eg_debug_split_stamps(unsigned long long* dst, size_t count) {
+  if (count > sizeof(g_split_stamps) / sizeof(unsigned long long)) return EG_ERR_UNSUPPORTED;
+  EG_HIP_CHECK(hipDeviceSynchronize());
+  EG_HIP_CHECK(hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_split_stamps), count * sizeof(unsigned long long)));
+  return 0;
+}
+#endif
