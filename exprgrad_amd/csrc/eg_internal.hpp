@@ -10,14 +10,11 @@
 #include <utility>
 #include <vector>
 
+#include "error.hpp"
 #include "exprgrad_hip.h"
 #include "switches.hpp"
 
 namespace eg {
-
-// Thread-local error text behind eg_last_error().
-void set_error(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
-void clear_error();
 
 #define EG_HIP_CHECK(expr)                                                             \
   do {                                                                                 \

@@ -6,7 +6,9 @@
 #include <cstdio>
 #include <set>
 
-#include "../eg_internal.hpp"
+#include "../error.hpp"
+#include "../switches.hpp"
+#include "exprgrad_hip.h"
 
 namespace eg {
 namespace kd {

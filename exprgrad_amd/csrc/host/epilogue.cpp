@@ -4,7 +4,9 @@
 #include <map>
 #include <set>
 
-#include "../eg_internal.hpp"
+#include "../error.hpp"
+#include "../switches.hpp"
+#include "exprgrad_hip.h"
 #include "codegen.hpp"
 
 namespace eg {

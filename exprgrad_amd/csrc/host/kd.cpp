@@ -11,7 +11,9 @@
 #include <set>
 #include <sstream>
 
-#include "../eg_internal.hpp"
+#include "../error.hpp"
+#include "../switches.hpp"
+#include "exprgrad_hip.h"
 
 namespace eg {
 namespace kd {

@@ -1,7 +1,8 @@
 // Pattern matching of lowered kernels against the hand-written library: contraction, bias add,
 // convolution and its two gradients.
-#include "model_types.hpp"
+#include "match.hpp"
 
+#include <set>
 
 namespace eg {
 namespace model {

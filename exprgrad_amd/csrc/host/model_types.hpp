@@ -26,7 +26,7 @@
 #include "codegen.hpp"
 #include "epilogue.hpp"
 #include "kd.hpp"
-#include "dp_schedule.hpp"
+#include "match.hpp"
 #include "rowfuse.hpp"
 
 namespace eg {
@@ -34,19 +34,6 @@ namespace model {
 
 using namespace eg::kd;
 using eg::set_error;
-
-struct GemmMatch {
-  int a_read = 0, b_read = 0;  // indices into k.reads
-  bool trans_a = false, trans_b = false;
-  int li = 0, lj = 0, lk = 0;  // loop indices of m, n, k
-};
-
-struct ConvMatch {
-  // which operand plays which part: -1 = the written tensor, 0 / 1 = k.reads[i]
-  int out_op = -1, img_op = 0, flt_op = 1;
-  bool batched = true;
-  enum Role { Forward, GradImage, GradFilter } role = Forward;
-};
 
 // WideRows: a row group with one wave per sample (rowfuse.hpp); Launch::row_group indexes Plan::row_groups as for RowFused
 enum class StepKind { Gemm, Conv, ConvGradImage, ConvGradFilter, Seed, GenericA, GenericB, RowFused, SmallFused, GemmFused, SampleFused, WideRows };
@@ -350,12 +337,6 @@ struct LaneSwap {
   }
 };
 
-// match.cpp
-bool bare2(const Op& op, int& r0, int& r1);
-int loop_index(const Kernel& k, int reg);
-bool match_gemm(const Kernel& k, GemmMatch& m);
-bool match_bias(const Kernel& k, int tensor);
-bool match_conv(const Kernel& k, ConvMatch& m);
 // lower.cpp
 int build_generic(eg_model* m, Generic& g);
 void inline_producers(eg_model* m, TargetState& ts);

@@ -63,7 +63,7 @@ int fuse_row_tails(eg_model* m, TargetState& ts, Plan& plan, const std::vector<K
       cap = eg::sw::integer("EG_ROW_TAIL_BLOCKS", cap);   // tuning aid
       pg.g.grid_blocks = std::min<long>(pg.nblocks, std::max(1L, cap));
     }
-    int rc = generate_row_group(m->prog, t.all, infos, plan.shapes, pg.g);
+    int rc = generate_row_group(t.all, infos, plan.shapes, pg.g);
     if (rc) return rc;
     bool replaced = false;
     for (auto& pk : plan.pending)
@@ -73,7 +73,7 @@ int fuse_row_tails(eg_model* m, TargetState& ts, Plan& plan, const std::vector<K
       }
     if (!replaced) {  // (cannot happen: the group's kernel is built with the plan)
       pg.g.tail_kernels.clear();
-      return generate_row_group(m->prog, t.all, infos, plan.shapes, pg.g);
+      return generate_row_group(t.all, infos, plan.shapes, pg.g);
     }
     pg.tail_group = S.row_group;
     R.tail_launch = i + 1;
@@ -165,7 +165,7 @@ int fuse_slab_fold(eg_model* m, TargetState& ts, Plan& plan, const std::vector<K
 //   * reads nothing that an earlier member sums over the batch (a block sees its own sample only), and
 //   * if it sums over the batch itself, writes a member of the gradient bucket without scatter (its per-sample
 //     contributions go to the slab; one slab_sum launch behind the kernel folds them, in a fixed order).
-// Switches: EG_NO_SAMPLE_FUSE=1, EG_SAMPLE_FUSE_MAX_BATCH (default 1280), EG_SAMPLE_THREADS (512), EG_SAMPLE_NO_LDS.
+// Switches: EG_NO_SAMPLE_FUSE=1, EG_SAMPLE_FUSE_MAX_BATCH (default 1280).
 int form_sample_group(eg_model* m, TargetState& ts, Plan& plan, const std::vector<KernelInfo>& infos, const std::map<int, int>& first_writer,
                       std::vector<int>& group_of, std::set<int>& needs_zero) {
   {
@@ -387,9 +387,8 @@ int form_sample_group(eg_model* m, TargetState& ts, Plan& plan, const std::vecto
       candidates.erase(k.write.tensor);
       for (auto& rd : k.reads) candidates.erase(rd.tensor);
     }
-    constexpr bool no_lds = false;
     long budget = 34L * 1024;  // floats (136 KB of the 160 KB a block may own; up to 16 KB more for the split reductions)
-    if (!m->keep_values && !no_lds)
+    if (!m->keep_values)
       for (int tid : candidates) {
         const long inner = prod(shapes.at(tid)) / B;
         if (inner <= 0 || inner > budget) continue;
@@ -422,7 +421,7 @@ int form_sample_group(eg_model* m, TargetState& ts, Plan& plan, const std::vecto
   char name[64];
   snprintf(name, sizeof(name), "eg_samples%d", m->kernel_serial++);
   g.name = name;
-  int rc = generate_sample_group(m->prog, t.all, infos, shapes, g);
+  int rc = generate_sample_group(t.all, infos, shapes, g);
   if (rc) return rc;
   if (g.slab_floats > 0) {
     EG_HIP_CHECK(hipSetDevice(m->ctx->device));
@@ -583,7 +582,7 @@ static int form_wide_groups(eg_model* m, TargetState& ts, Plan& plan, const std:
     snprintf(name, sizeof(name), "eg_wrows%d", m->kernel_serial++);
     g.name = name;
     pg->nblocks = (int)((B + 255) / 256);  // the grid of a row group; a block's four waves share its 256 samples
-    int rc = generate_wide_group(m->prog, t.all, infos, shapes, g);
+    int rc = generate_wide_group(t.all, shapes, g);
     if (rc) return rc;
     plan.pending.push_back({g.name, g.source, &pg->handle});
     if (g.red_total > 0) {
@@ -798,7 +797,7 @@ int form_row_groups(eg_model* m, TargetState& ts, Plan& plan, const std::vector<
     // several blocks: the last one to arrive folds the partial rows itself (rowfuse.hpp) — every thread of it keeps one
     // accumulator per total in registers (at most 64 totals), rows in strides of 256
     g.in_kernel_finalize = row_tails_enabled() && g.red_total > 0 && g.red_total <= 64 && pg->nblocks > 1 && pg->nblocks <= 4096;
-    int rc = generate_row_group(m->prog, t.all, infos, shapes, g);
+    int rc = generate_row_group(t.all, infos, shapes, g);
     if (rc) return rc;
     plan.pending.push_back({g.name, g.source, &pg->handle});
     if (g.red_total > 0) {
@@ -849,7 +848,7 @@ int form_row_groups(eg_model* m, TargetState& ts, Plan& plan, const std::vector<
       char name[64];
       snprintf(name, sizeof(name), "eg_small%d", m->kernel_serial++);
       sg->g.name = name;
-      int rc = generate_small_group(m->prog, t.all, infos, shapes, sg->g);
+      int rc = generate_small_group(t.all, infos, shapes, sg->g);
       if (rc) return rc;
       plan.pending.push_back({sg->g.name, sg->g.source, &sg->handle});
       const int gi = (int)plan.small_groups.size();

@@ -1,5 +1,8 @@
 // Row fusion: run a chain of per-sample kernels as ONE generated kernel, one thread per sample.
 //
+// The layer's public header.  Units, none with a HIP header: rowfuse_row.cpp (thread per sample), rowfuse_small.cpp (small, map),
+// rowfuse_sample.cpp + rowfuse_sample_conv.cpp (block per sample), rowfuse_wide.cpp (wave per sample), rowfuse_common.cpp.
+//
 // Role in the reference: fuseLoops (passes.nim:1929-2004, 2526-2549) merges consecutive kernels
 // that share their leading loop — on the CPU target dense + bias + activation become one `y`
 // loop.  The reference's GPU target does not benefit (each lowered kernel is still its own
@@ -116,8 +119,7 @@ struct RowGroup {
 // Emit the fused kernel.  Arguments of the generated kernel:
 //   (float* partial, float* / const float* t<ids>..., long B, float grad_scale, long epoch[, float* d<ids>...: single_block
 //    or in_kernel_finalize][, unsigned* counter, long MODE, float* u<ids>...: in_kernel_finalize])
-int generate_row_group(const Program& prog, const std::vector<Kernel>& all, const std::vector<KernelInfo>& infos,
-                       const Shapes& shapes, RowGroup& group);
+int generate_row_group(const std::vector<Kernel>& all, const std::vector<KernelInfo>& infos, const Shapes& shapes, RowGroup& group);
 
 // Emit a wide group's kernel (group.W > 0, group.wide filled in; tensor roles as above with inner = W for [B, W] and [W]
 // tensors and inner = 1 for [B] tensors and single elements).  256 threads, four waves, each wave walks samples with a grid
@@ -128,8 +130,7 @@ int generate_row_group(const Program& prog, const std::vector<Kernel>& all, cons
 // all lanes (a fixed order: two runs give the same bits).  Batch reductions: per-lane accumulators over the wave's
 // samples, the block's four waves folded through LDS into one partial row, row_finalize_kernel behind the launch.
 // Arguments of the generated kernel: (float* partial, float* / const float* t<ids>..., long B, float grad_scale, long epoch).
-int generate_wide_group(const Program& prog, const std::vector<Kernel>& all, const std::vector<KernelInfo>& infos,
-                        const Shapes& shapes, RowGroup& group);
+int generate_wide_group(const std::vector<Kernel>& all, const Shapes& shapes, RowGroup& group);
 
 // ---- small-kernel fusion -------------------------------------------------------------------------
 // Consecutive kernels that touch only small tensors (the optimizer updates: gradientDescent's
@@ -153,8 +154,7 @@ struct SmallGroup {
 
 // Arguments of the generated kernel: (float* / const float* t<ids>..., float grad_scale, long epoch).
 // Every kernel accumulates into its destination (the caller zeroes first-written results).
-int generate_small_group(const Program& prog, const std::vector<Kernel>& all, const std::vector<KernelInfo>& infos,
-                         const Shapes& shapes, SmallGroup& group);
+int generate_small_group(const std::vector<Kernel>& all, const std::vector<KernelInfo>& infos, const Shapes& shapes, SmallGroup& group);
 
 // ---- map groups ------------------------------------------------------------------------------------
 // Consecutive raw elementwise kernels over whole tensors of ANY size (`p{it} ++= -g{it} * rate` for
@@ -222,8 +222,7 @@ struct SampleGroup {
 };
 
 // Arguments of the generated kernel: (float* slab, float* t<ids>..., float grad_scale, long epoch); grid = B blocks of `threads`.
-int generate_sample_group(const Program& prog, const std::vector<Kernel>& all, const std::vector<KernelInfo>& infos,
-                          const Shapes& shapes, SampleGroup& group);
+int generate_sample_group(const std::vector<Kernel>& all, const std::vector<KernelInfo>& infos, const Shapes& shapes, SampleGroup& group);
 
 }  // namespace kd
 }  // namespace eg

@@ -232,7 +232,7 @@ int conv2_direct_grad_filter_try(eg_ctx* ctx, long N, long H, long W, long C, lo
        " + t] = acc[f * " + std::to_string(taps) + " + t] + g[f] * win[t];\n  }\n";
   s += "  __shared__ float red[4 * " + std::to_string(E) + "];\n";
   s += "  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;\n";
-  // (the butterfly over all values of a step together, not value by value: rowfuse.cpp, round 6)
+  // (the butterfly over all values of a step together, not value by value: rowfuse_row.cpp, round 6)
   s += "  _Pragma(\"unroll\") for (int off = 32; off >= 1; off >>= 1)\n";
   s += "    _Pragma(\"unroll\") for (int e = 0; e < " + std::to_string(E) + "; ++e) acc[e] += __shfl_xor(acc[e], off, 64);\n";
   s += "  if (lane == 0) {\n    _Pragma(\"unroll\") for (int e = 0; e < " + std::to_string(E) + "; ++e) red[wave * " + std::to_string(E) + " + e] = acc[e];\n  }\n  __syncthreads();\n";

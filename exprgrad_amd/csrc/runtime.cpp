@@ -15,26 +15,6 @@
 #include "eg_internal.hpp"
 
 namespace eg {
-static thread_local std::string g_error;
-
-void set_error(const char* fmt, ...) {
-  char stack[2048];
-  va_list ap;
-  va_start(ap, fmt);
-  int n = vsnprintf(stack, sizeof(stack), fmt, ap);
-  va_end(ap);
-  if (n < (int)sizeof(stack)) {
-    g_error.assign(stack, n < 0 ? 0 : n);
-    return;
-  }
-  std::vector<char> heap(n + 1);
-  va_start(ap, fmt);
-  vsnprintf(heap.data(), heap.size(), fmt, ap);
-  va_end(ap);
-  g_error.assign(heap.data(), n);
-}
-void clear_error() { g_error.clear(); }
-
 // EG_POISON=1 (debugging aid): every scratch block is filled with NaN bit patterns right before a
 // library call uses it, and models do the same with the parts of their result arena that the
 // kernels are supposed to overwrite completely.  A read of memory nobody wrote then shows up as NaN
@@ -165,7 +145,6 @@ int kernels_compile_batch(eg_ctx* ctx, const char* label, const char* source, co
 
 extern "C" {
 
-const char* eg_last_error(void) { return eg::g_error.c_str(); }
 int eg_version(void) { return 1000; }
 
 int eg_device_count(int* count) {

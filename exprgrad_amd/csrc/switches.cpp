@@ -8,7 +8,7 @@
 #include <unordered_map>
 #include <vector>
 
-#include "eg_internal.hpp"
+#include "exprgrad_hip.h"
 
 namespace {
 
