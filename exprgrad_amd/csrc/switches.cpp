@@ -49,6 +49,7 @@ const Row kSwitches[] = {
     {"EG_NO_ROW_TAIL", "execution", "a row group's last block neither folds the partial rows nor runs the update"},
     {"EG_PIPELINE", "execution", "the batch pipeline (two half batches, streaming launches under the other half's contraction): OFF unless 1"},
     {"EG_NO_SPLIT_GEMM", "execution", "eg_sgemm runs every product on the exact f32 matrix path, never as three-way split bf16"},
+    {"EG_SPLIT_PASS_SCALAR", "execution", "the split pass reads an operand whose k runs along ld as 4-byte loads per lane (units), not as 16-byte tiles through LDS"},
     {"EG_GEMM_NO_SKEW", "execution", "every wave of a contraction block runs the k loop in phase (the round-3 loop)"},
     {"EG_GEMM_NO_BK32", "execution", "16-deep k-tiles for long whole-tile products"},
     {"EG_GEMM_NO_PAIR", "execution", "no wave-pair / eight-wave small-tile kernels"},
