@@ -71,6 +71,8 @@ _SIGS = {
     "eg_kernel_launch": (c_int, [c_void_p, c_int, P(c_i64), P(c_i64)]),
     "eg_sgemm": (c_int, [c_void_p, c_int, c_int, c_i64, c_i64, c_i64, c_void_p, c_i64, c_void_p, c_i64,
                          c_void_p, c_i64, c_int, c_void_p]),
+    "eg_sgemm_batched": (c_int, [c_void_p, c_int, c_int, c_i64, c_i64, c_i64, c_i64, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_i64,
+                                 c_void_p, c_i64, c_i64, c_int, c_void_p]),
     "eg_bias_add": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_int]),
     "eg_colsum": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_int]),
     "eg_rowsum": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_int]),

@@ -35,7 +35,9 @@ void inline_producers(eg_model* m, TargetState& ts) {
   auto is_library = [&](const Kernel& k) {
     GemmMatch g;
     ConvMatch c;
-    return k.is_seed || match_gemm(k, g) || (!prog.f64 && match_conv(k, c));
+    BatchedGemmMatch bg;
+    return k.is_seed || match_gemm(k, g) || (!prog.f64 && match_conv(k, c)) ||
+           (!prog.f64 && !eg::sw::present("EG_NO_BATCHED_GEMM") && match_batched_gemm(k, bg));
   };
   for (size_t p = 0; p < t.live.size(); ++p) {
     if (ts.lowered[p].absorbed || (int)p == t.first_update) continue;
@@ -250,6 +252,17 @@ int lower_target(eg_model* m, TargetState& ts) {
       }
       continue;
     }
+    // a product with a leading batch index: one batched launch, or a plain product over the collapsed extents
+    // (EG_NO_BATCHED_GEMM=1: the generated kernel, as before)
+    if (!m->prog.f64 && !eg::sw::present("EG_NO_BATCHED_GEMM") && match_batched_gemm(k, lo.bgemm)) {
+      lo.kind = lo.bgemm.collapsed ? StepKind::Gemm : StepKind::GemmBatched;
+      lo.standalone = true;
+      lo.gemm.a_read = lo.bgemm.a_read;
+      lo.gemm.b_read = lo.bgemm.b_read;
+      lo.gemm.trans_a = lo.bgemm.trans_a;
+      lo.gemm.trans_b = lo.bgemm.trans_b;
+      continue;
+    }
     // (float64: no library convolution yet — conv2 and its gradients run as generated kernels over `double`)
     if (!m->prog.f64 && match_conv(k, lo.conv)) {
       lo.kind = lo.conv.role == ConvMatch::Forward     ? StepKind::Conv
@@ -306,6 +319,8 @@ void describe(eg_model* m) {
       const Lowered& lo = ts.lowered[p];
       const Kernel& k = ts.target->all[lo.all_index];
       const char* kind = lo.absorbed ? "fused-into-previous"
+                         : lo.kind == StepKind::GemmBatched ? "eg_bgemm"
+                         : lo.kind == StepKind::Gemm && lo.standalone ? (lo.bgemm.row_k ? "gemm(batch rows collapsed into k)" : "gemm(batch rows collapsed into m)")
                          : lo.kind == StepKind::Gemm ? (lo.bias_tensor ? "gemm+bias" : "gemm")
                          : lo.kind == StepKind::Conv ? "conv2"
                          : lo.kind == StepKind::ConvGradImage ? "conv2-grad-image"
@@ -313,7 +328,7 @@ void describe(eg_model* m) {
                          : lo.kind == StepKind::Seed ? "seed-fill"
                          : (lo.b_capable ? "generic(map|split-reduce)" : "generic(map)");
       os << "  [" << p << "] " << kind;
-      if (lo.kind == StepKind::Gemm) os << (lo.gemm.trans_a ? " T" : " N") << (lo.gemm.trans_b ? "T" : "N");
+      if (lo.kind == StepKind::Gemm || lo.kind == StepKind::GemmBatched) os << (lo.gemm.trans_a ? " T" : " N") << (lo.gemm.trans_b ? "T" : "N");
       os << " : " << to_text(k) << "\n";
     }
   }

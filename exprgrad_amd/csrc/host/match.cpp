@@ -3,6 +3,7 @@
 #include "match.hpp"
 
 #include <set>
+#include <vector>
 
 namespace eg {
 namespace model {
@@ -49,6 +50,105 @@ bool match_gemm(const Kernel& k, GemmMatch& m) {
       m.li = loop_index(k, wi);
       m.lj = loop_index(k, wj);
       m.lk = loop_index(k, kk);
+      return true;
+    }
+  }
+  return false;
+}
+
+namespace {
+// every dimension a single bare register, all different
+bool bare_dims(const Op& op, std::vector<int>& regs) {
+  regs.clear();
+  if (op.raw) return false;
+  std::set<int> seen;
+  for (auto& d : op.dims) {
+    const int r = d.only_register();
+    if (!r || !seen.insert(r).second) return false;
+    regs.push_back(r);
+  }
+  return true;
+}
+}  // namespace
+
+// out[g,i,j] += a[g,i,k] * b[g,k,j], its two derived forms, and the shared-weight forms that collapse to a plain product
+// (match.hpp).  Anything else — the batch index elsewhere, a bounded loop, a float64 program — is not a match.
+bool match_batched_gemm(const Kernel& k, BatchedGemmMatch& m) {
+  if (k.f64 || !k.index_instrs.empty()) return false;
+  if (k.instrs.size() != 1 || k.instrs[0].kind != IK::Mul || k.result != k.instrs[0].res) return false;
+  if (k.reads.size() != 2 || k.loops.size() != 4 || !k.setup.empty()) return false;
+  for (auto& lp : k.loops)
+    if (lp.has_bounds) return false;
+  const std::vector<int>& args = k.instrs[0].args;
+  if (!((args[0] == k.reads[0].reg && args[1] == k.reads[1].reg) || (args[0] == k.reads[1].reg && args[1] == k.reads[0].reg)))
+    return false;
+  std::vector<int> w, r[2];
+  if (!bare_dims(k.write, w) || !bare_dims(k.reads[0], r[0]) || !bare_dims(k.reads[1], r[1])) return false;
+  for (const std::vector<int>* regs : {&w, &r[0], &r[1]}) {
+    if (regs->size() != 2 && regs->size() != 3) return false;
+    for (int reg : *regs)
+      if (loop_index(k, reg) < 0) return false;
+  }
+  const int rank2 = (w.size() == 2) + (r[0].size() == 2) + (r[1].size() == 2);
+  auto is = [](int p, int q, int x, int y) { return (p == x && q == y) || (p == y && q == x); };
+  BatchedGemmMatch out;
+  if (rank2 == 0) {
+    const int g = w[0], wi = w[1], wj = w[2];
+    int kk = 0;
+    for (auto& lp : k.loops)
+      if (lp.reg != g && lp.reg != wi && lp.reg != wj) kk = lp.reg;
+    if (!kk || r[0][0] != g || r[1][0] != g) return false;
+    for (int a = 0; a < 2; ++a) {
+      const int b = 1 - a;
+      if (is(r[a][1], r[a][2], wi, kk) && is(r[b][1], r[b][2], kk, wj)) {
+        out.a_read = a;
+        out.b_read = b;
+        out.trans_a = r[a][1] == kk;
+        out.trans_b = r[b][1] == wj;
+        out.lg = loop_index(k, g);
+        out.li = loop_index(k, wi);
+        out.lj = loop_index(k, wj);
+        out.lk = loop_index(k, kk);
+        m = out;
+        return true;
+      }
+    }
+    return false;
+  }
+  if (rank2 != 1) return false;
+  out.collapsed = true;
+  if (w.size() == 3) {
+    // out[g,i,n] += a[g,i,k] * w(k,n): the rank-3 read has the write's two leading registers and k last
+    const int g = w[0], i = w[1], n = w[2];
+    const int a = r[0].size() == 3 ? 0 : 1, b = 1 - a;
+    if (r[a][0] != g || r[a][1] != i) return false;
+    const int kk = r[a][2];
+    if (kk == n || !is(r[b][0], r[b][1], kk, n)) return false;
+    out.a_read = a;
+    out.b_read = b;
+    out.trans_b = r[b][0] == n;
+    out.lg = loop_index(k, g);
+    out.li = loop_index(k, i);
+    out.lj = loop_index(k, n);
+    out.lk = loop_index(k, kk);
+    m = out;
+    return true;
+  }
+  // gw[m,n] += a[g,i,m] * b[g,i,n]: both reads share their two leading registers, which the write does not name
+  const int g = r[0][0], i = r[0][1];
+  if (r[1][0] != g || r[1][1] != i || g == w[0] || g == w[1] || i == w[0] || i == w[1]) return false;
+  for (int a = 0; a < 2; ++a) {
+    const int b = 1 - a;
+    if (r[a][2] == w[0] && r[b][2] == w[1]) {
+      out.row_k = true;
+      out.a_read = a;
+      out.b_read = b;
+      out.trans_a = true;
+      out.lg = loop_index(k, g);
+      out.lk = loop_index(k, i);
+      out.li = loop_index(k, w[0]);
+      out.lj = loop_index(k, w[1]);
+      m = out;
       return true;
     }
   }

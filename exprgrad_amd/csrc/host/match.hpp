@@ -20,9 +20,24 @@ struct ConvMatch {
   enum Role { Forward, GradImage, GradFilter } role = Forward;
 };
 
+// A `++=` product with a leading batch index (match_batched_gemm).
+//   batched:   write and both reads rank 3, the batch register first in each — one product per g
+//              (out[g,i,j] ++= a[g,i,k] * b[g,k,j] and its two derived gradients): trans_a / trans_b as for GemmMatch
+//   collapsed: exactly one operand is rank 2 (a weight shared by every g) and the product is a plain one once (g, i) is read
+//              as one index of the dense row-major rank-3 tensors:
+//                row_k = false: out[g,i,n] ++= a[g,i,k] * w(k,n)   M = G * I, A = a untransposed, trans_b from w
+//                row_k = true:  gw[m,n] ++= a[g,i,m] * b[g,i,n]    K = G * I, TN
+struct BatchedGemmMatch {
+  bool collapsed = false, row_k = false;
+  int a_read = 0, b_read = 0;  // indices into k.reads
+  bool trans_a = false, trans_b = false;
+  int lg = 0, li = 0, lj = 0, lk = 0;  // loop indices of g, m, n, k (collapsed: lg, and li (row_k: lk), are the two collapsed loops)
+};
+
 bool bare2(const Op& op, int& r0, int& r1);
 int loop_index(const Kernel& k, int reg);
 bool match_gemm(const Kernel& k, GemmMatch& m);
+bool match_batched_gemm(const Kernel& k, BatchedGemmMatch& m);
 bool match_bias(const Kernel& k, int tensor);
 bool match_conv(const Kernel& k, ConvMatch& m);
 

@@ -251,7 +251,7 @@ const char* eg_model_launch_text(eg_model* m, const char* target) {
       case StepKind::GemmFused:
         os << (L.kind == StepKind::GemmFused ? "gemm+epilogue " : "gemm ") << (L.trans_a ? "T" : "N") << (L.trans_b ? "T" : "N")
            << " " << L.M << "x" << L.N << "x" << L.K << " -> t" << L.c_tensor << (L.bias_tensor ? " +bias" : "")
-           << (L.accumulate ? " accumulate" : "");
+           << (L.accumulate ? " accumulate" : "") << (L.standalone ? " (batch rows collapsed)" : "");
         if (L.ones_tensor) os << " +ones-row -> t" << L.ones_tensor << " (bias gradient, kernel " << L.ones_lowered << ")";
         if (L.kind == StepKind::GemmFused) {
           const PlanEpilogue& pe = *plan.epilogues[L.epilogue];
@@ -262,6 +262,10 @@ const char* eg_model_launch_text(eg_model* m, const char* target) {
             os << " | row product NN " << pe.product.M << "x" << pe.product.N << "x" << pe.product.K << " -> t" << pe.product.c_tensor
                << (pe.product.bias_tensor ? " +bias" : "") << " (kernel " << pe.product.lowered << ")";
         }
+        break;
+      case StepKind::GemmBatched:
+        os << "eg_bgemm " << (L.trans_a ? "T" : "N") << (L.trans_b ? "T" : "N") << " " << L.batch << " x " << L.M << "x" << L.N << "x" << L.K
+           << " -> t" << L.c_tensor << (L.accumulate ? " accumulate" : "");
         break;
       case StepKind::Conv: os << "conv2 -> t" << L.c_tensor << (L.accumulate ? " accumulate" : ""); break;
       case StepKind::ConvGradImage: os << "conv2-grad-image -> t" << L.c_tensor << (L.accumulate ? " accumulate" : ""); break;

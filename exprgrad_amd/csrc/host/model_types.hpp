@@ -35,8 +35,9 @@ namespace model {
 using namespace eg::kd;
 using eg::set_error;
 
+// GemmBatched: one product per leading batch index in one launch (kernels/gemm_batched.hip)
 // WideRows: a row group with one wave per sample (rowfuse.hpp); Launch::row_group indexes Plan::row_groups as for RowFused
-enum class StepKind { Gemm, Conv, ConvGradImage, ConvGradFilter, Seed, GenericA, GenericB, RowFused, SmallFused, GemmFused, SampleFused, WideRows };
+enum class StepKind { Gemm, Conv, ConvGradImage, ConvGradFilter, Seed, GenericA, GenericB, RowFused, SmallFused, GemmFused, SampleFused, WideRows, GemmBatched };
 
 struct Generic {
   GenericSource src;
@@ -48,6 +49,10 @@ struct Lowered {
   StepKind kind = StepKind::GenericA;
   int all_index = 0;  // index into target.all
   GemmMatch gemm;
+  // A product with a leading batch index (match_batched_gemm): kind GemmBatched, or — collapsed — kind Gemm over the
+  // collapsed extents.  Both are stand-alone launches: no epilogue, no row / sample group, no side lane.
+  BatchedGemmMatch bgemm;
+  bool standalone = false;
   int bias_tensor = 0;  // fused bias (0 = none)
   bool absorbed = false;  // this kernel was folded into the previous step
   bool inlined = false;   // an elementwise producer recomputed inside its consumers: never launched, never stored
@@ -71,6 +76,8 @@ struct Launch {
   long M = 0, N = 0, K = 0, lda = 0, ldb = 0, ldc = 0;
   int a_tensor = 0, b_tensor = 0, c_tensor = 0, bias_tensor = 0;
   bool trans_a = false, trans_b = false;
+  long batch = 0, stride_a = 0, stride_b = 0, stride_c = 0;   // GemmBatched
+  bool standalone = false;   // Gemm: a collapsed batched product (Lowered::standalone): never fused, grouped or overlapped
   long cN = 0, cH = 0, cW = 0, cC = 0, cF = 0, cFH = 0, cFW = 0;
   // Seed
   long count = 0;

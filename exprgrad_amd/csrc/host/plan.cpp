@@ -442,7 +442,75 @@ int make_plan(eg_model* m, TargetState& ts, Plan& plan) {
       continue;
     }
     bool overwrite = first && full_cover(k, info, wshape);
-    if (lo.kind == StepKind::Gemm) {
+    if (lo.standalone) {
+      // A product with a leading batch index (match_batched_gemm).  The tensors are dense row-major, so an item of a rank-3
+      // operand [G, R, C] is a [R, C] matrix at g * R * C; collapsed forms read (g, i) as one row index, which needs the
+      // collapsed loops to cover that extent of every rank-3 operand.
+      const BatchedGemmMatch& g = lo.bgemm;
+      const Op& A = k.reads[g.a_read];
+      const Op& B = k.reads[g.b_read];
+      const std::vector<long>& as = shapes.at(A.tensor);
+      const std::vector<long>& bs = shapes.at(B.tensor);
+      auto ext = [&](int loop) { return info.bounds[loop].second; };
+      const long G = ext(g.lg);
+      bool ok = info.ok;
+      for (int l : {g.lg, g.li, g.lj, g.lk}) ok = ok && info.bounds[l].first == 0;
+      L.a_tensor = A.tensor;
+      L.b_tensor = B.tensor;
+      L.c_tensor = wt;
+      L.trans_a = g.trans_a;
+      L.trans_b = g.trans_b;
+      L.standalone = true;
+      if (!g.collapsed) {
+        L.kind = StepKind::GemmBatched;
+        L.batch = G;
+        L.M = ext(g.li);
+        L.N = ext(g.lj);
+        L.K = ext(g.lk);
+        ok = ok && as.size() == 3 && bs.size() == 3 && wshape.size() == 3 && as[0] >= G && bs[0] >= G && wshape[0] >= G;
+        if (ok) {
+          const long a_m = g.trans_a ? as[2] : as[1], a_k = g.trans_a ? as[1] : as[2];
+          const long b_k = g.trans_b ? bs[2] : bs[1], b_n = g.trans_b ? bs[1] : bs[2];
+          ok = a_m >= L.M && a_k >= L.K && b_k >= L.K && b_n >= L.N && wshape[1] >= L.M && wshape[2] >= L.N;
+          L.lda = as[2];
+          L.ldb = bs[2];
+          L.ldc = wshape[2];
+          L.stride_a = as[1] * as[2];
+          L.stride_b = bs[1] * bs[2];
+          L.stride_c = wshape[1] * wshape[2];
+        }
+      } else if (!g.row_k) {
+        const long I = ext(g.li);
+        L.kind = StepKind::Gemm;
+        L.M = G * I;
+        L.N = ext(g.lj);
+        L.K = ext(g.lk);
+        ok = ok && as.size() == 3 && bs.size() == 2 && wshape.size() == 3 && as[1] == I && wshape[1] == I && as[0] >= G && wshape[0] >= G &&
+             as[2] >= L.K && wshape[2] >= L.N && (g.trans_b ? bs[0] >= L.N && bs[1] >= L.K : bs[0] >= L.K && bs[1] >= L.N);
+        if (ok) {
+          L.lda = as[2];
+          L.ldb = bs[1];
+          L.ldc = wshape[2];
+        }
+      } else {
+        const long I = ext(g.lk);
+        L.kind = StepKind::Gemm;
+        L.M = ext(g.li);
+        L.N = ext(g.lj);
+        L.K = G * I;
+        ok = ok && as.size() == 3 && bs.size() == 3 && wshape.size() == 2 && as[1] == I && bs[1] == I && as[0] >= G && bs[0] >= G &&
+             as[2] >= L.M && bs[2] >= L.N && wshape[0] >= L.M && wshape[1] >= L.N;
+        if (ok) {
+          L.lda = as[2];
+          L.ldb = bs[2];
+          L.ldc = wshape[1];
+        }
+      }
+      if (!ok) {
+        set_error("batched contraction operands have inconsistent shapes");
+        return EG_ERR_SHAPE;
+      }
+    } else if (lo.kind == StepKind::Gemm) {
       const GemmMatch& g = lo.gemm;
       const Op& A = k.reads[g.a_read];
       const Op& B = k.reads[g.b_read];

@@ -61,6 +61,7 @@ void launch_io(eg_model* m, TargetState& ts, const Plan& plan, const Launch& L, 
   switch (L.kind) {
     case StepKind::Seed: wr(L.c_tensor, false); break;
     case StepKind::Gemm:
+    case StepKind::GemmBatched:
     case StepKind::Conv:
     case StepKind::ConvGradImage:
     case StepKind::ConvGradFilter:

@@ -121,7 +121,7 @@ int fuse_epilogues(eg_model* m, TargetState& ts, Plan& plan, const std::vector<K
   plan.epilogues.clear();
   for (size_t i = 0; i + 1 < plan.launches.size(); ++i) {
     Launch& G = plan.launches[i];
-    if (G.kind != StepKind::Gemm || G.accumulate) continue;
+    if (G.kind != StepKind::Gemm || G.accumulate || G.standalone) continue;
     if (G.ldc != G.N || G.M * G.N < min_elems || G.M * G.N <= 0) continue;
     // the consumer: the first later launch that reads the contraction result.  It need not be
     // adjacent (derive emits the other gradient contraction of a layer in between), as long as
@@ -233,7 +233,7 @@ int fold_row_products(eg_model* m, TargetState& ts, Plan& plan) {
       const Launch& P = plan.launches[pj];
       if (P.kind != StepKind::Gemm && P.kind != StepKind::GenericA && P.kind != StepKind::GenericB) break;
       if (P.consumer >= 0 || P.ones_tensor) break;
-      const bool candidate = P.kind == StepKind::Gemm && !P.trans_a && !P.trans_b && P.a_tensor == R && P.lda == G.N &&
+      const bool candidate = P.kind == StepKind::Gemm && !P.standalone && !P.trans_a && !P.trans_b && P.a_tensor == R && P.lda == G.N &&
                              P.M == G.M && P.K == G.N && P.N >= 1 && P.N <= 16 && !P.accumulate && P.ldc == P.N;
       if (!candidate) {
         const Kernel& kx = t.all[ts.lowered[P.lowered].all_index];
@@ -289,7 +289,7 @@ int fold_bias_gradients(eg_model* m, TargetState& ts, Plan& plan, const std::vec
   const Target& t = *ts.target;
   for (size_t gi = 0; gi < plan.launches.size(); ++gi) {
     Launch& G = plan.launches[gi];
-    if (G.kind != StepKind::Gemm || G.accumulate || !G.trans_a || G.trans_b || G.bias_tensor || G.ldc != G.N) continue;
+    if (G.kind != StepKind::Gemm || G.standalone || G.accumulate || !G.trans_a || G.trans_b || G.bias_tensor || G.ldc != G.N) continue;
     auto gw = ts.bucket_offset.find(G.c_tensor);
     if (gw == ts.bucket_offset.end()) continue;
     // candidate: a column sum of the same B operand whose destination follows gW in the bucket

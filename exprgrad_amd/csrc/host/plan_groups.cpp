@@ -226,6 +226,7 @@ int form_sample_group(eg_model* m, TargetState& ts, Plan& plan, const std::vecto
         }
       }
     }
+    if (lo.standalone) ski[p].ok = false;   // a batched product keeps its own launch
     if (ski[p].ok && ski[p].reduced && !ts.bucket_offset.count(k.write.tensor)) ski[p].ok = false;
     if (ski[p].ok && plan.alias.count(k.write.tensor)) ski[p].ok = false;
     // What belongs on the matrix cores stays there: a contraction whose two other extents are both >= 32 (a hidden layer of
@@ -615,6 +616,8 @@ int form_row_groups(eg_model* m, TargetState& ts, Plan& plan, const std::vector<
   std::vector<RowKernelInfo> rki(n);
   for (int p = 0; p < n; ++p)
     if (group_of[p] == -1) rki[p] = analyse_row_kernel(m->prog, t.all[t.live[p]], infos[t.live[p]], shapes, B);
+  for (int p = 0; p < n; ++p)
+    if (ts.lowered[p].standalone) rki[p].ok = false;   // a batched product keeps its own launch
   // a bias folded into a library contraction is not available on its own
   for (int p = 1; p < n; ++p)
     if (ts.lowered[p].absorbed && !rki[p - 1].ok) rki[p].ok = false;
@@ -821,7 +824,7 @@ int form_row_groups(eg_model* m, TargetState& ts, Plan& plan, const std::vector<
   p = 0;
   while (p < n) {
     auto eligible = [&](int s) {
-      if (group_of[s] != -1 || ts.lowered[s].absorbed || ts.lowered[s].bias_tensor) return false;
+      if (group_of[s] != -1 || ts.lowered[s].absorbed || ts.lowered[s].bias_tensor || ts.lowered[s].standalone) return false;
       return is_small_kernel(m->prog, t.all[t.live[s]], infos[t.live[s]], shapes);
     };
     if (!eligible(p)) {

@@ -78,7 +78,7 @@ void plan_overlap(eg_model* m, TargetState& ts, Plan& plan) {
   const int n = (int)plan.launches.size();
   for (int j = 1; j < n; ++j) {
     const Launch& B = plan.launches[j];
-    if (B.kind != StepKind::Gemm && B.kind != StepKind::GemmFused) continue;
+    if ((B.kind != StepKind::Gemm && B.kind != StepKind::GemmFused) || B.standalone) continue;
     const double flops = 2.0 * (double)B.M * (double)B.N * (double)B.K;
     if (flops < 8e9) continue;
     std::set<int> br, bw;
@@ -89,7 +89,7 @@ void plan_overlap(eg_model* m, TargetState& ts, Plan& plan) {
       if (i + 1 == plan.n_backward) break;  // never across the backward | update boundary
       if (!plan.overlaps.empty() && i <= plan.overlaps.back().big) break;
       const Launch& S = plan.launches[i];
-      if (S.kind != StepKind::Gemm && S.kind != StepKind::GenericA && S.kind != StepKind::GenericB) break;
+      if ((S.kind != StepKind::Gemm && S.kind != StepKind::GenericA && S.kind != StepKind::GenericB) || S.standalone) break;
       if (S.kind == StepKind::Gemm && 2.0 * (double)S.M * (double)S.N * (double)S.K * 4 > flops) break;
       std::set<int> sr, sw;
       if (!launch_tensors(plan, S, sr, sw)) break;

@@ -68,7 +68,7 @@ void plan_pipeline(eg_model* m, TargetState& ts, Plan& plan) {
         if (x && reductions.count(x)) return true;
       return false;
     };
-    if (L.kind == StepKind::Gemm || L.kind == StepKind::GemmFused) {
+    if ((L.kind == StepKind::Gemm || L.kind == StepKind::GemmFused) && !L.standalone) {
       if (reads_reduction({L.a_tensor, L.b_tensor, L.bias_tensor})) return;
       const double flops = 2.0 * (double)L.M * (double)L.N * (double)L.K;
       if (L.M == B && !L.trans_a && batch_major(L.a_tensor) && batch_major(L.c_tensor) && L.ldc == L.N) {

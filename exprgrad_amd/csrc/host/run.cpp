@@ -48,6 +48,10 @@ int run_launch(eg_model* m, TargetState& ts, Plan& plan, Launch& L) {
       return eg::gemm::sgemm_exact(ctx, L.trans_a, L.trans_b, L.M, L.N, L.K, tensor_ptr(m, ts, plan, L.a_tensor), L.lda,
                       tensor_ptr(m, ts, plan, L.b_tensor), L.ldb, tensor_ptr(m, ts, plan, L.c_tensor), L.ldc,
                       L.accumulate, L.bias_tensor ? tensor_ptr(m, ts, plan, L.bias_tensor) : nullptr);
+    case StepKind::GemmBatched:
+      return eg::gemm::sgemm_batched(ctx, L.trans_a, L.trans_b, L.batch, L.M, L.N, L.K, tensor_ptr(m, ts, plan, L.a_tensor), L.lda, L.stride_a,
+                                     tensor_ptr(m, ts, plan, L.b_tensor), L.ldb, L.stride_b, tensor_ptr(m, ts, plan, L.c_tensor), L.ldc,
+                                     L.stride_c, L.accumulate, nullptr);
     case StepKind::GemmFused: {
       PlanEpilogue& pe = *plan.epilogues[L.epilogue];
       const float* bias = L.bias_tensor ? tensor_ptr(m, ts, plan, L.bias_tensor) : nullptr;
@@ -425,11 +429,12 @@ int run_range_eager(eg_model* m, TargetState& ts, Plan& plan, int begin, int end
     }
     // Two independent tiny contractions next to each other (a dense layer's two gradients at a small batch): one launch
     // (EG_NO_SMALL_PAIR=1: two).  Independence is checked on the storage: neither writes what the other touches.
+    // (A collapsed batched product, Launch::standalone, keeps its own launch here as everywhere else.)
     const bool pair_off = eg::sw::raw("EG_NO_SMALL_PAIR") != nullptr;   // (read per launch sequence: a test builds one model each way)
     if (!pair_off && !m->f64 && i + 1 < end && i + 1 != plan.n_backward &&
         !(next_overlap < plan.overlaps.size() && plan.overlaps[next_overlap].first == i + 1)) {
       const Launch &A = plan.launches[i], &B = plan.launches[i + 1];
-      if (A.kind == StepKind::Gemm && B.kind == StepKind::Gemm && !A.ones_tensor && !B.ones_tensor &&
+      if (A.kind == StepKind::Gemm && B.kind == StepKind::Gemm && !A.ones_tensor && !B.ones_tensor && !A.standalone && !B.standalone &&
           eg::gemm_small_suits(A.M, A.N, A.K) && eg::gemm_small_suits(B.M, B.N, B.K)) {
         auto ptr = [&](int t) -> float* { return t ? tensor_ptr(m, ts, plan, t) : nullptr; };
         float *ca = ptr(A.c_tensor), *cb = ptr(B.c_tensor);

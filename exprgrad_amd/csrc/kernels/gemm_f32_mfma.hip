@@ -326,6 +326,8 @@ int gemm_small_pair(eg_ctx* ctx, const SmallGemm& g0, const SmallGemm& g1) {
 
 namespace eg {
 namespace gemm {
+const GemmSwitches& current_switches() { return gemm_switches(); }
+
 // The exact f32 product (v_mfma_f32_32x32x2_f32: a k-ordered fmaf chain per element).  Everything inside the library
 // (model plans, convolutions) calls this; only the public eg_sgemm may take the split-bf16 path first.
 int sgemm_exact(eg_ctx* ctx, int trans_a, int trans_b, long M, long N, long K, const float* A, long lda, const float* B, long ldb,

@@ -1059,7 +1059,7 @@ __device__ __forceinline__ void gemm_mainloop_dma_x(const GemmArgs& a, float* ld
 // 2 = B is that matrix with k = output pixel, n = tap (filter-gradient contraction).
 template <int BM, int BN, int BK, int WM, int WN, bool A_KC, bool B_KC, int VEC, bool EDGE, int CONV, int ABL, bool DMA,
           class Epi, bool XR = false>
-__device__ __forceinline__ void gemm_block(const GemmArgs& a) {
+__device__ __forceinline__ void gemm_block_at(const GemmArgs& a, const int block_id) {
   constexpr int WAVES_N = BN / WN;
   constexpr int MI = WM / 32, NI = WN / 32;
   constexpr int SA = LdsStride<BM, BK, A_KC>::value, SB = LdsStride<BN, BK, B_KC>::value;
@@ -1099,10 +1099,10 @@ __device__ __forceinline__ void gemm_block(const GemmArgs& a) {
   // set spread over the XCDs on its own (one contiguous remap of both would hand some XCDs nothing but
   // whole tiles and others nothing but slices: measured 2.3 ms instead of 1.4 for 4100^3).
   const int work = a.tail_tiles > 0
-                       ? ((int)blockIdx.x < tail_first
-                              ? xcd_remap(blockIdx.x, tail_first)
-                              : tail_first + xcd_remap(blockIdx.x - tail_first, a.tail_tiles * a.tail_splits))
-                       : xcd_remap(blockIdx.x, nfull + a.tiles_n * a.edge_splits);
+                       ? (block_id < tail_first
+                              ? xcd_remap(block_id, tail_first)
+                              : tail_first + xcd_remap(block_id - tail_first, a.tail_tiles * a.tail_splits))
+                       : xcd_remap(block_id, nfull + a.tiles_n * a.edge_splits);
   int split;
   long m_blk, n_blk, k_slice;
   int tail_slab = -1;  // >= 0: this block writes a whole-tile slab
@@ -1533,6 +1533,14 @@ __device__ __forceinline__ void gemm_block(const GemmArgs& a) {
   stamp(3);
 }
 
+// The block of a launch whose grid is the contraction's work items.  (gemm_block_at: the batched kernel of gemm_batched.hip
+// hands every item's blocks the ids of a launch of that item alone.)
+template <int BM, int BN, int BK, int WM, int WN, bool A_KC, bool B_KC, int VEC, bool EDGE, int CONV, int ABL, bool DMA,
+          class Epi, bool XR = false>
+__device__ __forceinline__ void gemm_block(const GemmArgs& a) {
+  gemm_block_at<BM, BN, BK, WM, WN, A_KC, B_KC, VEC, EDGE, CONV, ABL, DMA, Epi, XR>(a, (int)blockIdx.x);
+}
+
 // Waves per SIMD the register allocator must leave room for.  The ragged-tile variants of the
 // 64-wide tiles need a few registers more than the 128 that four waves allow (they spilled 2-38
 // VGPRs to scratch): three waves there.
@@ -1621,7 +1629,8 @@ __global__ __launch_bounds__(256, 4) void gemm_streamk_kernel(GemmArgs a) {
 }
 
 // One block per REMAINING tile: the sum of its pieces in block (= k) order.
-__global__ __launch_bounds__(256) void gemm_streamk_fixup_kernel(const float* __restrict__ partial, float* C, const float* __restrict__ bias,
+// (static, like gemm_splitk_reduce_kernel below: this header is part of two translation units, gemm_f32_mfma.hip and gemm_batched.hip)
+static __global__ __launch_bounds__(256) void gemm_streamk_fixup_kernel(const float* __restrict__ partial, float* C, const float* __restrict__ bias,
                                                                  long ldc, int tiles_m, int tiles_n, long tiles_dp, int nk, long per,
                                                                  int accumulate) {
   constexpr int BM = 64, BN = 64;
@@ -1765,7 +1774,7 @@ __device__ __forceinline__ void gemm_narrow_k_block(const GemmArgs& a) {
 
 // Second pass of split-K: C[m,n] = (accumulate ? C : 0) + sum_z partial[z][m][n] + bias[n],
 // slabs added in increasing z (fixed order => run-to-run deterministic).
-__global__ __launch_bounds__(256) void gemm_splitk_reduce_kernel(const float* __restrict__ partial, float* C,
+static __global__ __launch_bounds__(256) void gemm_splitk_reduce_kernel(const float* __restrict__ partial, float* C,
                                                                  const float* __restrict__ bias, long M, long N,
                                                                  long ldc, int splits, int accumulate,
                                                                  long edge_row, int edge_splits) {

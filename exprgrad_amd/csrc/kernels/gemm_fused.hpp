@@ -49,6 +49,14 @@ bool exact_single_launch(eg_ctx* ctx, int trans_a, int trans_b, long M, long N, 
 int sgemm_split(eg_ctx* ctx, int trans_a, int trans_b, long M, long N, long K, const float* A, long lda, const float* B, long ldb,
                 float* C, long ldc, int accumulate, const float* bias);
 
+// `batch` exact f32 products of one shape, X_b = X + b * stride_x, in one launch (gemm_batched.hip): what eg_sgemm_batched
+// and the model layer's batched launches run.
+int sgemm_batched(eg_ctx* ctx, int trans_a, int trans_b, long batch, long M, long N, long K, const float* A, long lda, long stride_a,
+                  const float* B, long ldb, long stride_b, float* C, long ldc, long stride_c, int accumulate, const float* bias);
+// The planner's switches as the exact product reads them (gemm_plan.hpp; gemm_f32_mfma.hip keeps them per thread).
+struct GemmSwitches;
+const GemmSwitches& current_switches();
+
 // Weight gradient + bias gradient in one contraction (gemm_f32_mfma.hip): C[M + 1, N] = [op(A); 1] * op(B).
 bool ones_row_supported(int trans_a, int trans_b, long M, long N, long K, const float* A, long lda, const float* B, long ldb);
 int sgemm_ones_row(eg_ctx* ctx, int trans_a, int trans_b, long M, long N, long K, const float* A, long lda, const float* B,

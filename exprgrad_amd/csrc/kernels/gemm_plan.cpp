@@ -594,6 +594,36 @@ GemmPlan plan_gemm(const GemmProblem& p, const GemmSwitches& sw) {
   return r;
 }
 
+GemmPlan plan_gemm_batched(const GemmProblem& item, long batch, const GemmSwitches& sw) {
+  const long M = item.M, N = item.N, K = item.K;
+  GemmPlan r;
+  r.route = Route::Generic;
+  // 64 x 64 tiles for every item: the most blocks, and four of them per CU.  The only tile that is built.
+  // (Tried and dropped: 128 x 128 tiles whenever the launch still had two blocks for every CU, slower at every shape that
+  // reached them — the figures are in profiles/batched_gemm.txt; items large enough to want a larger tile fill the chip by
+  // themselves and run as plain products, batched_runs_as_loop.  Not measured, so not built: 128 x 32 tiles for a
+  // bias-sized N.  sw.force_tile is not read: the launch has this one tile.)
+  r.bm = r.bn = 64;
+  r.kb = BK;
+  r.waves = tile_waves(r.bm, r.bn);
+  set_variant(r, item);
+  r.tiles_m = (int)((M + r.bm - 1) / r.bm);
+  r.tiles_n = (int)((N + r.bn - 1) / r.bn);
+  r.splits = 1;
+  r.k_per_split = std::max<long>(((K + BK - 1) / BK) * BK, BK);
+  r.wide_store = wide_store_ok(item, sw, false);
+  r.no_skew = sw.no_skew;
+  r.grid = batch * r.tiles_m * r.tiles_n;
+  r.block = (r.bm / r.waves.wm) * (r.bn / r.waves.wn) * 64;
+  return r;
+}
+
+bool batched_runs_as_loop(const GemmProblem& item, const GemmSwitches& sw) {
+  const GemmPlan p = plan_gemm(item, sw);
+  if (p.route == Route::Remainder) return true;   // (whole 256 x 256 tiles and then some)
+  return p.grid >= item.cus && p.route != Route::Small;
+}
+
 bool exact_single_launch(const GemmPlan& p) {
   return p.route == Route::Bk32 || (p.route == Route::Generic && p.bm == 256 && p.bn == 256 && !p.edge && p.splits <= 1 &&
                                     p.tail_tiles == 0 && p.second == Second::None);

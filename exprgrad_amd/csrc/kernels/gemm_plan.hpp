@@ -100,6 +100,16 @@ bool wide_store_ok(const GemmProblem& p, const GemmSwitches& sw, bool to_partial
 
 GemmPlan plan_gemm(const GemmProblem& p, const GemmSwitches& sw);
 
+// `batch` products of one shape in ONE launch (gemm_batched.hip): item.M / N / K, the layouts, the leading dimensions and the
+// alignment facts describe one item (the caller folds the items' strides into the alignment facts).  The plan is always
+// Route::Generic on 64 x 64 tiles, unsliced (splits = 1, no second pass, no workspace: every output element is one in-order
+// sum over k), with grid = batch x tiles_m x tiles_n.  (gemm_plan.cpp has what was measured.)
+GemmPlan plan_gemm_batched(const GemmProblem& item, long batch, const GemmSwitches& sw);
+
+// Does one item fill the chip by itself?  Its own plan has at least one block per CU: such a batch runs as a loop of plain
+// products on their own routes.  Decided from the item alone, so that an item has the same bits whatever batch it is part of.
+bool batched_runs_as_loop(const GemmProblem& item, const GemmSwitches& sw);
+
 // Is the plan ONE launch of the whole-tile 256 x 256 kernel (no k-slices, tail slices or second pass)?  Only such a launch
 // can stand behind the split-bf16 product as its fallback: GemmArgs::run_if gates the tile kernel, not the reduce kernels.
 bool exact_single_launch(const GemmPlan& p);

@@ -36,6 +36,7 @@ const Row kSwitches[] = {
     {"EG_NO_PREDICATE", "execution", "pre-activations stored as values, not as predicate bits"},
     {"EG_NO_ROW_PRODUCT", "execution", "the 10-wide forward product as its own launch, not in the previous layer's epilogue"},
     {"EG_NO_ROW_DIRECT", "execution", "a one-block row group writes a partial row for row_finalize instead of its totals"},
+    {"EG_NO_BATCHED_GEMM", "execution", "products with a leading batch index as generated kernels instead of eg_bgemm launches / collapsed products"},
     {"EG_NO_SMALL_PAIR", "execution", "two independent tiny contractions as two launches"},
     {"EG_NO_SKINNY_GEMM", "execution", "N <= 16 products on the matrix tiles instead of the streaming skinny kernel"},
     {"EG_NO_NARROW_K", "execution", "K <= 16 products with a generated epilogue on the matrix tile instead of the streaming kernel"},

@@ -154,6 +154,21 @@ int eg_sgemm(eg_ctx* ctx, int trans_a, int trans_b, int64_t M, int64_t N, int64_
              const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc,
              int accumulate, const float* bias);
 
+/* C_b[m,n] (+)= sum_k opA_b(m,k) * opB_b(k,n) (+ bias[n]) for b in [0, batch): X_b = X + b * stride_x.
+ * trans_a / trans_b, lda / ldb / ldc, accumulate and bias as for eg_sgemm; bias is shared by all items.
+ * stride_a == 0 or stride_b == 0: that operand is shared by all items.  stride_c >= (M - 1) * ldc + N.
+ * Always the exact f32 path.
+ * One launch of batch x tiles blocks (kernels/gemm_batched.hip): every output element is one k-ascending sum on the f32
+ * matrix instruction, so an item has the same bits whatever batch it is part of.  Items that fill the chip by themselves
+ * run as a loop of exact products instead.  Covers out[g,i,j] ++= a[g,i,k] * b[g,k,j] and its two derived gradients
+ * (trans_b = 1 / trans_a = 1, as for eg_sgemm).
+ * EG_ERR_INVALID: a negative extent or stride, a leading dimension shorter than a row, a stride_c that makes items
+ * overlap, a NULL pointer with a non-empty product.  batch == 0 and empty products succeed and launch nothing; K == 0 with
+ * accumulate == 0 writes bias or zeros. */
+int eg_sgemm_batched(eg_ctx* ctx, int trans_a, int trans_b, int64_t batch, int64_t M, int64_t N, int64_t K,
+                     const float* A, int64_t lda, int64_t stride_a, const float* B, int64_t ldb, int64_t stride_b,
+                     float* C, int64_t ldc, int64_t stride_c, int accumulate, const float* bias);
+
 /* out[y,x] (+)= bias[x]   — dense's second kernel, dnn.nim:22-24. out is [rows, cols]. */
 int eg_bias_add(eg_ctx* ctx, int64_t rows, int64_t cols, const float* bias, float* out,
                 int accumulate);
