@@ -134,6 +134,8 @@ _SIGS = {
     "eg_model_source_text": (c_char_p, [c_void_p]),
     "eg_dgemm": (c_int, [c_void_p, c_int, c_int, c_i64, c_i64, c_i64, c_void_p, c_i64, c_void_p, c_i64,
                          c_void_p, c_i64, c_int, c_void_p]),
+    "eg_dgemm_batched": (c_int, [c_void_p, c_int, c_int, c_i64, c_i64, c_i64, c_i64, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_i64,
+                                 c_void_p, c_i64, c_i64, c_int, c_void_p]),
     "eg_colsum_f64": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_int]),
     "eg_fill_f64": (c_int, [c_void_p, c_i64, c_f64, c_void_p]),
     "eg_fill_uniform_f64": (c_int, [c_void_p, c_i64, c_f64, c_f64, c_void_p, ctypes.c_uint64, c_void_p]),

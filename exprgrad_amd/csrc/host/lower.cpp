@@ -37,7 +37,7 @@ void inline_producers(eg_model* m, TargetState& ts) {
     ConvMatch c;
     BatchedGemmMatch bg;
     return k.is_seed || match_gemm(k, g) || (!prog.f64 && match_conv(k, c)) ||
-           (!prog.f64 && !eg::sw::present("EG_NO_BATCHED_GEMM") && match_batched_gemm(k, bg));
+           (!eg::sw::present("EG_NO_BATCHED_GEMM") && match_batched_gemm(k, bg));
   };
   for (size_t p = 0; p < t.live.size(); ++p) {
     if (ts.lowered[p].absorbed || (int)p == t.first_update) continue;
@@ -254,7 +254,8 @@ int lower_target(eg_model* m, TargetState& ts) {
     }
     // a product with a leading batch index: one batched launch, or a plain product over the collapsed extents
     // (EG_NO_BATCHED_GEMM=1: the generated kernel, as before)
-    if (!m->prog.f64 && !eg::sw::present("EG_NO_BATCHED_GEMM") && match_batched_gemm(k, lo.bgemm)) {
+    // (either scalar type: eg_sgemm_batched / eg_dgemm_batched, the collapsed forms eg_sgemm / eg_dgemm)
+    if (!eg::sw::present("EG_NO_BATCHED_GEMM") && match_batched_gemm(k, lo.bgemm)) {
       lo.kind = lo.bgemm.collapsed ? StepKind::Gemm : StepKind::GemmBatched;
       lo.standalone = true;
       lo.gemm.a_read = lo.bgemm.a_read;

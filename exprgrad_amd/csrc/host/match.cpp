@@ -72,9 +72,9 @@ bool bare_dims(const Op& op, std::vector<int>& regs) {
 }  // namespace
 
 // out[g,i,j] += a[g,i,k] * b[g,k,j], its two derived forms, and the shared-weight forms that collapse to a plain product
-// (match.hpp).  Anything else — the batch index elsewhere, a bounded loop, a float64 program — is not a match.
+// (match.hpp), in either scalar type.  Anything else — the batch index elsewhere, a bounded loop — is not a match.
 bool match_batched_gemm(const Kernel& k, BatchedGemmMatch& m) {
-  if (k.f64 || !k.index_instrs.empty()) return false;
+  if (!k.index_instrs.empty()) return false;
   if (k.instrs.size() != 1 || k.instrs[0].kind != IK::Mul || k.result != k.instrs[0].res) return false;
   if (k.reads.size() != 2 || k.loops.size() != 4 || !k.setup.empty()) return false;
   for (auto& lp : k.loops)

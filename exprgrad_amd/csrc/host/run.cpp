@@ -49,6 +49,11 @@ int run_launch(eg_model* m, TargetState& ts, Plan& plan, Launch& L) {
                       tensor_ptr(m, ts, plan, L.b_tensor), L.ldb, tensor_ptr(m, ts, plan, L.c_tensor), L.ldc,
                       L.accumulate, L.bias_tensor ? tensor_ptr(m, ts, plan, L.bias_tensor) : nullptr);
     case StepKind::GemmBatched:
+      if (m->f64) {
+        auto dp = [&](int t) { return reinterpret_cast<double*>(tensor_ptr(m, ts, plan, t)); };
+        return eg::gemm::dgemm_batched(ctx, L.trans_a, L.trans_b, L.batch, L.M, L.N, L.K, dp(L.a_tensor), L.lda, L.stride_a, dp(L.b_tensor), L.ldb,
+                                       L.stride_b, dp(L.c_tensor), L.ldc, L.stride_c, L.accumulate, nullptr);
+      }
       return eg::gemm::sgemm_batched(ctx, L.trans_a, L.trans_b, L.batch, L.M, L.N, L.K, tensor_ptr(m, ts, plan, L.a_tensor), L.lda, L.stride_a,
                                      tensor_ptr(m, ts, plan, L.b_tensor), L.ldb, L.stride_b, tensor_ptr(m, ts, plan, L.c_tensor), L.ldc,
                                      L.stride_c, L.accumulate, nullptr);

@@ -67,8 +67,8 @@ void launch_config(eg_ctx* ctx, unsigned grid, bool a_kc, bool b_kc, const GemmP
   });
 }
 
-// blocks of one launch: grid x block threads stays below 2^32 and the block id an int
-constexpr long MAX_BLOCKS = 1L << 22;
+// blocks of one launch (gemm_plan.hpp: the float64 batched launch keeps the same limit)
+constexpr long MAX_BLOCKS = BATCHED_MAX_BLOCKS;
 
 }  // namespace
 

@@ -12,10 +12,16 @@
 // fall into different bank halves).  All four storage orders go through one loader (strides), ragged
 // tiles are zero filled, K is cut into slices with a fixed-order second pass when the tiles alone
 // cannot fill the chip (deterministic: no atomics).
+//
+// eg_dgemm_batched — `out[g,i,j] ++= a[g,i,k] * b[g,k,j]` of a float64 program and its two derived gradients, which the
+// reference runs as one work-item per output element — is the same tile body, one block per (item, tile), in one launch:
+// dgemm_batched_kernel below, planned by plan_dgemm_batched (gemm_plan.cpp).
 #include <cstdlib>
 #include <cstring>
 
 #include "../eg_internal.hpp"
+#include "gemm_fused.hpp"
+#include "gemm_plan.hpp"
 
 namespace {
 
@@ -101,8 +107,11 @@ struct TileLoader {
 // 34 against 77.8 TFLOP/s) — the matrix pipe needs several waves per SIMD that are multiplying at the same time.  So a tile
 // is shared by WR x WC waves with small sub-tiles (128 x 128: eight waves of 64 x 32; 64 x 64: four of 32 x 32) and
 // blocks are small enough in LDS for two (three) of them per CU, which meet their barriers at different times.
+//
+// dgemm_tile_at is the work of one block: tile `tile` of the output (row-major over tiles_m x tiles_n), the k range
+// [kbeg, kend) of slice `slice`.  dgemm_kernel runs it on its block ids, dgemm_batched_kernel on the tile of its item.
 template <int BM, int BN, int WR, int WC, bool AKC, bool BKC, bool VEC>
-__global__ __launch_bounds__(WR* WC * 64, 4) void dgemm_kernel(DgemmArgs a) {
+__device__ __forceinline__ void dgemm_tile_at(const DgemmArgs& a, long tile, long slice, long kbeg, long kend) {
   constexpr int NT = WR * WC * 64;
   constexpr int WM = BM / WR, WN = BN / WC;
   constexpr int FM = WM / 16, FN = WN / 16;
@@ -113,15 +122,8 @@ __global__ __launch_bounds__(WR* WC * 64, 4) void dgemm_kernel(DgemmArgs a) {
   double* Bs = lds + 2 * LA::LDS_DOUBLES;       // [2][LB::LDS_DOUBLES]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = (wave / WC) * WM, wn = (wave % WC) * WN;
-  long tile = blockIdx.x;
-  if (a.remap) {
-    const long per = (long)gridDim.x >> 3;
-    tile = (tile & 7) * per + (tile >> 3);
-  }
   const long tm = tile / a.tiles_n, tn = tile % a.tiles_n;
   const long m0 = tm * BM, n0 = tn * BN;
-  const long kbeg = (long)blockIdx.y * a.k_per_split;
-  const long kend = min(a.K, kbeg + a.k_per_split);
 
   d4 acc[FM][FN];
 #pragma unroll
@@ -172,7 +174,7 @@ __global__ __launch_bounds__(WR* WC * 64, 4) void dgemm_kernel(DgemmArgs a) {
 
   // C / D: column lane & 15, row (lane >> 4) + 4 r
   const bool slab = a.splits > 1;
-  double* C = slab ? a.C + (long)blockIdx.y * a.M * a.N : a.C;
+  double* C = slab ? a.C + slice * a.M * a.N : a.C;
   const long ldc = slab ? a.N : a.ldc;
 #pragma unroll
   for (int i = 0; i < FM; ++i)
@@ -193,6 +195,49 @@ __global__ __launch_bounds__(WR* WC * 64, 4) void dgemm_kernel(DgemmArgs a) {
         C[row * ldc + col] = v;
       }
     }
+}
+
+template <int BM, int BN, int WR, int WC, bool AKC, bool BKC, bool VEC>
+__global__ __launch_bounds__(WR* WC * 64, 4) void dgemm_kernel(DgemmArgs a) {
+  long tile = blockIdx.x;
+  if (a.remap) {
+    const long per = (long)gridDim.x >> 3;
+    tile = (tile & 7) * per + (tile >> 3);
+  }
+  const long kbeg = (long)blockIdx.y * a.k_per_split;
+  const long kend = min(a.K, kbeg + a.k_per_split);
+  dgemm_tile_at<BM, BN, WR, WC, AKC, BKC, VEC>(a, tile, (long)blockIdx.y, kbeg, kend);
+}
+
+// `batch` products of one shape in ONE launch: the batch is folded into grid x (grid y and z stop at 65 535), block id ->
+// (item, tile), and the block runs dgemm_tile_at over the whole K on a copy of the arguments whose three pointers are
+// advanced to its item (block-uniform 64-bit values).  The 64 x 64 tile of eight waves, no k-slices: every output element
+// is one k-ascending chain of matrix instructions, the chain eg_dgemm gives it wherever that takes no slices, whatever
+// tile it picks.  remap (the launch's block count is a multiple of 8, gemm_plan.cpp): every XCD gets a contiguous range of
+// the launch's blocks, so the tiles of one item, which share its A rows and B columns, meet in one L2.
+struct DgemmBatchedArgs {
+  DgemmArgs item;   // item 0 of the launch; splits = 1
+  long stride_a, stride_b, stride_c;   // doubles between consecutive items (0: the operand is shared)
+  int tiles;        // blocks per item
+  int remap;
+};
+
+constexpr int BT = 64;   // the batched tile, <BT, BT, 2, 4>
+
+template <bool AKC, bool BKC, bool VEC>
+__global__ __launch_bounds__(512, 4) void dgemm_batched_kernel(DgemmBatchedArgs b) {
+  int work = (int)blockIdx.x;
+  if (b.remap) {
+    const int per = (int)(gridDim.x >> 3);
+    work = (work & 7) * per + (work >> 3);
+  }
+  const int it = work / b.tiles;
+  const int tile = work - it * b.tiles;
+  DgemmArgs a = b.item;
+  a.A += (long)it * b.stride_a;
+  a.B += (long)it * b.stride_b;
+  a.C += (long)it * b.stride_c;
+  dgemm_tile_at<BT, BT, 2, 4, AKC, BKC, VEC>(a, tile, 0, 0, a.K);
 }
 
 // Second pass of a sliced product: out = (accumulate ? out : 0) + (slab 0 + slab 1 + ...) + bias, slabs in order.
@@ -296,6 +341,38 @@ int launch_dgemm(eg_ctx* ctx, DgemmArgs& a, bool akc, bool bkc, bool vec) {
   return EG_ERR_INVALID;
 }
 
+template <bool AKC, bool BKC, bool VEC>
+int launch_batched_one(eg_ctx* ctx, unsigned grid, const DgemmBatchedArgs& b) {
+  using LA = TileLoader<BT, 512, AKC, VEC>;
+  using LB = TileLoader<BT, 512, BKC, VEC>;
+  constexpr size_t lds = (size_t)2 * (LA::LDS_DOUBLES + LB::LDS_DOUBLES) * sizeof(double);
+  static bool attr_set = false;
+  if (!attr_set) {
+    EG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&dgemm_batched_kernel<AKC, BKC, VEC>),
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    attr_set = true;
+  }
+  hipLaunchKernelGGL((dgemm_batched_kernel<AKC, BKC, VEC>), dim3(grid), dim3(512), lds, ctx->stream, b);
+  EG_HIP_CHECK(hipGetLastError());
+  return EG_OK;
+}
+
+// 8 kernels: four storage orders x (16-byte | 8-byte loads)
+int launch_batched(eg_ctx* ctx, unsigned grid, const DgemmBatchedArgs& b, bool akc, bool bkc, bool vec) {
+#define EG_DGEMM_CASE(AK, BK_, V) \
+  if (akc == AK && bkc == BK_ && vec == V) return launch_batched_one<AK, BK_, V>(ctx, grid, b);
+  EG_DGEMM_CASE(true, true, true)
+  EG_DGEMM_CASE(true, false, true)
+  EG_DGEMM_CASE(false, true, true)
+  EG_DGEMM_CASE(false, false, true)
+  EG_DGEMM_CASE(true, true, false)
+  EG_DGEMM_CASE(true, false, false)
+  EG_DGEMM_CASE(false, true, false)
+  EG_DGEMM_CASE(false, false, false)
+#undef EG_DGEMM_CASE
+  return EG_ERR_INVALID;
+}
+
 }  // namespace
 
 namespace eg {
@@ -327,8 +404,12 @@ int colsum_f64_with_scratch(eg_ctx* ctx, long rows, long cols, const double* in,
 
 }  // namespace eg
 
-extern "C" int eg_dgemm(eg_ctx* ctx, int trans_a, int trans_b, int64_t M, int64_t N, int64_t K, const double* A, int64_t lda, const double* B,
-                        int64_t ldb, double* C, int64_t ldc, int accumulate, const double* bias) {
+namespace eg {
+namespace gemm {
+
+// The one internal entry of the plain float64 product: eg_dgemm and the items of a batch that runs as a loop come here.
+int dgemm(eg_ctx* ctx, int trans_a, int trans_b, long M, long N, long K, const double* A, long lda, const double* B, long ldb, double* C,
+          long ldc, int accumulate, const double* bias) {
   EG_REQUIRE(ctx, EG_ERR_INVALID, "eg_dgemm: ctx is NULL");
   EG_REQUIRE(M >= 0 && N >= 0 && K >= 0, EG_ERR_INVALID, "eg_dgemm: negative extent");
   if (M == 0 || N == 0) return EG_OK;
@@ -419,6 +500,94 @@ extern "C" int eg_dgemm(eg_ctx* ctx, int trans_a, int trans_b, int64_t M, int64_
     EG_HIP_CHECK(hipGetLastError());
   }
   return EG_OK;
+}
+
+// The one internal entry of the batched float64 product: eg_dgemm_batched and the model layer's batched launches
+// (host/run.cpp) both come here.  No workspace, so it may run under graph capture.
+int dgemm_batched(eg_ctx* ctx, int trans_a, int trans_b, long batch, long M, long N, long K, const double* A, long lda, long stride_a,
+                  const double* B, long ldb, long stride_b, double* C, long ldc, long stride_c, int accumulate, const double* bias) {
+  EG_REQUIRE(ctx, EG_ERR_INVALID, "eg_dgemm_batched: ctx is NULL");
+  EG_REQUIRE(batch >= 0 && M >= 0 && N >= 0 && K >= 0, EG_ERR_INVALID, "eg_dgemm_batched: negative extent");
+  if (batch == 0 || M == 0 || N == 0) return EG_OK;
+  EG_REQUIRE(C, EG_ERR_INVALID, "eg_dgemm_batched: C is NULL");
+  EG_REQUIRE(K == 0 || (A && B), EG_ERR_INVALID, "eg_dgemm_batched: NULL operand");
+  EG_REQUIRE(lda >= (trans_a ? M : K) && ldb >= (trans_b ? K : N) && ldc >= N, EG_ERR_INVALID,
+             "eg_dgemm_batched: leading dimension smaller than the row length");
+  EG_REQUIRE(stride_a >= 0 && stride_b >= 0, EG_ERR_INVALID, "eg_dgemm_batched: negative stride");
+  EG_REQUIRE(batch == 1 || stride_c >= (M - 1) * ldc + N, EG_ERR_INVALID, "eg_dgemm_batched: stride_c makes the items of C overlap");
+  int rc = eg::set_device(ctx);
+  if (rc) return rc;
+
+  auto aligned16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+  DgemmBatchedProblem prob;
+  prob.batch = batch;
+  prob.M = M;
+  prob.N = N;
+  prob.K = K;
+  prob.lda = lda;
+  prob.ldb = ldb;
+  prob.stride_a = stride_a;
+  prob.stride_b = stride_b;
+  prob.a_aligned = aligned16(A);
+  prob.b_aligned = aligned16(B);
+  prob.cus = ctx->compute_units;
+  if (const char* e = eg::sw::raw("EG_DGEMM_BATCHED_ROUTE")) prob.force = strcmp(e, "launch") == 0 ? 1 : strcmp(e, "loop") == 0 ? 2 : 0;
+  const DgemmBatchedPlan plan = plan_dgemm_batched(prob);
+  if (plan.loop) {   // every item fills the chip by itself: plain products on their own routes
+    for (long b = 0; b < batch; ++b) {
+      rc = dgemm(ctx, trans_a, trans_b, M, N, K, A ? A + b * stride_a : A, lda, B ? B + b * stride_b : B, ldb, C + b * stride_c, ldc, accumulate,
+                 bias);
+      if (rc) return rc;
+    }
+    return EG_OK;
+  }
+  EG_REQUIRE(plan.tiles > 0 && plan.tiles <= BATCHED_MAX_BLOCKS, EG_ERR_INVALID, "eg_dgemm_batched: an item has too many tiles for one launch");
+  const bool akc = !trans_a, bkc = trans_b != 0;
+  for (long i = 0; i < plan.launches; ++i) {
+    const DgemmBatchedLaunch l = dgemm_batched_launch(plan, batch, i);
+    EG_REQUIRE(l.items > 0 && l.grid > 0 && l.grid <= BATCHED_MAX_BLOCKS, EG_ERR_INVALID, "eg_dgemm_batched: launch out of range");
+    DgemmBatchedArgs args = {};
+    DgemmArgs& a = args.item;
+    a.A = A ? A + l.first * stride_a : A;
+    a.B = B ? B + l.first * stride_b : B;
+    a.C = C + l.first * stride_c;
+    a.bias = bias;
+    a.M = M;
+    a.N = N;
+    a.K = K;
+    a.lda = lda;
+    a.ldb = ldb;
+    a.ldc = ldc;
+    a.accumulate = accumulate;
+    a.splits = 1;
+    a.k_per_split = ((K + BK - 1) / BK) * BK;
+    if (a.k_per_split == 0) a.k_per_split = BK;
+    a.tiles_m = plan.tiles_m;
+    a.tiles_n = plan.tiles_n;
+    args.stride_a = stride_a;
+    args.stride_b = stride_b;
+    args.stride_c = stride_c;
+    args.tiles = (int)plan.tiles;
+    args.remap = l.remap ? 1 : 0;
+    rc = launch_batched(ctx, (unsigned)l.grid, args, akc, bkc, plan.vec);
+    if (rc) return rc;
+  }
+  return EG_OK;
+}
+
+}  // namespace gemm
+}  // namespace eg
+
+extern "C" int eg_dgemm(eg_ctx* ctx, int trans_a, int trans_b, int64_t M, int64_t N, int64_t K, const double* A, int64_t lda, const double* B,
+                        int64_t ldb, double* C, int64_t ldc, int accumulate, const double* bias) {
+  return eg::gemm::dgemm(ctx, trans_a, trans_b, M, N, K, A, lda, B, ldb, C, ldc, accumulate, bias);
+}
+
+extern "C" int eg_dgemm_batched(eg_ctx* ctx, int trans_a, int trans_b, int64_t batch, int64_t M, int64_t N, int64_t K, const double* A,
+                                int64_t lda, int64_t stride_a, const double* B, int64_t ldb, int64_t stride_b, double* C, int64_t ldc,
+                                int64_t stride_c, int accumulate, const double* bias) {
+  return eg::gemm::dgemm_batched(ctx, trans_a, trans_b, batch, M, N, K, A, lda, stride_a, B, ldb, stride_b, C, ldc, stride_c, accumulate,
+                                 bias);
 }
 
 extern "C" int eg_fill_f64(eg_ctx* ctx, int64_t n, double value, double* out) {

@@ -53,6 +53,12 @@ int sgemm_split(eg_ctx* ctx, int trans_a, int trans_b, long M, long N, long K, c
 // and the model layer's batched launches run.
 int sgemm_batched(eg_ctx* ctx, int trans_a, int trans_b, long batch, long M, long N, long K, const float* A, long lda, long stride_a,
                   const float* B, long ldb, long stride_b, float* C, long ldc, long stride_c, int accumulate, const float* bias);
+// The float64 twins (gemm_f64_mfma.hip): the plain product behind eg_dgemm, and `batch` of them in one launch — what
+// eg_dgemm_batched and a float64 model's batched launches run.  Strides and leading dimensions in doubles.
+int dgemm(eg_ctx* ctx, int trans_a, int trans_b, long M, long N, long K, const double* A, long lda, const double* B, long ldb, double* C,
+          long ldc, int accumulate, const double* bias);
+int dgemm_batched(eg_ctx* ctx, int trans_a, int trans_b, long batch, long M, long N, long K, const double* A, long lda, long stride_a,
+                  const double* B, long ldb, long stride_b, double* C, long ldc, long stride_c, int accumulate, const double* bias);
 // The planner's switches as the exact product reads them (gemm_plan.hpp; gemm_f32_mfma.hip keeps them per thread).
 struct GemmSwitches;
 const GemmSwitches& current_switches();

@@ -624,6 +624,52 @@ bool batched_runs_as_loop(const GemmProblem& item, const GemmSwitches& sw) {
   return p.grid >= item.cus && p.route != Route::Small;
 }
 
+bool dgemm_batched_vec(const DgemmBatchedProblem& p) {
+  const bool strides_even = p.batch <= 1 || (p.stride_a % 2 == 0 && p.stride_b % 2 == 0);
+  return p.lda % 2 == 0 && p.ldb % 2 == 0 && p.a_aligned && p.b_aligned && strides_even;
+}
+
+// The rule: an item whose 64 x 64 tiles number at least DGEMM_LOOP_TILES_PER_CU per CU runs as a plain product — it
+// has a block for every CU by itself, the condition of the float32 rule (batched_runs_as_loop), and eg_dgemm may give it a
+// larger tile.  K does not enter: k-slices are what eg_dgemm adds for few tiles and a long K, and such items are on the
+// batched side, where the batch is what fills the chip.
+// THE THRESHOLD HAS NOT BEEN MEASURED: tools/bench_batched_f64.py times both sides of it (its "forced" columns, at one tile
+// row less than, exactly and one more than a tile per CU), but no run of it on an MI355X exists yet, so there are no
+// figures to write beside the rule and profiles/ has no batched_dgemm.txt.  1 is the float32 rule's number, not a result.
+constexpr long DGEMM_LOOP_TILES_PER_CU = 1;
+
+bool dgemm_batched_runs_as_loop(long M, long N, long K, int cus) {
+  (void)K;
+  const long T = DGEMM_BATCHED_TILE;
+  const long tiles = ((M + T - 1) / T) * ((N + T - 1) / T);
+  return tiles >= DGEMM_LOOP_TILES_PER_CU * std::max(cus, 1) || tiles > BATCHED_MAX_BLOCKS;
+}
+
+DgemmBatchedPlan plan_dgemm_batched(const DgemmBatchedProblem& p) {
+  DgemmBatchedPlan r;
+  const long T = DGEMM_BATCHED_TILE;
+  r.loop = dgemm_batched_runs_as_loop(p.M, p.N, p.K, p.cus);
+  if (p.force == 2) r.loop = true;
+  if (p.force == 1) r.loop = ((p.M + T - 1) / T) * ((p.N + T - 1) / T) > BATCHED_MAX_BLOCKS;
+  if (r.loop || p.batch <= 0 || p.M <= 0 || p.N <= 0) return r;
+  r.vec = dgemm_batched_vec(p);
+  r.tiles_m = (int)((p.M + T - 1) / T);
+  r.tiles_n = (int)((p.N + T - 1) / T);
+  r.tiles = (long)r.tiles_m * r.tiles_n;
+  r.items_per_launch = std::max(1L, BATCHED_MAX_BLOCKS / r.tiles);
+  r.launches = (p.batch + r.items_per_launch - 1) / r.items_per_launch;
+  return r;
+}
+
+DgemmBatchedLaunch dgemm_batched_launch(const DgemmBatchedPlan& plan, long batch, long index) {
+  DgemmBatchedLaunch l;
+  l.first = index * plan.items_per_launch;
+  l.items = std::min(plan.items_per_launch, batch - l.first);
+  l.grid = l.items * plan.tiles;
+  l.remap = l.grid % 8 == 0 && l.grid >= 16;
+  return l;
+}
+
 bool exact_single_launch(const GemmPlan& p) {
   return p.route == Route::Bk32 || (p.route == Route::Generic && p.bm == 256 && p.bn == 256 && !p.edge && p.splits <= 1 &&
                                     p.tail_tiles == 0 && p.second == Second::None);

@@ -110,6 +110,49 @@ GemmPlan plan_gemm_batched(const GemmProblem& item, long batch, const GemmSwitch
 // products on their own routes.  Decided from the item alone, so that an item has the same bits whatever batch it is part of.
 bool batched_runs_as_loop(const GemmProblem& item, const GemmSwitches& sw);
 
+// ---- float64: `batch` products of one shape (gemm_f64_mfma.hip, dgemm_batched_kernel) ---------------------------------
+// Blocks of one batched launch, float32 and float64: grid x block threads stays below 2^32 and the block id an int.
+constexpr long BATCHED_MAX_BLOCKS = 1L << 22;
+constexpr int DGEMM_BATCHED_TILE = 64;   // the one tile the batched float64 kernel is built for
+
+// One call as the planner sees it.  Leading dimensions and strides in doubles; a stride of 0 shares the operand.
+struct DgemmBatchedProblem {
+  long batch = 0, M = 0, N = 0, K = 0;
+  long lda = 0, ldb = 0, stride_a = 0, stride_b = 0;
+  bool a_aligned = true, b_aligned = true;   // 16-byte aligned base pointers of item 0
+  int cus = 256;
+  int force = 0;   // EG_DGEMM_BATCHED_ROUTE (measurement aid), set by the caller: 1 one launch, 2 the loop
+};
+
+struct DgemmBatchedPlan {
+  bool loop = false;   // every item is a plain float64 product on its own route; the fields below are then unused
+  bool vec = false;    // 16-byte loads (dgemm_batched_vec)
+  int tiles_m = 0, tiles_n = 0;
+  long tiles = 0;             // blocks per item
+  long items_per_launch = 0;  // BATCHED_MAX_BLOCKS / tiles
+  long launches = 0;
+};
+
+// Launch `index` of a plan: items [first, first + items), grid = items x tiles blocks.  remap: the block count is a
+// multiple of 8 and at least 16, so the kernel hands every XCD a contiguous range of the launch's blocks.
+struct DgemmBatchedLaunch {
+  long first = 0, items = 0, grid = 0;
+  bool remap = false;
+};
+
+// 16-byte loads: a piece is two doubles that are neighbours in memory, at an even offset from its item's base, so every
+// row start (lda, ldb even), item 0 (both bases 16-byte aligned) and every further item (stride_a, stride_b even wherever
+// the batch has a second item; a shared operand's stride of 0 is even) must be 16-byte aligned.  Anything else: 8-byte loads.
+bool dgemm_batched_vec(const DgemmBatchedProblem& p);
+
+// Does one item fill the chip by itself?  Then the batch runs as a loop of plain float64 products, each on its own route
+// (tile, k-slices).  Decided from the item alone — never from the batch —, so that an item has the same route, and the same
+// bits, whatever batch it is part of.  (gemm_plan.cpp has the rule and what was measured.)
+bool dgemm_batched_runs_as_loop(long M, long N, long K, int cus);
+
+DgemmBatchedPlan plan_dgemm_batched(const DgemmBatchedProblem& p);
+DgemmBatchedLaunch dgemm_batched_launch(const DgemmBatchedPlan& plan, long batch, long index);
+
 // Is the plan ONE launch of the whole-tile 256 x 256 kernel (no k-slices, tail slices or second pass)?  Only such a launch
 // can stand behind the split-bf16 product as its fallback: GemmArgs::run_if gates the tile kernel, not the reduce kernels.
 bool exact_single_launch(const GemmPlan& p);

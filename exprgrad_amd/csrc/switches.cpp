@@ -96,6 +96,7 @@ const Row kSwitches[] = {
     {"EG_STREAMK_MIN_RATIO", "tuning", "microseconds the balance model must promise before a 64 x 64 launch goes stream-K (default 24)"},
     {"EG_GEMM_SMALL_BK32", "tuning", "32-deep k-tiles for every 64 x 64 launch"},
     {"EG_DGEMM_TILE", "tuning", "config[,splits]: force the float64 tile"},
+    {"EG_DGEMM_BATCHED_ROUTE", "tuning", "launch | loop: force eg_dgemm_batched onto the one-launch kernel or the loop of plain products"},
     {"EG_CONV_BAND_PIXELS", "tuning", "pixels per band of the band convolutions"},
     {"EG_CONV_DIRECT_BLOCKS", "tuning", "block cap of the direct filter gradient"},
     {"EG_ROW_TAIL_BLOCKS", "tuning", "blocks of a row group that carries a tail (default: 12 KB of rows per block, at least 64)"},

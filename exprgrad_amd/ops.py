@@ -36,6 +36,14 @@ def sgemm_batched(ctx, batch, M, N, K, A, lda, stride_a, B, ldb, stride_b, C, ld
          _p(C), ldc, stride_c, int(accumulate), _p(bias))
 
 
+def dgemm_batched(ctx, batch, M, N, K, A, lda, stride_a, B, ldb, stride_b, C, ldc, stride_c, trans_a=False, trans_b=False,
+                  accumulate=False, bias=None):
+    """The float64 form of sgemm_batched: item b uses A + b * stride_a, B + b * stride_b, C + b * stride_c (strides and
+    leading dimensions in doubles; stride_a / stride_b 0: the operand is shared)."""
+    call("eg_dgemm_batched", ctx.handle, int(trans_a), int(trans_b), batch, M, N, K, _p(A), lda, stride_a, _p(B), ldb, stride_b,
+         _p(C), ldc, stride_c, int(accumulate), _p(bias))
+
+
 def bias_add(ctx, rows, cols, bias, out, accumulate=True):
     call("eg_bias_add", ctx.handle, rows, cols, _p(bias), _p(out), int(accumulate))
 

@@ -236,6 +236,23 @@ int eg_conv2_nhwc_grad_image(eg_ctx* ctx, int64_t N, int64_t H, int64_t W, int64
  *   fixed order), eg_colsum_f64 / eg_fill_f64 / eg_fill_uniform_f64: as eg_colsum / eg_fill_f32 / eg_fill_uniform. */
 int eg_dgemm(eg_ctx* ctx, int trans_a, int trans_b, int64_t M, int64_t N, int64_t K, const double* A, int64_t lda,
              const double* B, int64_t ldb, double* C, int64_t ldc, int accumulate, const double* bias);
+/* eg_dgemm_batched: the float64 form of eg_sgemm_batched, with its conventions word for word.
+ * C_b[m,n] (+)= sum_k opA_b(m,k) * opB_b(k,n) (+ bias[n]) for b in [0, batch): X_b = X + b * stride_x, strides in doubles.
+ * stride_a == 0 or stride_b == 0: that operand is shared by all items; bias is shared by all items.
+ * stride_c >= (M - 1) * ldc + N when batch > 1.
+ * One launch of batch x tiles blocks on 64 x 64 tiles (kernels/gemm_f64_mfma.hip, dgemm_batched_kernel): no k-slices, no
+ * second pass, no workspace, no atomics.  Every output element is one k-ascending chain of `v_mfma_f64_16x16x4_f64`, so an
+ * item has the same bits whatever batch it is part of, and the bits of eg_dgemm wherever that takes no k-slices (it
+ * considers them for K >= 512 only).  Items that fill the chip by themselves (at least one 64 x 64 tile per compute unit)
+ * run as a loop of plain float64 products instead, each on eg_dgemm's own route.
+ * Covers out[g,i,j] ++= a[g,i,k] * b[g,k,j] of a compile[float64] program (base.nim:27-28 with a leading batch index;
+ * model.nim:253-260) and its two derived gradients (passes.nim:519-549; trans_b = 1 / trans_a = 1, as for eg_dgemm).
+ * EG_ERR_INVALID: a NULL ctx, a negative extent or stride, a leading dimension shorter than a row, a stride_c that makes
+ * items overlap, a NULL pointer with a non-empty product.  batch == 0 and empty products succeed and launch nothing;
+ * K == 0 with accumulate == 0 writes bias or zeros. */
+int eg_dgemm_batched(eg_ctx* ctx, int trans_a, int trans_b, int64_t batch, int64_t M, int64_t N, int64_t K,
+                     const double* A, int64_t lda, int64_t stride_a, const double* B, int64_t ldb, int64_t stride_b,
+                     double* C, int64_t ldc, int64_t stride_c, int accumulate, const double* bias);
 int eg_colsum_f64(eg_ctx* ctx, int64_t rows, int64_t cols, const double* in, double* out, int accumulate);
 int eg_fill_f64(eg_ctx* ctx, int64_t n, double value, double* out);
 int eg_fill_uniform_f64(eg_ctx* ctx, int64_t n, double lo, double hi, const uint64_t* state, uint64_t stream, double* out);
