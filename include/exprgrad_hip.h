@@ -145,6 +145,12 @@ int eg_kernel_launch(eg_kernel* kernel, int dims, const int64_t* groups, const i
  * (dnn.nim:19-24), and the two derived gradient contractions of passes.nim:519-549:
  *   gradA[y,it] += g[y,x]*B[it,x]  -> trans_b = 1      gradB[it,x] += A[y,it]*g[y,x] -> trans_a = 1
  * bias may be NULL.
+ * A, B, C and bias may be views into larger tensors (tests/test_gpu_gemm_views.py holds every route to this):
+ *   - no alignment is required of any pointer, and ldc >= N; alignment and leading dimensions only choose the kernel;
+ *   - elements of A and B outside the rows x cols view (behind a row's end, in front of the pointer, behind the last
+ *     row, which needs no padding) are never used, whatever they hold — NaN included;
+ *   - elements of C outside the M x N view are never written;
+ *   - with accumulate == 0, C is not read.
  * Large products (M, N multiples of 256 with at least one 256 x 256 tile per CU, K a multiple of 32 and >= 2048) run
  * as six bf16 matrix-core terms of an exact three-way operand split (kernels/gemm_split_bf16.hip): not bit-identical
  * to the exact f32 path, with an error against float64 no larger than its own.  An operand with
@@ -233,7 +239,10 @@ int eg_conv2_nhwc_grad_image(eg_ctx* ctx, int64_t N, int64_t H, int64_t W, int64
 /* float64 forms of the library kernels — what a `compile[float64]` model (model.nim:253-260: every kernel of the
  * program instantiated over Scalar64) runs on; same conventions as their float32 namesakes above.
  *   eg_dgemm: `v_mfma_f64_16x16x4_f64` tiles (exact float64 multiply-adds in k order; sliced products are summed in a
- *   fixed order), eg_colsum_f64 / eg_fill_f64 / eg_fill_uniform_f64: as eg_colsum / eg_fill_f32 / eg_fill_uniform. */
+ *   fixed order), eg_colsum_f64 / eg_fill_f64 / eg_fill_uniform_f64: as eg_colsum / eg_fill_f32 / eg_fill_uniform.
+ *   eg_dgemm on views, as eg_sgemm: no alignment is required of any pointer (16-byte loads are taken when lda and ldb
+ *   are even and A and B 16-byte aligned); elements of A and B outside the rows x cols view are never used, whatever
+ *   they hold; elements of C outside the M x N view are never written; with accumulate == 0, C is not read. */
 int eg_dgemm(eg_ctx* ctx, int trans_a, int trans_b, int64_t M, int64_t N, int64_t K, const double* A, int64_t lda,
              const double* B, int64_t ldb, double* C, int64_t ldc, int accumulate, const double* bias);
 /* eg_dgemm_batched: the float64 form of eg_sgemm_batched, with its conventions word for word.
