@@ -8,6 +8,7 @@
 // plan_gemm_batched (gemm_plan.cpp).  No k-slices, no second pass, no workspace, no atomics, never the split-bf16 route.
 #include "gemm_f32_mfma.hpp"
 #include "gemm_fused.hpp"
+#include "gemm_layout.hpp"
 #include "gemm_plan.hpp"
 
 #include <algorithm>
@@ -41,14 +42,6 @@ gemm_batched_kernel(BatchedArgs b) {
 }
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-template <class F>
-void with_layout(bool a_kc, bool b_kc, F&& f) {
-  if (a_kc && !b_kc) f(std::true_type(), std::false_type());         // NN
-  else if (a_kc && b_kc) f(std::true_type(), std::true_type());      // NT
-  else if (!a_kc && !b_kc) f(std::false_type(), std::false_type());  // TN
-  else f(std::false_type(), std::true_type());                       // TT
-}
 
 constexpr int TILE = 64;   // the one tile of plan_gemm_batched
 

@@ -10,6 +10,7 @@
 #include "gemm_skinny.hpp"
 #include "gemm_f32_pair.hpp"
 #include "gemm_fused.hpp"
+#include "gemm_layout.hpp"
 #include "gemm_plan.hpp"
 
 #include <algorithm>
@@ -75,15 +76,6 @@ GemmArgs sgemm_args(long M, long N, long K, const float* A, long lda, const floa
 GemmProblem sgemm_problem(const eg_ctx* ctx, const GemmArgs& a, bool a_kc, bool b_kc) {
   const bool vec_a = operand_vec(a.lda, a_kc ? a.K : a.M, aligned16(a.A)), vec_b = operand_vec(a.ldb, b_kc ? a.K : a.N, aligned16(a.B));
   return problem_of(ctx, a, a_kc, b_kc, 0, vec_a && vec_b, vec_a && !vec_b);
-}
-
-// Calls f(std::bool_constant<A_KC>, std::bool_constant<B_KC>) for the runtime operand layout.
-template <class F>
-void with_layout(bool a_kc, bool b_kc, F&& f) {
-  if (a_kc && !b_kc) f(std::true_type(), std::false_type());         // NN
-  else if (a_kc && b_kc) f(std::true_type(), std::true_type());      // NT
-  else if (!a_kc && !b_kc) f(std::false_type(), std::false_type());  // TN
-  else f(std::false_type(), std::true_type());                       // TT
 }
 
 template <int BM, int BN, int KB, bool AKC, bool BKC, int V, bool E, int CV>

@@ -21,6 +21,7 @@
 
 #include "../eg_internal.hpp"
 #include "gemm_fused.hpp"
+#include "gemm_layout.hpp"
 #include "gemm_plan.hpp"
 
 namespace {
@@ -305,8 +306,10 @@ __global__ __launch_bounds__(256) void fill_uniform_f64_kernel(double* __restric
   }
 }
 
+using eg::gemm::DgemmPlan;
+
 template <int BM, int BN, int WR, int WC, bool AKC, bool BKC, bool VEC>
-int launch_one(eg_ctx* ctx, DgemmArgs& a) {
+int launch_one(eg_ctx* ctx, const DgemmPlan& p, const DgemmArgs& a) {
   using LA = TileLoader<BM, WR * WC * 64, AKC, VEC>;
   using LB = TileLoader<BN, WR * WC * 64, BKC, VEC>;
   constexpr size_t lds = (size_t)2 * (LA::LDS_DOUBLES + LB::LDS_DOUBLES) * sizeof(double);
@@ -316,29 +319,17 @@ int launch_one(eg_ctx* ctx, DgemmArgs& a) {
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     attr_set = true;
   }
-  a.tiles_m = (int)((a.M + BM - 1) / BM);
-  a.tiles_n = (int)((a.N + BN - 1) / BN);
-  const long tiles = (long)a.tiles_m * a.tiles_n;
-  a.remap = tiles % 8 == 0 && tiles >= 16;
-  hipLaunchKernelGGL((dgemm_kernel<BM, BN, WR, WC, AKC, BKC, VEC>), dim3((unsigned)tiles, (unsigned)a.splits), dim3(WR * WC * 64), lds, ctx->stream, a);
+  hipLaunchKernelGGL((dgemm_kernel<BM, BN, WR, WC, AKC, BKC, VEC>), dim3((unsigned)p.grid_x, (unsigned)p.grid_y), dim3(WR * WC * 64), lds, ctx->stream, a);
   EG_HIP_CHECK(hipGetLastError());
   return EG_OK;
 }
 
+// 8 kernels per tile: four storage orders x (16-byte | 8-byte loads)
 template <int BM, int BN, int WR, int WC>
-int launch_dgemm(eg_ctx* ctx, DgemmArgs& a, bool akc, bool bkc, bool vec) {
-#define EG_DGEMM_CASE(AK, BK_, V) \
-  if (akc == AK && bkc == BK_ && vec == V) return launch_one<BM, BN, WR, WC, AK, BK_, V>(ctx, a);
-  EG_DGEMM_CASE(true, true, true)
-  EG_DGEMM_CASE(true, false, true)
-  EG_DGEMM_CASE(false, true, true)
-  EG_DGEMM_CASE(false, false, true)
-  EG_DGEMM_CASE(true, true, false)
-  EG_DGEMM_CASE(true, false, false)
-  EG_DGEMM_CASE(false, true, false)
-  EG_DGEMM_CASE(false, false, false)
-#undef EG_DGEMM_CASE
-  return EG_ERR_INVALID;
+int launch_dgemm(eg_ctx* ctx, const DgemmPlan& p, const DgemmArgs& a, bool akc, bool bkc) {
+  int rc = EG_ERR_INVALID;
+  eg::gemm::with_layout_vec(akc, bkc, p.vec, [&](auto ak, auto bk, auto v) { rc = launch_one<BM, BN, WR, WC, ak, bk, v>(ctx, p, a); });
+  return rc;
 }
 
 template <bool AKC, bool BKC, bool VEC>
@@ -357,20 +348,33 @@ int launch_batched_one(eg_ctx* ctx, unsigned grid, const DgemmBatchedArgs& b) {
   return EG_OK;
 }
 
-// 8 kernels: four storage orders x (16-byte | 8-byte loads)
 int launch_batched(eg_ctx* ctx, unsigned grid, const DgemmBatchedArgs& b, bool akc, bool bkc, bool vec) {
-#define EG_DGEMM_CASE(AK, BK_, V) \
-  if (akc == AK && bkc == BK_ && vec == V) return launch_batched_one<AK, BK_, V>(ctx, grid, b);
-  EG_DGEMM_CASE(true, true, true)
-  EG_DGEMM_CASE(true, false, true)
-  EG_DGEMM_CASE(false, true, true)
-  EG_DGEMM_CASE(false, false, true)
-  EG_DGEMM_CASE(true, true, false)
-  EG_DGEMM_CASE(true, false, false)
-  EG_DGEMM_CASE(false, true, false)
-  EG_DGEMM_CASE(false, false, false)
-#undef EG_DGEMM_CASE
-  return EG_ERR_INVALID;
+  int rc = EG_ERR_INVALID;
+  eg::gemm::with_layout_vec(akc, bkc, vec, [&](auto ak, auto bk, auto v) { rc = launch_batched_one<ak, bk, v>(ctx, grid, b); });
+  return rc;
+}
+
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// The argument checks of eg_dgemm and eg_dgemm_batched (`who`; the plain product is a batch of one).  empty: the call is
+// valid and there is nothing to compute.
+int check_product(const char* who, const eg_ctx* ctx, int trans_a, int trans_b, long batch, long M, long N, long K, const double* A, long lda,
+                  const double* B, long ldb, const double* C, long ldc, bool& empty) {
+  EG_REQUIRE(ctx, EG_ERR_INVALID, "%s: ctx is NULL", who);
+  EG_REQUIRE(batch >= 0 && M >= 0 && N >= 0 && K >= 0, EG_ERR_INVALID, "%s: negative extent", who);
+  empty = batch == 0 || M == 0 || N == 0;
+  if (empty) return EG_OK;
+  EG_REQUIRE(C, EG_ERR_INVALID, "%s: C is NULL", who);
+  EG_REQUIRE(K == 0 || (A && B), EG_ERR_INVALID, "%s: NULL operand", who);
+  EG_REQUIRE(lda >= (trans_a ? M : K) && ldb >= (trans_b ? K : N) && ldc >= N, EG_ERR_INVALID, "%s: leading dimension smaller than the row length",
+             who);
+  return EG_OK;
+}
+
+// The arguments of a plain launch (C: the destination, or the slabs of a sliced product) or of item 0 of a batched one.
+DgemmArgs dgemm_args(const double* A, long lda, const double* B, long ldb, double* C, long ldc, const double* bias, long M, long N, long K,
+                     int accumulate, int splits, long k_per_split, int tiles_m, int tiles_n, bool remap) {
+  return {A, B, C, bias, M, N, K, lda, ldb, ldc, accumulate, splits, k_per_split, tiles_m, tiles_n, remap ? 1 : 0};
 }
 
 }  // namespace
@@ -408,129 +412,55 @@ namespace eg {
 namespace gemm {
 
 // The one internal entry of the plain float64 product: eg_dgemm and the items of a batch that runs as a loop come here.
+// plan_dgemm (gemm_plan.cpp) decides tile, k-slices and geometry; this turns its plan into launches.
 int dgemm(eg_ctx* ctx, int trans_a, int trans_b, long M, long N, long K, const double* A, long lda, const double* B, long ldb, double* C,
           long ldc, int accumulate, const double* bias) {
-  EG_REQUIRE(ctx, EG_ERR_INVALID, "eg_dgemm: ctx is NULL");
-  EG_REQUIRE(M >= 0 && N >= 0 && K >= 0, EG_ERR_INVALID, "eg_dgemm: negative extent");
-  if (M == 0 || N == 0) return EG_OK;
-  EG_REQUIRE(C, EG_ERR_INVALID, "eg_dgemm: C is NULL");
-  EG_REQUIRE(K == 0 || (A && B), EG_ERR_INVALID, "eg_dgemm: NULL operand");
-  EG_REQUIRE(lda >= (trans_a ? M : K) && ldb >= (trans_b ? K : N) && ldc >= N, EG_ERR_INVALID,
-             "eg_dgemm: leading dimension smaller than the row length");
-  int rc = eg::set_device(ctx);
+  bool empty = false;
+  int rc = check_product("eg_dgemm", ctx, trans_a, trans_b, 1, M, N, K, A, lda, B, ldb, C, ldc, empty);
+  if (rc || empty) return rc;
+  rc = eg::set_device(ctx);
   if (rc) return rc;
-  DgemmArgs a = {};
-  a.A = A;
-  a.B = B;
-  a.C = C;
-  a.bias = bias;
-  a.M = M;
-  a.N = N;
-  a.K = K;
-  a.lda = lda;
-  a.ldb = ldb;
-  a.ldc = ldc;
+  DgemmProblem prob = {M, N, K, lda, ldb, aligned16(A), aligned16(B), ctx->compute_units};
+  if (const char* e = eg::sw::raw("EG_DGEMM_TILE")) {  // measurement aid: "<config>[,<splits>]"; without the count the model's slices stay
+    prob.force_config = atoi(e);
+    if (const char* comma = strchr(e, ',')) prob.force_splits = atol(comma + 1) > 0 ? atol(comma + 1) : 1;
+  }
+  const DgemmPlan p = plan_dgemm(prob);
+  if (p.workspace_doubles > 0) {
+    rc = eg::ensure_workspace(ctx, (size_t)p.workspace_doubles * sizeof(double));
+    if (rc) return rc;
+  }
+  double* slabs = static_cast<double*>(ctx->workspace);
+  const DgemmArgs a = dgemm_args(A, lda, B, ldb, p.reduce ? slabs : C, ldc, bias, M, N, K, accumulate, p.splits, p.k_per_split, p.tiles_m, p.tiles_n, p.remap);
   // A(m, k): [M, K] rows are k-contiguous unless transposed; B(k, n): [K, N] rows are n-contiguous unless transposed
   const bool akc = !trans_a, bkc = trans_b != 0;
-  const bool vec = lda % 2 == 0 && ldb % 2 == 0 && (reinterpret_cast<uintptr_t>(A) & 15) == 0 && (reinterpret_cast<uintptr_t>(B) & 15) == 0;
-  a.accumulate = accumulate;
-  a.splits = 1;
-  a.k_per_split = ((K + BK - 1) / BK) * BK;
-  if (a.k_per_split == 0) a.k_per_split = BK;
-  // Tile shape by a small time model.  What a SIMD's matrix pipe delivers depends on how many waves multiply on it at the
-  // same time (tools/mfma_ceiling_f64.hip: one wave 0.44 of peak, two 0.99 in a bare loop), so a launch is priced as
-  // rounds of resident blocks, each round at the rate of the waves it puts on a SIMD:
-  //   config        waves  blocks / CU (LDS)   relative loop efficiency
-  //   128 x 128     8      2 (74 KB)           1.00
-  //   128 x  64     8      2 (55 KB)           0.97
-  //    64 x  64     8      4 (37 KB)           0.92
-  const long cus = ctx->compute_units;
-  struct Cfg { int bm, bn, cap; double eff; };
-  static const Cfg cfgs[3] = {{128, 128, 2, 1.0}, {128, 64, 2, 0.97}, {64, 64, 4, 0.92}};
-  auto rate = [](long waves_per_simd) { return waves_per_simd <= 1 ? 0.44 : waves_per_simd == 2 ? 0.80 : waves_per_simd == 3 ? 0.88 : 0.92; };
-  auto cost = [&](const Cfg& c, long splits) {
-    const long tiles = ((M + c.bm - 1) / c.bm) * ((N + c.bn - 1) / c.bn) * splits;
-    const double t_tile = (double)c.bm * c.bn * ((double)K / splits) / c.eff;  // matrix work of one block at the pipe's full rate
-    const long slots = cus * c.cap;
-    const long full = tiles / slots, rem = tiles % slots;
-    double t = (double)full * c.cap * t_tile / rate(2L * c.cap);  // 8-wave blocks: two waves per SIMD each
-    if (rem > 0) {
-      const long per_cu = (rem + cus - 1) / cus;
-      t += (double)per_cu * t_tile / rate(2L * per_cu);
-    }
-    // slabs out and back (16 bytes per element and slice at ~3 TB/s, in units of a CU's 64 multiply-adds per clock) and a second launch (~5 us)
-    if (splits > 1) t += (double)M * N * splits * 1.0 + 8.0e5;
-    return t;
-  };
-  int best = 0;
-  long best_splits = 1;
-  double best_t = 1e300;
-  for (int c = 0; c < 3; ++c)
-    for (long splits = 1; splits <= 64 && (splits == 1 || K / splits >= 256); splits *= 2) {
-      const double t = cost(cfgs[c], splits);
-      if (t < best_t) {
-        best_t = t;
-        best = c;
-        best_splits = splits;
-      }
-    }
-  if (const char* e = eg::sw::raw("EG_DGEMM_TILE")) {  // measurement aid: "<config>[,<splits>]"
-    best = atoi(e) % 3;
-    if (const char* comma = strchr(e, ',')) best_splits = atol(comma + 1) > 0 ? atol(comma + 1) : 1;
-  }
-  if (best_splits > 1) {
-    long per = (K + best_splits - 1) / best_splits;
-    per = ((per + BK - 1) / BK) * BK;
-    const long splits = (K + per - 1) / per;
-    if (splits > 1) {
-      rc = eg::ensure_workspace(ctx, (size_t)splits * M * N * sizeof(double));
-      if (rc) return rc;
-      a.splits = (int)splits;
-      a.k_per_split = per;
-      a.C = static_cast<double*>(ctx->workspace);
-    }
-  }
-  rc = best == 0   ? launch_dgemm<128, 128, 2, 4>(ctx, a, akc, bkc, vec)
-       : best == 1 ? launch_dgemm<128, 64, 4, 2>(ctx, a, akc, bkc, vec)
-                   : launch_dgemm<64, 64, 2, 4>(ctx, a, akc, bkc, vec);
+  rc = p.config == 0   ? launch_dgemm<128, 128, 2, 4>(ctx, p, a, akc, bkc)
+       : p.config == 1 ? launch_dgemm<128, 64, 4, 2>(ctx, p, a, akc, bkc)
+                       : launch_dgemm<64, 64, 2, 4>(ctx, p, a, akc, bkc);
   if (rc) return rc;
-  if (a.splits > 1) {
-    hipLaunchKernelGGL(dgemm_reduce_kernel, dim3((unsigned)((M * N + 255) / 256)), dim3(256), 0, ctx->stream, static_cast<const double*>(ctx->workspace), C,
-                       bias, (long)M, (long)N, (long)ldc, a.splits, accumulate);
+  if (p.reduce) {
+    hipLaunchKernelGGL(dgemm_reduce_kernel, dim3((unsigned)((M * N + 255) / 256)), dim3(256), 0, ctx->stream, slabs, C, bias, (long)M, (long)N,
+                       (long)ldc, p.splits, accumulate);
     EG_HIP_CHECK(hipGetLastError());
   }
   return EG_OK;
 }
 
 // The one internal entry of the batched float64 product: eg_dgemm_batched and the model layer's batched launches
-// (host/run.cpp) both come here.  No workspace, so it may run under graph capture.
+// (host/run.cpp) both come here.  The one-launch side takes no workspace, so it may run under graph capture.  The loop
+// side is dgemm() per item: it takes the workspace wherever plan_dgemm slices the item (DgemmBatchedPlan::item says
+// whether and how much), which the model layer's eager run of a launch sequence sizes before the sequence is captured.
 int dgemm_batched(eg_ctx* ctx, int trans_a, int trans_b, long batch, long M, long N, long K, const double* A, long lda, long stride_a,
                   const double* B, long ldb, long stride_b, double* C, long ldc, long stride_c, int accumulate, const double* bias) {
-  EG_REQUIRE(ctx, EG_ERR_INVALID, "eg_dgemm_batched: ctx is NULL");
-  EG_REQUIRE(batch >= 0 && M >= 0 && N >= 0 && K >= 0, EG_ERR_INVALID, "eg_dgemm_batched: negative extent");
-  if (batch == 0 || M == 0 || N == 0) return EG_OK;
-  EG_REQUIRE(C, EG_ERR_INVALID, "eg_dgemm_batched: C is NULL");
-  EG_REQUIRE(K == 0 || (A && B), EG_ERR_INVALID, "eg_dgemm_batched: NULL operand");
-  EG_REQUIRE(lda >= (trans_a ? M : K) && ldb >= (trans_b ? K : N) && ldc >= N, EG_ERR_INVALID,
-             "eg_dgemm_batched: leading dimension smaller than the row length");
+  bool empty = false;
+  int rc = check_product("eg_dgemm_batched", ctx, trans_a, trans_b, batch, M, N, K, A, lda, B, ldb, C, ldc, empty);
+  if (rc || empty) return rc;
   EG_REQUIRE(stride_a >= 0 && stride_b >= 0, EG_ERR_INVALID, "eg_dgemm_batched: negative stride");
   EG_REQUIRE(batch == 1 || stride_c >= (M - 1) * ldc + N, EG_ERR_INVALID, "eg_dgemm_batched: stride_c makes the items of C overlap");
-  int rc = eg::set_device(ctx);
+  rc = eg::set_device(ctx);
   if (rc) return rc;
 
-  auto aligned16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  DgemmBatchedProblem prob;
-  prob.batch = batch;
-  prob.M = M;
-  prob.N = N;
-  prob.K = K;
-  prob.lda = lda;
-  prob.ldb = ldb;
-  prob.stride_a = stride_a;
-  prob.stride_b = stride_b;
-  prob.a_aligned = aligned16(A);
-  prob.b_aligned = aligned16(B);
-  prob.cus = ctx->compute_units;
+  DgemmBatchedProblem prob = {batch, M, N, K, lda, ldb, stride_a, stride_b, aligned16(A), aligned16(B), ctx->compute_units};
   if (const char* e = eg::sw::raw("EG_DGEMM_BATCHED_ROUTE")) prob.force = strcmp(e, "launch") == 0 ? 1 : strcmp(e, "loop") == 0 ? 2 : 0;
   const DgemmBatchedPlan plan = plan_dgemm_batched(prob);
   if (plan.loop) {   // every item fills the chip by itself: plain products on their own routes
@@ -546,29 +476,9 @@ int dgemm_batched(eg_ctx* ctx, int trans_a, int trans_b, long batch, long M, lon
   for (long i = 0; i < plan.launches; ++i) {
     const DgemmBatchedLaunch l = dgemm_batched_launch(plan, batch, i);
     EG_REQUIRE(l.items > 0 && l.grid > 0 && l.grid <= BATCHED_MAX_BLOCKS, EG_ERR_INVALID, "eg_dgemm_batched: launch out of range");
-    DgemmBatchedArgs args = {};
-    DgemmArgs& a = args.item;
-    a.A = A ? A + l.first * stride_a : A;
-    a.B = B ? B + l.first * stride_b : B;
-    a.C = C + l.first * stride_c;
-    a.bias = bias;
-    a.M = M;
-    a.N = N;
-    a.K = K;
-    a.lda = lda;
-    a.ldb = ldb;
-    a.ldc = ldc;
-    a.accumulate = accumulate;
-    a.splits = 1;
-    a.k_per_split = ((K + BK - 1) / BK) * BK;
-    if (a.k_per_split == 0) a.k_per_split = BK;
-    a.tiles_m = plan.tiles_m;
-    a.tiles_n = plan.tiles_n;
-    args.stride_a = stride_a;
-    args.stride_b = stride_b;
-    args.stride_c = stride_c;
-    args.tiles = (int)plan.tiles;
-    args.remap = l.remap ? 1 : 0;
+    const DgemmArgs item = dgemm_args(A ? A + l.first * stride_a : A, lda, B ? B + l.first * stride_b : B, ldb, C + l.first * stride_c, ldc, bias, M, N, K,
+                                      accumulate, 1, dgemm_k_unsliced(K), plan.tiles_m, plan.tiles_n, false);
+    const DgemmBatchedArgs args = {item, stride_a, stride_b, stride_c, (int)plan.tiles, l.remap ? 1 : 0};
     rc = launch_batched(ctx, (unsigned)l.grid, args, akc, bkc, plan.vec);
     if (rc) return rc;
   }

@@ -1,4 +1,4 @@
-// The f32 contraction's planner (gemm_plan.hpp): cost models, tile choice and the route of a product.
+// The contractions' planner (gemm_plan.hpp): cost models, tile choice and the route of a product, f32 first, float64 behind it.
 #include "gemm_plan.hpp"
 
 #include <algorithm>
@@ -624,15 +624,98 @@ bool batched_runs_as_loop(const GemmProblem& item, const GemmSwitches& sw) {
   return p.grid >= item.cus && p.route != Route::Small;
 }
 
+// ---- float64 -----------------------------------------------------------------------------------------------------------
+namespace {
+
+// Tile shape by a small time model.  What a SIMD's matrix pipe delivers depends on how many waves multiply on it at the
+// same time (tools/mfma_ceiling_f64.hip: one wave 0.44 of peak, two 0.99 in a bare loop), so a launch is priced as
+// rounds of resident blocks, each round at the rate of the waves it puts on a SIMD:
+//   config        waves      blocks / CU (LDS)   relative loop efficiency
+//   128 x 128     8 (2 x 4)  2 (74 KB)           1.00
+//   128 x  64     8 (4 x 2)  2 (55 KB)           0.97
+//    64 x  64     8 (2 x 4)  4 (37 KB)           0.92
+struct DgemmCfg {
+  int bm, bn, wr, wc, cap;
+  double eff;
+};
+const DgemmCfg kDgemmCfgs[3] = {{128, 128, 2, 4, 2, 1.0}, {128, 64, 4, 2, 2, 0.97}, {64, 64, 2, 4, 4, 0.92}};
+
+double dgemm_rate(long waves_per_simd) { return waves_per_simd <= 1 ? 0.44 : waves_per_simd == 2 ? 0.80 : waves_per_simd == 3 ? 0.88 : 0.92; }
+
+double dgemm_cost(const DgemmCfg& c, long M, long N, long K, long cus, long splits) {
+  const long tiles = ((M + c.bm - 1) / c.bm) * ((N + c.bn - 1) / c.bn) * splits;
+  const double t_tile = (double)c.bm * c.bn * ((double)K / splits) / c.eff;  // matrix work of one block at the pipe's full rate
+  const long slots = cus * c.cap;
+  const long full = tiles / slots, rem = tiles % slots;
+  double t = (double)full * c.cap * t_tile / dgemm_rate(2L * c.cap);  // 8-wave blocks: two waves per SIMD each
+  if (rem > 0) {
+    const long per_cu = (rem + cus - 1) / cus;
+    t += (double)per_cu * t_tile / dgemm_rate(2L * per_cu);
+  }
+  // slabs out and back (16 bytes per element and slice at ~3 TB/s, in units of a CU's 64 multiply-adds per clock) and a second launch (~5 us)
+  if (splits > 1) t += (double)M * N * splits * 1.0 + 8.0e5;
+  return t;
+}
+
+}  // namespace
+
+DgemmPlan plan_dgemm(const DgemmProblem& p) {
+  const long M = p.M, N = p.N, K = p.K, cus = p.cus;
+  // the cheapest (config, slices): 1, 2, 4, ... 64 slices of at least 256 each; on a tie the larger tile and the fewer slices
+  int best = 0;
+  long best_splits = 1;
+  double best_t = 1e300;
+  for (int c = 0; c < 3; ++c)
+    for (long splits = 1; splits <= 64 && (splits == 1 || K / splits >= 256); splits *= 2) {
+      const double t = dgemm_cost(kDgemmCfgs[c], M, N, K, cus, splits);
+      if (t < best_t) {
+        best_t = t;
+        best = c;
+        best_splits = splits;
+      }
+    }
+  if (p.force_config >= 0) best = p.force_config % 3;
+  if (p.force_splits > 0) best_splits = p.force_splits;
+  DgemmPlan r;
+  r.config = best;
+  const DgemmCfg& cfg = kDgemmCfgs[best];
+  r.bm = cfg.bm;
+  r.bn = cfg.bn;
+  r.wr = cfg.wr;
+  r.wc = cfg.wc;
+  r.vec = dgemm_vec(p.lda, p.ldb, p.a_aligned, p.b_aligned);
+  r.k_per_split = dgemm_k_unsliced(K);
+  // slices of whole k-tiles, none of them empty; one slice is the unsliced product (no slabs, no second launch)
+  if (best_splits > 1) {
+    long per = (K + best_splits - 1) / best_splits;
+    per = ((per + BK - 1) / BK) * BK;
+    const long splits = (K + per - 1) / per;
+    if (splits > 1) {
+      r.splits = (int)splits;
+      r.k_per_split = per;
+      r.workspace_doubles = splits * M * N;
+      r.reduce = true;
+    }
+  }
+  r.tiles_m = (int)((M + r.bm - 1) / r.bm);
+  r.tiles_n = (int)((N + r.bn - 1) / r.bn);
+  r.grid_x = (long)r.tiles_m * r.tiles_n;
+  r.grid_y = r.splits;
+  r.remap = dgemm_remap(r.grid_x);
+  return r;
+}
+
 bool dgemm_batched_vec(const DgemmBatchedProblem& p) {
   const bool strides_even = p.batch <= 1 || (p.stride_a % 2 == 0 && p.stride_b % 2 == 0);
-  return p.lda % 2 == 0 && p.ldb % 2 == 0 && p.a_aligned && p.b_aligned && strides_even;
+  return dgemm_vec(p.lda, p.ldb, p.a_aligned, p.b_aligned) && strides_even;
 }
 
 // The rule: an item whose 64 x 64 tiles number at least DGEMM_LOOP_TILES_PER_CU per CU runs as a plain product — it
 // has a block for every CU by itself, the condition of the float32 rule (batched_runs_as_loop), and eg_dgemm may give it a
-// larger tile.  K does not enter: k-slices are what eg_dgemm adds for few tiles and a long K, and such items are on the
-// batched side, where the batch is what fills the chip.
+// larger tile.  K does not enter, although plan_dgemm slices many items on the loop side: a tile per CU is one block of
+// the four a CU holds, and with a long K two slices per tile put more waves on every SIMD (64 CUs: 64 x 4096 x 4096 takes
+// 64 x 64 tiles in two slices).  Such a loop uses the workspace, DgemmBatchedPlan::item.workspace_doubles of it, and its
+// items do not have the bits of the unsliced chain.
 // THE THRESHOLD HAS NOT BEEN MEASURED: tools/bench_batched_f64.py times both sides of it (its "forced" columns, at one tile
 // row less than, exactly and one more than a tile per CU), but no run of it on an MI355X exists yet, so there are no
 // figures to write beside the rule and profiles/ has no batched_dgemm.txt.  1 is the float32 rule's number, not a result.
@@ -651,7 +734,11 @@ DgemmBatchedPlan plan_dgemm_batched(const DgemmBatchedProblem& p) {
   r.loop = dgemm_batched_runs_as_loop(p.M, p.N, p.K, p.cus);
   if (p.force == 2) r.loop = true;
   if (p.force == 1) r.loop = ((p.M + T - 1) / T) * ((p.N + T - 1) / T) > BATCHED_MAX_BLOCKS;
-  if (r.loop || p.batch <= 0 || p.M <= 0 || p.N <= 0) return r;
+  if (r.loop) {
+    r.item = plan_dgemm({p.M, p.N, p.K, p.lda, p.ldb, p.a_aligned, p.b_aligned, p.cus});
+    return r;
+  }
+  if (p.batch <= 0 || p.M <= 0 || p.N <= 0) return r;
   r.vec = dgemm_batched_vec(p);
   r.tiles_m = (int)((p.M + T - 1) / T);
   r.tiles_n = (int)((p.N + T - 1) / T);
@@ -666,7 +753,7 @@ DgemmBatchedLaunch dgemm_batched_launch(const DgemmBatchedPlan& plan, long batch
   l.first = index * plan.items_per_launch;
   l.items = std::min(plan.items_per_launch, batch - l.first);
   l.grid = l.items * plan.tiles;
-  l.remap = l.grid % 8 == 0 && l.grid >= 16;
+  l.remap = dgemm_remap(l.grid);
   return l;
 }
 

@@ -110,6 +110,48 @@ GemmPlan plan_gemm_batched(const GemmProblem& item, long batch, const GemmSwitch
 // products on their own routes.  Decided from the item alone, so that an item has the same bits whatever batch it is part of.
 bool batched_runs_as_loop(const GemmProblem& item, const GemmSwitches& sw);
 
+// ---- float64: the plain product (gemm_f64_mfma.hip, dgemm_kernel) -------------------------------------------------------
+// One eg_dgemm call as the planner sees it.  Leading dimensions in doubles.
+struct DgemmProblem {
+  long M = 0, N = 0, K = 0;
+  long lda = 0, ldb = 0;
+  bool a_aligned = true, b_aligned = true;   // 16-byte aligned base pointers
+  int cus = 256;
+  int force_config = -1;   // EG_DGEMM_TILE (measurement aid), set by the caller: the config (-1: the model's) and the
+  long force_splits = 0;   // slice count before normalisation (0: the model's)
+};
+
+// Tile, k-slices and launch geometry of one product: what DgemmArgs and the launch are filled from.
+struct DgemmPlan {
+  int config = 0;            // 0: 128 x 128, 1: 128 x 64, 2: 64 x 64 (gemm_plan.cpp has the table)
+  int bm = 0, bn = 0;
+  int wr = 0, wc = 0;        // the tile's wave grid: wr x wc waves of (bm / wr) x (bn / wc)
+  bool vec = false;          // 16-byte loads (dgemm_vec)
+  int splits = 1;            // k-slices after normalisation: none of them is empty
+  long k_per_split = 0;      // a multiple of 16, at least 16
+  int tiles_m = 0, tiles_n = 0;
+  bool remap = false;        // dgemm_remap of the tiles
+  long grid_x = 0, grid_y = 0;   // tiles x splits blocks of wr * wc * 64 threads
+  long workspace_doubles = 0;    // slabs: 0 unsliced, splits * M * N sliced
+  bool reduce = false;           // the slabs are folded in slice order by a second launch
+};
+
+// 16-byte loads: a piece is two doubles that are neighbours in memory, so every row start (lda, ldb even) and both bases
+// must be 16-byte aligned.  Anything else: 8-byte loads.
+inline bool dgemm_vec(long lda, long ldb, bool a_aligned, bool b_aligned) { return lda % 2 == 0 && ldb % 2 == 0 && a_aligned && b_aligned; }
+
+// The kernels hand every XCD a contiguous range of a launch's `blocks` tiles (id -> (id & 7) * (blocks >> 3) + (id >> 3)): a
+// permutation only for a multiple of 8, and worth it from two tiles per XCD on.
+inline bool dgemm_remap(long blocks) { return blocks % 8 == 0 && blocks >= 16; }
+
+// k range of a block of an unsliced product: the whole K in 16-deep k-tiles, at least one (K = 0 still stores C).
+inline long dgemm_k_unsliced(long K) {
+  const long per = ((K + BK - 1) / BK) * BK;
+  return per == 0 ? BK : per;
+}
+
+DgemmPlan plan_dgemm(const DgemmProblem& p);
+
 // ---- float64: `batch` products of one shape (gemm_f64_mfma.hip, dgemm_batched_kernel) ---------------------------------
 // Blocks of one batched launch, float32 and float64: grid x block threads stays below 2^32 and the block id an int.
 constexpr long BATCHED_MAX_BLOCKS = 1L << 22;
@@ -125,7 +167,10 @@ struct DgemmBatchedProblem {
 };
 
 struct DgemmBatchedPlan {
-  bool loop = false;   // every item is a plain float64 product on its own route; the fields below are then unused
+  bool loop = false;   // every item is a plain float64 product on its own route; the fields behind `item` are then unused
+  // loop: plan_dgemm of item 0 without EG_DGEMM_TILE.  The loop plans every item again with its own base alignment, which
+  // changes `vec` alone: item.workspace_doubles — nonzero for a sliced item — is what every item of the loop takes.
+  DgemmPlan item;
   bool vec = false;    // 16-byte loads (dgemm_batched_vec)
   int tiles_m = 0, tiles_n = 0;
   long tiles = 0;             // blocks per item
@@ -133,16 +178,14 @@ struct DgemmBatchedPlan {
   long launches = 0;
 };
 
-// Launch `index` of a plan: items [first, first + items), grid = items x tiles blocks.  remap: the block count is a
-// multiple of 8 and at least 16, so the kernel hands every XCD a contiguous range of the launch's blocks.
+// Launch `index` of a plan: items [first, first + items), grid = items x tiles blocks.  remap: dgemm_remap of the grid.
 struct DgemmBatchedLaunch {
   long first = 0, items = 0, grid = 0;
   bool remap = false;
 };
 
-// 16-byte loads: a piece is two doubles that are neighbours in memory, at an even offset from its item's base, so every
-// row start (lda, ldb even), item 0 (both bases 16-byte aligned) and every further item (stride_a, stride_b even wherever
-// the batch has a second item; a shared operand's stride of 0 is even) must be 16-byte aligned.  Anything else: 8-byte loads.
+// 16-byte loads: dgemm_vec of item 0, and every further item 16-byte aligned as well (stride_a, stride_b even wherever the
+// batch has a second item; a shared operand's stride of 0 is even).  Anything else: 8-byte loads.
 bool dgemm_batched_vec(const DgemmBatchedProblem& p);
 
 // Does one item fill the chip by itself?  Then the batch runs as a loop of plain float64 products, each on its own route

@@ -1,5 +1,5 @@
 """The cases of tests/test_gpu_gemm_views.py (eg_sgemm and eg_dgemm called on strided views) and of
-tests/test_gemm_view_plan_cpu.py (which routes of kernels/gemm_plan.cpp those cases reach).  No GPU, no HIP.
+tests/test_gemm_view_plan_cpu.py and tests/test_dgemm_view_plan_cpu.py (which routes of kernels/gemm_plan.cpp those cases reach).  No GPU, no HIP.
 
 A ViewCase is one call with its host buffers.  The contract of include/exprgrad_hip.h is lda >= K, ldb >= N, ldc >= N and
 any base pointer, so every buffer here is a view into a larger allocation:
@@ -62,6 +62,13 @@ class ViewCase:
         return "exact %d %d %d %d %d %d %d %d %d %d %d %d 0 %s" % (
             M, N, K, self.ta, self.tb, self.lda, self.ldb, self.ldc, al(self.off_a), al(self.off_b), al(self.off_c),
             (al(self.off_bias) if self.bias else 0), self.switches)
+
+    # ---- the float64 planner driver's case (tests/test_dgemm_plan_cpu.py, dgemm_plans): offsets are in doubles ----
+    def dgemm_driver_case(self, cus=256):
+        assert self.dtype == np.float64
+        M, N, K = self.dims
+        return dict(M=M, N=N, K=K, lda=self.lda, ldb=self.ldb, a=int(self.off_a % 2 == 0), b=int(self.off_b % 2 == 0), cus=cus,
+                    tile=self.env.get("EG_DGEMM_TILE", "-"))
 
     def tight(self):
         """The same call on the same values with tight leading dimensions and aligned bases."""
@@ -256,9 +263,11 @@ def f32_table():
 
 
 # ---- the float64 table -----------------------------------------------------------------------------------------------------
-# eg_dgemm has no planner on the CPU: EG_DGEMM_TILE=<config>,<slices> (a measurement aid) picks the tile (0: 128 x 128,
-# 1: 128 x 64, 2: 64 x 64) and the number of k-slices.  16-byte loads need even lda and ldb and aligned bases, whatever the
-# extents: with pad 2 and an odd K or M the second double of a row's last pair is the NaN behind the row.
+# Left alone, plan_dgemm (kernels/gemm_plan.cpp) gives every shape here one tile and one slice count, so EG_DGEMM_TILE=
+# <config>,<slices> (a measurement aid) takes the table through every tile (0: 128 x 128, 1: 128 x 64, 2: 64 x 64), unsliced
+# and sliced; tests/test_dgemm_view_plan_cpu.py asserts through the planner that each case ends where its name says.
+# 16-byte loads need even lda and ldb and aligned bases, whatever the extents: with pad 2 and an odd K or M the second
+# double of a row's last pair is the NaN behind the row.
 F64_SHAPES = [(65, 63, 17), (130, 70, 1027), (257, 129, 1000)]     # odd extents; K = 1027: four slices of at least 256
 F64_KINDS = {
     "even": ((2, 2, 2), (0, 0, 0)),       # 16-byte loads

@@ -132,3 +132,35 @@ def test_loop_rule_reads_the_item_alone(driver, cus):
 def test_a_looping_plan_has_no_launches(driver):
     (plan, launches), = plans(driver, [call(8, 2048, 2048, 256)])
     assert plan["loop"] == 1 and plan["launches"] == 0 and launches == []
+
+
+def test_a_looping_plan_reports_the_workspace_of_its_items(driver):
+    """An item with a tile per CU runs as eg_dgemm, and eg_dgemm's model slices many such items (the other block slots of
+    a CU are free and K is long): the loop then writes slabs.  The plan carries the plain plan of an item, so a caller can
+    see it; the one-launch side never takes workspace."""
+    cases = [call(3, 64, 4096, 4096, cus=64), call(3, 512, 512, 65536, cus=64), call(3, 4096, 4096, 4096, cus=256),
+             call(1000, 130, 70, 4096, cus=64), call(8, 64, 2048, 65536, cus=256)]
+    sliced, sliced_long, unsliced, launch, launch_long = plans(driver, cases)
+    assert sliced[0]["loop"] == 1 and (sliced[0]["item_config"], sliced[0]["item_splits"]) == (2, 2)
+    assert sliced[0]["item_workspace_doubles"] == 2 * 64 * 4096 > 0
+    assert sliced_long[0]["loop"] == 1 and (sliced_long[0]["item_config"], sliced_long[0]["item_splits"]) == (0, 8)
+    assert sliced_long[0]["item_workspace_doubles"] == 8 * 512 * 512
+    assert unsliced[0]["loop"] == 1 and unsliced[0]["item_splits"] == 1 and unsliced[0]["item_workspace_doubles"] == 0
+    for plan, launches in (launch, launch_long):
+        assert plan["loop"] == 0 and plan["launches"] == len(launches) == 1 and plan["item_workspace_doubles"] == 0
+
+
+def test_vec_of_a_batch_of_one_is_the_plain_rule(driver):
+    """dgemm_batched_vec is dgemm_vec plus the parity of the strides, which a batch of one never uses."""
+    cases = [call(batch, 33, 20, 18, lda=lda, ldb=ldb, stride_a=33 * lda + sa, stride_b=18 * ldb + sb, a_aligned=a, b_aligned=b)
+             for batch in (1, 2) for lda in (18, 19) for ldb in (20, 21) for a in (0, 1) for b in (0, 1) for sa in (0, 1) for sb in (0, 1)]
+    seen = set()
+    for c, (plan, _) in zip(cases, plans(driver, cases)):
+        batch, lda, ldb, stride_a, stride_b, a, b = c[0], c[4], c[5], c[6], c[7], c[8], c[9]
+        assert plan["loop"] == 0 and plan["dgemm_vec"] == int(lda % 2 == 0 and ldb % 2 == 0 and a and b), c
+        if batch == 1:
+            assert plan["vec"] == plan["dgemm_vec"], c
+        else:
+            assert plan["vec"] == int(plan["dgemm_vec"] and stride_a % 2 == 0 and stride_b % 2 == 0), c
+        seen.add((batch, plan["vec"], plan["dgemm_vec"]))
+    assert seen == {(1, 0, 0), (1, 1, 1), (2, 0, 0), (2, 1, 1), (2, 0, 1)}
