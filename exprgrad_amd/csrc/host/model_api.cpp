@@ -231,6 +231,19 @@ EG_CATCH_ALL
 
 const char* eg_model_plan_text(eg_model* m) { return m ? m->plan_text.c_str() : ""; }
 
+// The emitter route of a generated launch, as the plan decided it (codegen.cpp): scatter or serial / split reduction, four
+// elements per thread, and which of the two bodies the launch-uniform branch takes.  Appended to the end of the launch line.
+static std::string route_words(const Launch& L) {
+  const GenericSource& src = L.generic->src;
+  std::string s = " |";
+  if (src.scatter) s += " scatter";
+  else if (!src.red.empty()) s += " reduce";
+  if (L.vec_ok) s += " vec4";
+  for (size_t i = 0; i < src.slots.size() && i < L.params.size(); ++i)
+    if (src.slots[i].kind == Slot::Narrow) s += L.params[i] ? " narrow" : " wide";
+  return s == " |" ? std::string() : s;
+}
+
 const char* eg_model_launch_text(eg_model* m, const char* target) {
   if (!m || !target) return "";
   auto it = m->targets.find(target);
@@ -275,8 +288,12 @@ const char* eg_model_launch_text(eg_model* m, const char* target) {
         if (L.conv_direct64) os << " | " << (L.conv_direct64 == 1 ? "convolution" : L.conv_direct64 == 2 ? "convolution's image gradient" : "convolution's filter gradient")
                                  << ": the float64 matrix-core kernel (eg_conv_band_f64_* / eg_conv_mfma64_*) when the shape suits it";
         if (L.consumer >= 0) os << " (with its consumer, kernel " << L.consumer << ")";
+        os << route_words(L);
         break;
-      case StepKind::GenericB: os << "generated(split-reduce) kernel " << L.lowered << " -> t" << L.c_tensor; break;
+      case StepKind::GenericB:
+        os << "generated(split-reduce) kernel " << L.lowered << " -> t" << L.c_tensor << route_words(L) << " tx=" << L.generic->src.tx
+           << " chunks=" << L.partial_rows;
+        break;
       case StepKind::RowFused: {
         const PlanRowGroup& pg = *plan.row_groups[L.row_group];
         os << "row-fused " << pg.g.kernel_index.size() << " kernels";
