@@ -296,8 +296,14 @@ const char* eg_model_launch_text(eg_model* m, const char* target) {
         break;
       case StepKind::RowFused: {
         const PlanRowGroup& pg = *plan.row_groups[L.row_group];
-        os << "row-fused " << pg.g.kernel_index.size() << " kernels";
-        if (pg.g.in_kernel_finalize) os << " | partial rows folded by the last block to arrive";
+        os << "row-fused " << pg.g.kernel_index.size() << " kernels, grid " << pg.nblocks << " x 256";
+        // how the batch totals reach their tensors: the generator's own decisions (RowGroup), not read from its text
+        if (pg.g.red_total <= 0) os << " | no sums";
+        else if (pg.g.single_block) os << " | direct";
+        else if (pg.g.in_kernel_finalize) os << " | partial rows folded by the last block to arrive";
+        else os << " | row_finalize";
+        os << " sums=" << pg.g.red_total;
+        if (pg.g.unrolled_trips > 0) os << " | unrolled trips=" << pg.g.unrolled_trips;
         if (L.tail_launch >= 0) os << " | which goes on with launch " << L.tail_launch << " when a range holds both";
         break;
       }
@@ -308,6 +314,12 @@ const char* eg_model_launch_text(eg_model* m, const char* target) {
           const int wt = ts.target->all[pg.g.kernel_index[ki]].write.tensor;
           const std::string& nm = m->prog.tensors[wt].name;
           os << (ki ? ", " : "") << (nm.empty() || nm == "-" ? "t" + std::to_string(wt) : nm);
+          // the member's kind as analyse_wide_kernel decided it (generate_wide_group branches on the same fields)
+          const eg::kd::WideKernelInfo& wi = pg.g.wide[ki];
+          os << ":" << (wi.seed ? "seed" : wi.kind == eg::kd::WideKernelInfo::Map ? "map" : wi.kind == eg::kd::WideKernelInfo::RowRed ? "rowsum"
+                        : wi.kind == eg::kd::WideKernelInfo::ColRed ? "colsum" : "total");
+          if (wi.raw) os << " raw";
+          else if (!wi.seed && wi.col_loop < 0) os << " nocol";
         }
         os << "), one wave per sample, grid " << pg.nblocks << " x 256";
         if (pg.g.red_total > 0) os << " | " << pg.red_tensors.size() << " batch sums folded by row_finalize";
@@ -317,6 +329,29 @@ const char* eg_model_launch_text(eg_model* m, const char* target) {
         const PlanSampleGroup& sg = *plan.sample_group;
         os << "sample-fused " << sg.g.kernel_index.size() << " kernels, one block per sample (" << sg.g.B << " blocks)";
         if (sg.g.slab_floats > 0) os << " | " << sg.sum_tensors.size() << " batch sums " << (L.fold_launch >= 0 ? "folded by launch " + std::to_string(L.fold_launch) + " (one slab pass when a range ends between them)" : std::string("folded by one slab pass"));
+        // the generator's record (SampleGroup::routes), one entry per member in order
+        os << " | threads=" << sg.g.threads << " " << (sg.g.narrow ? "narrow" : "wide") << " lds=" << sg.g.lds.size() << " zeroed=" << sg.g.lds_zero.size()
+           << " staged=" << sg.g.staged.size() << " barriers=" << sg.g.barriers_kept << "/" << sg.g.routes.size() << " |";
+        for (size_t ri = 0; ri < sg.g.routes.size(); ++ri) {
+          const eg::kd::SampleMemberRoute& r = sg.g.routes[ri];
+          using K = eg::kd::SampleMemberRoute;
+          os << (ri ? "; " : " ") << ri << ":";
+          switch (r.kind) {
+            case K::Seed: os << "seed"; break;
+            case K::Raw: os << "raw"; break;
+            case K::Items: os << "items"; break;
+            case K::Scatter: os << "scatter"; break;
+            case K::Split: os << "split T=" << r.T; break;
+            case K::Gather: os << "gather"; break;
+            case K::Conv: os << (r.conv_role == 1 ? "conv-forward" : r.conv_role == 2 ? "conv-grad-filter" : "conv-grad-image"); break;
+          }
+          if (r.kind == K::Split && r.ragged > 0) os << " ragged=" << r.ragged;
+          if (r.R > 1) os << " R=" << r.R;
+          if (r.trips >= 0) os << " trips=" << r.trips << (r.ragged_trip ? " +ragged" : "");
+          if (r.rolled) os << " rolled";
+          if (r.slab) os << (r.slab == 1 ? " slab" : " slab+");
+          if (r.lds) os << " lds";
+        }
         break;
       }
       case StepKind::SmallFused: {
@@ -595,6 +630,18 @@ static int tensor_shape(eg_model* m, TargetState& ts, int tid, int* rank, int64_
   return EG_OK;
 }
 
+// A row or wide group keeps a member's result in registers when nothing behind the group touches it (RowGroupTensor::store
+// == false), and the seed in every thread (SmallLocal): the tensor's storage then holds whatever was there before.
+static bool kept_in_registers(const Plan& plan, int tid) {
+  for (auto& pg : plan.row_groups) {
+    auto it = pg->g.tensors.find(tid);
+    if (it == pg->g.tensors.end()) continue;
+    const RowGroupTensor& gt = it->second;
+    if ((gt.role == RowGroupTensor::RowLocal && !gt.store) || gt.role == RowGroupTensor::SmallLocal) return true;
+  }
+  return false;
+}
+
 static int read_tensor(eg_model* m, TargetState& ts, int tid, void* host, int64_t count, bool f64 = false) {
   EG_REQUIRE(ts.last && host, EG_ERR_INVALID, "nothing to read");
   EG_REQUIRE_SCALAR(m, f64, f64 ? "eg_model_read_*_f64" : "eg_model_read_*");
@@ -609,7 +656,11 @@ static int read_tensor(eg_model* m, TargetState& ts, int tid, void* host, int64_
              "tensor %d lived in the LDS of a sample group's blocks in the last run's plan: its values were never stored "
              "(eg_model_keep_values(model, 1) makes the plans keep values)", tid);
   float* p = tensor_ptr(m, ts, *ts.last, tid);
+  // (no storage at all: the tensor of a producer that was inlined into its readers when the model was compiled)
   EG_REQUIRE(p, EG_ERR_INVALID, "tensor %d was not materialised by the last run", tid);
+  EG_REQUIRE(!kept_in_registers(*ts.last, tid), EG_ERR_INVALID,
+             "tensor %d lived in the registers of a row group's threads in the last run's plan: its values were never stored "
+             "(eg_model_keep_values(model, 1) makes the plans store the rows of such tensors)", tid);
   return eg::copy_d2h(m->ctx, host, p, (size_t)n * sizeof(float) * m->esz);
 }
 
@@ -685,7 +736,12 @@ int eg_model_tensor_ptr(eg_model* m, const char* target, int tensor_id, float** 
   EG_REQUIRE(!(ts->last->sample_group && ts->last->sample_group->g.lds.count(tensor_id)), EG_ERR_INVALID,
              "tensor %d lived in the LDS of a sample group's blocks in the last run's plan: its values were never stored "
              "(eg_model_keep_values(model, 1) makes the plans keep values)", tensor_id);
-  if (device_ptr) *device_ptr = tensor_ptr(m, *ts, *ts->last, tensor_id);
+  float* const p = tensor_ptr(m, *ts, *ts->last, tensor_id);
+  EG_REQUIRE(p || prod(s->second) == 0, EG_ERR_INVALID, "tensor %d was not materialised by the last run", tensor_id);
+  EG_REQUIRE(!kept_in_registers(*ts->last, tensor_id), EG_ERR_INVALID,
+             "tensor %d lived in the registers of a row group's threads in the last run's plan: its values were never stored "
+             "(eg_model_keep_values(model, 1) makes the plans store the rows of such tensors)", tensor_id);
+  if (device_ptr) *device_ptr = p;
   if (count) *count = prod(s->second);
   return EG_OK;
 }

@@ -569,7 +569,8 @@ static int form_wide_groups(eg_model* m, TargetState& ts, Plan& plan, const std:
       if (gt.role == RowGroupTensor::RowLocal) {
         gt.load_first = written_outside_before(kv.first);
         // (the readers of an inlined producer's tensor recompute it: it is stored nowhere)
-        gt.store = used_after(kv.first) && !inlined.count(kv.first);
+        // (eg_model_keep_values: the rows of every member's result are stored, so that eg_model_read_tensor finds them)
+        gt.store = (used_after(kv.first) || m->keep_values) && !inlined.count(kv.first);
       } else if (gt.role == RowGroupTensor::Reduction) {
         const TK kind = m->prog.tensors[kv.first].kind;
         gt.accumulate = kind != TK::Result || written_outside_before(kv.first);
@@ -770,6 +771,11 @@ int form_row_groups(eg_model* m, TargetState& ts, Plan& plan, const std::vector<
       }
       return false;
     };
+    auto inlined_tensor = [&](int tensor) {
+      for (int s = 0; s < n; ++s)
+        if (ts.lowered[s].inlined && t.all[t.live[s]].write.tensor == tensor) return true;
+      return false;
+    };
     bool leaks = false;  // a thread-local small tensor somebody outside the group wants
     for (auto& kv : g.tensors)
       if (kv.second.role == RowGroupTensor::SmallLocal && (used_after(kv.first) || written_outside_before(kv.first)))
@@ -783,7 +789,8 @@ int form_row_groups(eg_model* m, TargetState& ts, Plan& plan, const std::vector<
       RowGroupTensor& gt = kv.second;
       if (gt.role == RowGroupTensor::RowLocal) {
         gt.load_first = written_outside_before(kv.first);
-        gt.store = used_after(kv.first);
+        // (eg_model_keep_values: every member's rows are stored; an inlined producer's tensor has no storage)
+        gt.store = used_after(kv.first) || (m->keep_values && !inlined_tensor(kv.first));
       } else if (gt.role == RowGroupTensor::Reduction) {
         const TK kind = m->prog.tensors[kv.first].kind;
         gt.accumulate = kind != TK::Result || written_outside_before(kv.first);

@@ -109,6 +109,9 @@ struct RowGroup {
   // fully unrolled: the loads of all of a thread's samples are in flight together instead of one memory round trip per sample
   // (four in a row at the XOR step).  The generic loop stays in the kernel for any other grid / B.
   long grid_blocks = 0;
+  // What generate_row_group emitted, for eg_model_launch_text: the literal trip count of the unrolled sample loop (0: the
+  // generic strided loop, or one sample per thread).
+  long unrolled_trips = 0;
   std::vector<int> tail_kernels;   // indices into target.all, in execution order
   std::vector<int> tail_ptr_args;  // tensor ids of the tail kernels, in pointer-argument order
   // Wide groups ("one wave per sample", below): W > 0, and `wide` holds the members' analysis instead of `infos`.
@@ -200,6 +203,20 @@ struct SampleKernelInfo {
 
 SampleKernelInfo analyse_sample_kernel(const Program& prog, const Kernel& k, const KernelInfo& info, const Shapes& shapes, long B);
 
+// What generate_sample_group decided for one member, recorded while the member is emitted (eg_model_launch_text prints it;
+// nothing reads it back into the generated text).
+struct SampleMemberRoute {
+  enum Kind { Seed, Raw, Items, Scatter, Split, Gather, Conv } kind = Items;
+  int conv_role = 0;        // Conv: SampleKernelInfo::conv_role
+  long T = 1, ragged = 0;   // Split: lanes per item; what the outermost reduction extent leaves over T (the guarded last trip)
+  long R = 1;               // register blocking (1: none)
+  long trips = -1;          // item loop: whole trips of the block over the items (-1: the member has no item loop)
+  bool ragged_trip = false; // item loop: a last trip that not every thread takes
+  bool rolled = false;      // the item loop (or a split's walk over its outer reduction iterator) has no literal trip count
+  int slab = 0;             // 1: first contribution of the block to a batch sum (a store), 2: a later one (an addition)
+  bool lds = false;         // the result lives in the block's LDS
+};
+
 struct SampleGroup {
   std::vector<int> kernel_index;  // indices into target.all, in execution order
   std::vector<SampleKernelInfo> infos;
@@ -219,6 +236,10 @@ struct SampleGroup {
   // kernel's start: a member that walked them with dependent loads paid an L2 round trip per iteration (the 400-term dense
   // layer of the fashion_mnist network: eight of them in a row).  tensor id -> floats.
   std::map<int, long> staged;
+  // Filled in by generate_sample_group: one record per member, 32-bit index arithmetic, barriers behind members that stayed.
+  std::vector<SampleMemberRoute> routes;
+  bool narrow = false;
+  int barriers_kept = 0;
 };
 
 // Arguments of the generated kernel: (float* slab, float* t<ids>..., float grad_scale, long epoch); grid = B blocks of `threads`.

@@ -48,6 +48,7 @@ struct SampleMember {
   bool reads_zeros4 = false;   // gathers read the four zeros the prologue keeps in LDS
   bool needs_dummy = false;    // row blocks store the lanes outside their tensor to a slot per thread of `dummy_`
   bool barrier_after = true;   // cleared by the barrier elision when the next member is independent of this one
+  SampleMemberRoute route;     // the decisions taken while `text` was written (SampleGroup::routes)
 };
 
 struct SampleCtx {

@@ -222,6 +222,7 @@ int generate_row_group(const std::vector<Kernel>& all, const std::vector<KernelI
   // row group with a tail: 64 blocks — fewer arrivals at the ticket counter, fewer partial rows for the last block);
   // with ceil(B / 256) blocks the loop runs once and every value is what the one-sample-per-thread form computes.
   const bool strided = g.in_kernel_finalize;
+  g.unrolled_trips = 0;
   if (!strided) c += "  const long y = (long)blockIdx.x * 256 + threadIdx.x;\n  const bool active = y < B;\n";
   std::string init;  // per-sample state: (re)initialised for every sample
   for (auto& kv : g.tensors) {
@@ -255,6 +256,7 @@ int generate_row_group(const std::vector<Kernel>& all, const std::vector<KernelI
     c += "  };\n";
     const long per_trip = g.grid_blocks * 256;
     const long trips = per_trip > 0 && g.B % per_trip == 0 ? g.B / per_trip : 0;
+    g.unrolled_trips = trips >= 2 && trips <= 8 ? trips : 0;
     if (trips >= 2 && trips <= 8) {
       // the launch this kernel was generated for: every thread has exactly `trips` samples, no bounds test between them
       c += "  if (gridDim.x == " + std::to_string(g.grid_blocks) + " && B == " + std::to_string(g.B) + "L) {\n";

@@ -151,6 +151,8 @@ struct LoopNest : MemberEmitter {
       w = literal_element(k.write, shapes, "t" + std::to_string(k.write.tensor), local(k.write.tensor));
     }
     for (int l : red) rtotal *= std::max(0L, info.bounds[l].second - info.bounds[l].first);
+    m.route.slab = si.reduced ? (plain ? 1 : 2) : 0;
+    m.route.lds = !si.reduced && local(k.write.tensor) > 0;
     return EG_OK;
   }
 
@@ -196,6 +198,7 @@ struct LoopNest : MemberEmitter {
       }
     }
     items = total / R;
+    m.route.R = R;
     RS = std::to_string(R);
     breg = blk >= 0 ? "r" + std::to_string(k.loops[indep[blk]].reg) : "";
     zero_acc = "      float acc[" + RS + "];\n      _Pragma(\"unroll\") for (int u = 0; u < " + RS + "; ++u) acc[u] = 0.0f;\n";
@@ -299,6 +302,8 @@ struct LoopNest : MemberEmitter {
     const std::vector<long>&gi_s = shapes.at(si.g_img), &go_s = shapes.at(si.g_out), &fl_s = shapes.at(si.g_flt);
     const long H = gi_s[1], W = gi_s[2], C = gi_s[3], Ho = go_s[1], Wo = go_s[2], F = go_s[3], FH = fl_s[1], FW = fl_s[2];
     auto L = [](long v) { return std::to_string(v) + "L"; };
+    m.route.kind = SampleMemberRoute::Gather;
+    m.route.lds = local(si.g_img) > 0;
     const std::string img = "t" + std::to_string(si.g_img), out = "t" + std::to_string(si.g_out), flt = "t" + std::to_string(si.g_flt);
     c += "    for (long idx = threadIdx.x; idx < " + L(H * W * C) + "; idx += " + NT + ") {\n";
     c += "      const long ch = idx % " + L(C) + ", X = (idx / " + L(C) + ") % " + L(W) + ", Y = idx / " + L(C * W) + ";\n";
@@ -322,6 +327,10 @@ struct LoopNest : MemberEmitter {
       const std::string r = "r" + std::to_string(k.loops[l].reg);
       // literal trip count for the whole trips (their loads go out together), the ragged last one guarded
       const long ext0 = info.bounds[l].second - info.bounds[l].first, whole = ext0 / T, ragged = ext0 % T;
+      m.route.kind = SampleMemberRoute::Split;
+      m.route.T = T;
+      m.route.ragged = ragged;
+      m.route.rolled = whole > 16;
       std::string body = inner_loops(1, "          ") + accumulate("          ");
       for (size_t i = 1; i < red.size(); ++i) body += "          }\n";
       if (whole <= 16) {
@@ -367,6 +376,10 @@ struct LoopNest : MemberEmitter {
     // compiler does not move loads across: the 784-float copy of a sample's image was two dependent trips to memory).  A
     // scatter adds onto elements other trips may touch: it keeps the rolled loop.
     const long whole_trips = items / g.threads, ragged_items = items % g.threads;
+    m.route.kind = si.seed ? SampleMemberRoute::Seed : scatter ? SampleMemberRoute::Scatter : si.raw ? SampleMemberRoute::Raw : SampleMemberRoute::Items;
+    m.route.trips = whole_trips;
+    m.route.ragged_trip = ragged_items > 0;
+    m.route.rolled = !(!scatter && whole_trips <= 12 && rtotal * whole_trips <= 256);
     if (!scatter && whole_trips <= 12 && rtotal * whole_trips <= 256) {
       if (ragged_items > 0)
         c += "    {\n      const bool ok_ = threadIdx.x < " + std::to_string(ragged_items) + ";\n      const long idx = ok_ ? threadIdx.x + " +
@@ -505,6 +518,10 @@ int generate_sample_group(const std::vector<Kernel>& all, const std::vector<Kern
     m.text = "  {  // kernel " + std::to_string(gi) + ": " + to_text(all[g.kernel_index[gi]]).substr(0, 100) + "\n";
     const MemberEmitter e{cx, gi, m};
     if (e.si.conv_role != 0) {
+      m.route.kind = SampleMemberRoute::Conv;
+      m.route.conv_role = e.si.conv_role;
+      m.route.slab = e.si.reduced ? (cx.slab_seen.count(e.k.write.tensor) ? 2 : 1) : 0;
+      m.route.lds = !e.si.reduced && e.local(e.k.write.tensor) > 0;
       emit_conv_member(e);
     } else if (LoopNest nest(e); e.si.gather) {
       nest.emit_gather();
@@ -531,7 +548,14 @@ int generate_sample_group(const std::vector<Kernel>& all, const std::vector<Kern
   if (scratch_floats > 0) head = "  __shared__ float scratch[" + std::to_string(scratch_floats) + "];\n" + head;
   if (eg::sw::raw("EG_SAMPLE_KEEP_BARRIERS") == nullptr) elide_barriers(cx, prologue_barrier, members);
   const std::string row = g.slab_floats > 0 ? "  float* const row = slab + n * " + std::to_string(g.slab_floats) + "L;\n" : "";
-  g.source = sig + " {\n" + assemble(cx, head, prologue_barrier || zeros4_barrier, row, members, index_fits_32_bits(cx, touched)) + "}\n";
+  g.narrow = index_fits_32_bits(cx, touched);
+  g.routes.clear();
+  g.barriers_kept = 0;
+  for (auto& mem : members) {
+    g.routes.push_back(mem.route);
+    if (mem.barrier_after) ++g.barriers_kept;
+  }
+  g.source = sig + " {\n" + assemble(cx, head, prologue_barrier || zeros4_barrier, row, members, g.narrow) + "}\n";
   return EG_OK;
 }
 

@@ -356,7 +356,8 @@ int eg_model_tensor_shape(eg_model* model, const char* target, int tensor_id, in
 int eg_model_read_tensor(eg_model* model, const char* target, int tensor_id, float* host,
                          int64_t count);
 /* (eg_model_read_tensor and eg_model_tensor_ptr refuse — EG_ERR_INVALID — a tensor whose values the last run's plan
- * never stored: predicate bits, tensors that lived in the LDS of a sample group; see eg_model_keep_values.) */
+ * never stored: predicate bits, tensors that lived in the LDS of a sample group or in the registers of a row group's
+ * threads, the tensor of a producer that was inlined into its readers; see eg_model_keep_values.) */
 int eg_model_tensor_ptr(eg_model* model, const char* target, int tensor_id, float** device_ptr,
                         int64_t* count);
 /* Intermediates are an implementation matter of a plan: a tensor every reader of which is fused away may never exist,
