@@ -118,13 +118,13 @@ int launch_conv(eg_ctx* ctx, const GemmArgs& args, bool vec) {
   dim3 grid((unsigned)(args.tiles_m * args.tiles_n), 1, 1);
   // channels a multiple of the k-tile: interior tiles gather with LDS-DMA (a k-tile lies inside one tap)
   if (vec && args.cC % CBK == 0)
-    hipLaunchKernelGGL((gemm_f32_mfma_kernel<BM, BN, CBK, WM, WN, MINB, true, true, 4, true, true, 0, true>), grid,
+    hipLaunchKernelGGL((gemm_f32_mfma_kernel<BM, BN, CBK, WM, WN, MINB, true, true, 4, true, 1, 0, true>), grid,
                        dim3(NT), 0, ctx->stream, args);
   else if (vec)
-    hipLaunchKernelGGL((gemm_f32_mfma_kernel<BM, BN, CBK, WM, WN, MINB, true, true, 4, true, true>), grid, dim3(NT), 0,
+    hipLaunchKernelGGL((gemm_f32_mfma_kernel<BM, BN, CBK, WM, WN, MINB, true, true, 4, true, 1>), grid, dim3(NT), 0,
                        ctx->stream, args);
   else
-    hipLaunchKernelGGL((gemm_f32_mfma_kernel<BM, BN, CBK, WM, WN, MINB, true, true, 1, true, true>), grid, dim3(NT), 0,
+    hipLaunchKernelGGL((gemm_f32_mfma_kernel<BM, BN, CBK, WM, WN, MINB, true, true, 1, true, 1>), grid, dim3(NT), 0,
                        ctx->stream, args);
   EG_HIP_CHECK(hipGetLastError());
   return EG_OK;

@@ -1,25 +1,36 @@
-// f32 contraction kernel template for CDNA4 (gfx950) matrix cores — see gemm_f32_mfma.hip for the
-// role of this kernel in the backend.  Kept in a header so the tuning harness
-// (tools/gemm_tune.hip) instantiates exactly the code the library ships.
+// The f32 tile kernels for CDNA4 (gfx950) matrix cores: every f32 matrix product, convolution as GEMM, batched product
+// (gemm_batched.hip) and run-time-compiled fused contraction (gemm_fused.hpp) goes through this text; gemm_f32_mfma.hip
+// says what role they play in the backend.  v_mfma_f32_32x32x2_f32 throughout: exact f32 products and accumulation (an
+// fmaf chain), 64 cycles per instruction per SIMD = the 157 TFLOP/s f32 matrix peak; no reduced-precision path exists or
+// is wanted here (parity is 1e-5 relative against the reference's f32 CPU path).  A block owns a BM x BN tile, its
+// (BM / WM) * (BN / WN) waves a WM x WN sub-tile of 32x32 accumulator blocks each, in registers for the whole k loop.
 //
-// Design (gfx950):
-//   * v_mfma_f32_32x32x2_f32: exact f32 products and accumulation (an fmaf chain), 64 cycles per
-//     instruction per SIMD = the 157 TFLOP/s f32 matrix peak.  No reduced-precision path exists
-//     or is wanted (parity is 1e-5 relative against the reference's f32 CPU path).
-//   * block tile BM x BN x BK, (BM/WM)*(BN/WN) waves; every wave owns a WM x WN sub-tile made of
-//     32x32 MFMA blocks, accumulators stay in registers for the whole K loop (the reference
-//     re-reads and re-writes C once per k: tests/cache/matmul_basic.ir).
-//   * both operand tiles are staged in LDS as [k][m|n] so that an MFMA operand fetch is a
-//     ds_read of 32 consecutive dwords per half-wave (bank-conflict free).  An operand whose
-//     global layout is k-contiguous (A of NN/NT, B of NT) is transposed on the way in: coalesced
-//     16-byte global loads along k, four ds_write_b32; the row stride is chosen so those writes
-//     spread over all 32 banks.
-//   * double-buffered LDS + register prefetch of the next k-tile: one barrier per k-tile; operand
-//     fragments of k-step kk+1 are fetched before the MFMAs of k-step kk issue.
-//   * XCD-aware tile order: consecutive block ids land on different XCDs (id % 8), so ids are
-//     remapped to give each XCD's private L2 a contiguous, squarish patch of output tiles.
-//   * split-K (grid.z) with a deterministic second pass for contractions whose output is small
-//     and whose K is the batch (the weight gradients): no float atomics, fixed summation order.
+// The parts, in file order:
+//   GemmArgs, EpiNone / epi_apply   one argument struct for every kernel; the epilogue functor a generated kernel replaces
+//   TileLoader, xcd_remap, tile_origin, Interleaved / sub_index, Geometry
+//   shared parts                    acc_row, zero_acc, live_blocks, read_fragments, zero_k_tail, park_block_row,
+//                                   fold_pred_nibbles: one copy each, used by the loops and stores here and in gemm_f32_pair.hpp
+//   the three k loops               gemm_mainloop: operands staged through registers into double-buffered [k][m|n] LDS
+//                                   tiles — unaligned operands and ragged im2col tiles only;
+//                                   gemm_mainloop_dma (DmaLoader, dma_publish_barrier): tiles written to LDS by the memory
+//                                   pipeline, unclamped on whole tiles, clamped (rows / columns, and k with a zeroed tail) on
+//                                   ragged ones, odd waves one k-group late — every aligned product;
+//                                   gemm_mainloop_dma_x: that loop plus a strip of extra rows (GemmArgs::x_rows)
+//   the block body                  trace_stamp, decode_work, stage_row_product_weights, run_k_loop (who takes which loop),
+//                                   RowProduct, then gemm_block_at: decode, zero, (W2), k loop, store — through LDS as whole
+//                                   rows (wide store) or lane by lane; gemm_block; gemm_f32_mfma_kernel
+//   gemm_streamk_kernel / _fixup    persistent blocks for 64 x 64 tiles that load the CUs unevenly
+//   gemm_narrow_k_block             K <= 16 with a generated epilogue: a streaming kernel on the vector ALUs
+//   gemm_splitk_reduce_kernel, gemm_tail_reduce_kernel   the deterministic second passes (no float atomics, fixed order)
+//
+// Work items: the grid is one-dimensional.  A block id maps to a (k-slice, tile) pair, split-major, through xcd_remap (every
+// XCD gets a contiguous id range: block b runs on XCD b % 8) and tile_origin (groups of 8 tile rows), see decode_work.
+//
+// Relied on from outside: the Makefile turns this file into a string (gemm_src.inc) that hiprtc compiles as the main file
+// with a generated functor and a kernel calling gemm_block or gemm_narrow_k_block appended — so it includes nothing but the
+// HIP runtime, and tests/test_lds_dma_isa.py reads it as one file.  gemm_batched.hip calls gemm_block_at.  The tools
+// (tools/gemm_pipe.hip, dgrad_ab.hip, narrow_k_harness.hip, gemm_tune.hip) instantiate the kernels and entry points by
+// name with their full template parameter lists, ABL (ablation bits, 0 in the library) included.
 #ifndef __HIPCC_RTC__  // hiprtc (kernels/gemm_fused.hpp) compiles this text as the main file, runtime built in
 #pragma once
 #include <hip/hip_runtime.h>
@@ -321,6 +332,152 @@ struct Geometry {
   static constexpr int NT = WAVES * 64;
 };
 
+// ---- parts shared by the k loops and the stores (gemm_f32_pair.hpp uses them too) -----------------------------------------
+// 32x32 accumulator block: register r of lane l holds row acc_row(r, l) = acc_reg_row(r) + 4 * (l >> 5), column l & 31.
+__device__ __forceinline__ int acc_reg_row(int r) { return (r & 3) + 8 * (r >> 2); }
+__device__ __forceinline__ int acc_row(int r, int lane) { return acc_reg_row(r) + 4 * (lane >> 5); }
+
+__device__ __forceinline__ void zero_acc(f32x16& v) {
+#pragma unroll
+  for (int r = 0; r < 16; ++r) v[r] = 0.f;
+}
+template <int MI, int NI>
+__device__ __forceinline__ void zero_acc(f32x16 (&acc)[MI][NI]) {
+#pragma unroll
+  for (int i = 0; i < MI; ++i)
+#pragma unroll
+    for (int j = 0; j < NI; ++j) zero_acc(acc[i][j]);
+}
+
+// Ragged tiles: bit i * NI + j is set when 32x32 sub-block (i, j) of the wave tile at (m_blk + wm0, n_blk + wn0) has a row
+// and a column inside the problem; the others are skipped (wave-uniform branch), so a ragged M or N costs matrix work at
+// 32-row granularity instead of tile granularity (M = 784 with 128-row tiles: 800 rows of work, not 896).
+template <int BM, int BN, int MI, int NI, bool AIL, bool BIL>
+__device__ __forceinline__ unsigned live_blocks(const GemmArgs& a, long m_blk, long n_blk, int wm0, int wn0) {
+  const int m_w = __builtin_amdgcn_readfirstlane((int)min(a.M - m_blk - wm0, (long)BM));
+  const int n_w = __builtin_amdgcn_readfirstlane((int)min(a.N - n_blk - wn0, (long)BN));
+  unsigned live = 0;
+#pragma unroll
+  for (int i = 0; i < MI; ++i)
+#pragma unroll
+    for (int j = 0; j < NI; ++j)
+      if ((AIL ? i : i * 32) < m_w && (BIL ? j : j * 32) < n_w) live |= 1u << (i * NI + j);
+  return live;
+}
+
+// LDS-DMA tiles (DmaLoader below): 16-byte chunk c of k-contiguous row r sits in slot c ^ dma_swizzle<BK>(r).
+template <int BK>
+__device__ __forceinline__ int dma_swizzle(int r) {
+  return BK == 16 ? (r >> 2) & 3 : BK == 32 ? (r >> 1) & 7 : r & 15;
+}
+
+// Fragments of k-group pp (8 k) of the LDS-DMA stage at As (A tile, then B tile): av[mi][j] / bv[ni][j] = this lane's A / B
+// value of block mi / ni for MFMA k-step j (k = 8 pp + j in lanes 0-31, 8 pp + 4 + j in lanes 32-63).  An interleaved
+// operand (AIL / BIL) brings this lane's value for every block with one 8- or 16-byte read per k; a k-contiguous one
+// with one ds_read_b128 per block (four k-steps).
+template <int BM, int BN, int BK, int MI, int NI, bool A_KC, bool B_KC, bool AIL, bool BIL>
+__device__ __forceinline__ void read_fragments(const float* As, int pp, int wm0, int wn0, int lane, float (&av)[MI][4],
+                                               float (&bv)[NI][4]) {
+  const int i = lane & 31, hi = lane >> 5;
+  const float* Bs = As + BK * BM;
+  if constexpr (AIL) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      typedef float vecA __attribute__((ext_vector_type(MI)));
+      const vecA v = *reinterpret_cast<const vecA*>(As + (8 * pp + j + 4 * hi) * BM + wm0 + MI * i);
+#pragma unroll
+      for (int mi = 0; mi < MI; ++mi) av[mi][j] = v[mi];
+    }
+  }
+  if constexpr (BIL) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      typedef float vecB __attribute__((ext_vector_type(NI)));
+      const vecB v = *reinterpret_cast<const vecB*>(Bs + (8 * pp + j + 4 * hi) * BN + wn0 + NI * i);
+#pragma unroll
+      for (int ni = 0; ni < NI; ++ni) bv[ni][j] = v[ni];
+    }
+  }
+#pragma unroll
+  for (int mi = 0; mi < MI; ++mi) {
+    if (AIL) break;
+    const int row = wm0 + mi * 32 + i;
+    if (A_KC) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(As + row * BK + (((2 * pp + hi) ^ dma_swizzle<BK>(row)) << 2));
+#pragma unroll
+      for (int j = 0; j < 4; ++j) av[mi][j] = v[j];
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) av[mi][j] = As[(8 * pp + j + 4 * hi) * BM + row];
+    }
+  }
+#pragma unroll
+  for (int ni = 0; ni < NI; ++ni) {
+    if (BIL) break;
+    const int col = wn0 + ni * 32 + i;
+    if (B_KC) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(Bs + col * BK + (((2 * pp + hi) ^ dma_swizzle<BK>(col)) << 2));
+#pragma unroll
+      for (int j = 0; j < 4; ++j) bv[ni][j] = v[j];
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) bv[ni][j] = Bs[(8 * pp + j + 4 * hi) * BN + col];
+    }
+  }
+}
+
+// Ragged end of K in an LDS-DMA tile: the loaders re-read the last valid k for the missing ones; every thread of the block
+// zeroes its share of them on the A side (k_tail .. BK - 1 of the stage At) so they contribute nothing.  The caller's barrier
+// publishes the zeros.
+template <int BM, int BK, int NT, bool A_KC>
+__device__ __forceinline__ void zero_k_tail(float* At, int k_tail, int tid) {
+  const int width = BK - k_tail;
+  for (int e = tid; e < BM * width; e += NT) {
+    if (A_KC) {
+      const int r = e / width, k = k_tail + e % width;
+      At[r * BK + (((k >> 2) ^ dma_swizzle<BK>(r)) << 2) + (k & 3)] = 0.f;
+    } else {
+      At[k_tail * BM + e] = 0.f;
+    }
+  }
+}
+
+// One accumulator block row (NI blocks of a wave's sub-tile) parked in LDS as rows of STRIDE floats: block register r of
+// this lane goes to row row0 + acc_row(r, lane), column wn0 + (its column of the sub-tile).  bil: the lane's NI columns are
+// adjacent (see Interleaved): one 8- / 16-byte LDS write per row.
+template <int NI, int STRIDE>
+__device__ __forceinline__ void park_block_row(float* park, const f32x16 (&acc)[NI], bool bil, int row0, int wn0, int lane) {
+  if (bil) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      typedef float vecN __attribute__((ext_vector_type(NI)));
+      vecN v;
+#pragma unroll
+      for (int j = 0; j < NI; ++j) v[j] = acc[j][r];
+      *reinterpret_cast<vecN*>(&park[(row0 + acc_row(r, lane)) * STRIDE + wn0 + NI * (lane & 31)]) = v;
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < NI; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) park[(row0 + acc_row(r, lane)) * STRIDE + wn0 + j * 32 + (lane & 31)] = acc[j][r];
+  }
+}
+
+// Packed predicate words: eight neighbouring lanes hold the eight nibbles of a 32-bit word (lane t: bits 4 (t & 7) ..).
+// Three butterfly steps leave the whole word in each of them, for all G words at once — chunk by chunk, each behind its
+// guarded store, every one of the 3 x 8 crossbar shuffles of a pass waited out its own latency (round 6; the pattern
+// EG_ROW_TRACE found in the row groups).
+template <int G>
+__device__ __forceinline__ void fold_pred_nibbles(unsigned (&w)[G], int tid) {
+#pragma unroll
+  for (int c = 0; c < G; ++c) w[c] <<= 4 * (tid & 7);
+#pragma unroll
+  for (int step = 1; step <= 4; step <<= 1)
+#pragma unroll
+    for (int c = 0; c < G; ++c) w[c] |= __shfl_xor(w[c], step, 64);
+}
+
 // K loop of one block.  E = predicate every global load against the problem edges.
 // ABL (tuning harness only; the library always instantiates 0): bit 0 = no LDS fragment reads in
 // the k loop, bit 1 = no global loads / LDS stores after the first tile, bit 2 = no barriers,
@@ -356,20 +513,7 @@ __device__ __forceinline__ void gemm_mainloop(const GemmArgs& a, float* lds, f32
   const int b_off = (lane >> 5) * SB + wn0 + (BIL ? NI * (lane & 31) : (lane & 31));
   constexpr int A_STEP = AIL ? 1 : 32, B_STEP = BIL ? 1 : 32;  // distance between a lane's blocks in an LDS row
 
-  // Edge tiles: 32x32 sub-blocks of the wave tile that lie completely outside the problem are
-  // skipped (wave-uniform branch), so a ragged M or N costs matrix work at 32-row granularity
-  // instead of tile granularity (M = 784 with 128-row tiles: 800 rows of work, not 896).
-  unsigned live = 0xffffffffu;
-  if (E) {
-    const long m_w = __builtin_amdgcn_readfirstlane((int)min(a.M - m_blk - wm0, (long)BM));
-    const long n_w = __builtin_amdgcn_readfirstlane((int)min(a.N - n_blk - wn0, (long)BN));
-    live = 0;
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-      for (int j = 0; j < NI; ++j)
-        if ((AIL ? i : i * 32) < m_w && (BIL ? j : j * 32) < n_w) live |= 1u << (i * NI + j);
-  }
+  const unsigned live = E ? live_blocks<BM, BN, MI, NI, AIL, BIL>(a, m_blk, n_blk, wm0, wn0) : 0xffffffffu;  // edge tiles
 
   for (int kt = 0; kt < nk; ++kt) {
     const int cur = kt & 1;
@@ -502,7 +646,7 @@ struct DmaLoader {
   mutable int pix_x[PER_WAVE], pix_y[PER_WAVE];
   mutable long pix_next = -1;
 
-  __device__ __forceinline__ static int swizzle(int r) { return BK == 16 ? (r >> 2) & 3 : BK == 32 ? (r >> 1) & 7 : r & 15; }
+  __device__ __forceinline__ static int swizzle(int r) { return dma_swizzle<BK>(r); }
 
   __device__ __forceinline__ void init(const GemmArgs& a, long mn0, int wave, int lane, long limit = 0, long ld = 0,
                                        bool ones = false) {
@@ -692,23 +836,11 @@ __device__ __forceinline__ void gemm_mainloop_dma(const GemmArgs& a, float* lds,
   using DmaA = DmaLoader<BM, BK, NT, A_KC, CONV == 1, CL, KCL>;
   using DmaB = DmaLoader<BN, BK, NT, B_KC, CONV == 2, CL, KCL>;
   const int lane = tid & 63, wave = tid >> 6;
-  const int i = lane & 31, hi = lane >> 5;
   // IL: interleaved accumulator rows / columns (see Interleaved).  The clamped loop runs blocked for tiles
   // that are ragged in M or N, interleaved for the last k-tile of a tile that is ragged at the end of K only.
   constexpr bool AIL = IL && Interleaved<A_KC, MI>::value, BIL = IL && Interleaved<B_KC, NI>::value;
 
-  // ragged tile: 32x32 sub-blocks of the wave tile that lie outside the problem are skipped
-  unsigned live = 0xffffffffu;
-  if (CL) {
-    const int m_w = __builtin_amdgcn_readfirstlane((int)min(a.M - m_blk - wm0, (long)BM));
-    const int n_w = __builtin_amdgcn_readfirstlane((int)min(a.N - n_blk - wn0, (long)BN));
-    live = 0;
-#pragma unroll
-    for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-      for (int ni = 0; ni < NI; ++ni)
-        if ((AIL ? mi : mi * 32) < m_w && (BIL ? ni : ni * 32) < n_w) live |= 1u << (mi * NI + ni);
-  }
+  const unsigned live = CL ? live_blocks<BM, BN, MI, NI, AIL, BIL>(a, m_blk, n_blk, wm0, wn0) : 0xffffffffu;  // ragged tile
 
   DmaA da;
   DmaB db;
@@ -722,82 +854,24 @@ __device__ __forceinline__ void gemm_mainloop_dma(const GemmArgs& a, float* lds,
   const int k_tail = KCL ? (int)((k_end - k_begin) % BK) : 0;  // valid k of a ragged last k-tile (0 = full)
   dma_publish_barrier();
 
-  // Fragments of k-group pp (8 k) of the tile at As: av[mi][j] / bv[ni][j] = this lane's A / B value of block mi / ni for
-  // MFMA k-step j (k = 8 pp + j in lanes 0-31, 8 pp + 4 + j in lanes 32-63).
   auto fragments = [&](const float* As, int pp, float (&av)[MI][4], float (&bv)[NI][4]) {
-    const float* Bs = As + BK * BM;
-    if constexpr (AIL) {  // one 8- or 16-byte read per k brings this lane's value for every block
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        typedef float vecA __attribute__((ext_vector_type(MI)));
-        const vecA v = *reinterpret_cast<const vecA*>(As + (8 * pp + j + 4 * hi) * BM + wm0 + MI * i);
-#pragma unroll
-        for (int mi = 0; mi < MI; ++mi) av[mi][j] = v[mi];
-      }
-    }
-    if constexpr (BIL) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        typedef float vecB __attribute__((ext_vector_type(NI)));
-        const vecB v = *reinterpret_cast<const vecB*>(Bs + (8 * pp + j + 4 * hi) * BN + wn0 + NI * i);
-#pragma unroll
-        for (int ni = 0; ni < NI; ++ni) bv[ni][j] = v[ni];
-      }
-    }
-#pragma unroll
-    for (int mi = 0; mi < MI; ++mi) {
-      if (AIL) break;
-      const int row = wm0 + mi * 32 + i;
-      if (A_KC) {
-        const int slot = (2 * pp + hi) ^ DmaA::swizzle(row);
-        const f32x4 v = *reinterpret_cast<const f32x4*>(As + row * BK + slot * 4);
-        av[mi][0] = v[0];
-        av[mi][1] = v[1];
-        av[mi][2] = v[2];
-        av[mi][3] = v[3];
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) av[mi][j] = As[(8 * pp + j + 4 * hi) * BM + row];
-      }
-    }
-#pragma unroll
-    for (int ni = 0; ni < NI; ++ni) {
-      if (BIL) break;
-      const int col = wn0 + ni * 32 + i;
-      if (B_KC) {
-        const int slot = (2 * pp + hi) ^ DmaB::swizzle(col);
-        const f32x4 v = *reinterpret_cast<const f32x4*>(Bs + col * BK + slot * 4);
-        bv[ni][0] = v[0];
-        bv[ni][1] = v[1];
-        bv[ni][2] = v[2];
-        bv[ni][3] = v[3];
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) bv[ni][j] = Bs[(8 * pp + j + 4 * hi) * BN + col];
-      }
-    }
+    read_fragments<BM, BN, BK, MI, NI, A_KC, B_KC, AIL, BIL>(As, pp, wm0, wn0, lane, av, bv);
   };
   auto multiply_step = [&](const float (&av)[MI][4], const float (&bv)[NI][4], int j) {  // MFMA k-step j of a k-group
 #pragma unroll
     for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
       for (int ni = 0; ni < NI; ++ni)
+        // A wave with ONE block (64 x 64, 128 x 32 tiles) multiplies unconditionally: a test per MFMA is a scalar
+        // branch per MFMA, with the fragment reads stuck in front of it — a ragged tile's waves ran ~25 % slower
+        // per k-tile than an interior tile's, and a launch is as slow as its slowest block.  What a wave outside
+        // the problem accumulates (clamped re-reads of valid data) is never stored.
         if (!CL || MI * NI == 1 || (live >> (mi * NI + ni) & 1))
           acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[mi][j], bv[ni][j], acc[mi][ni], 0, 0, 0);
   };
   auto multiply = [&](const float (&av)[MI][4], const float (&bv)[NI][4]) {
 #pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < NI; ++ni)
-          // A wave with ONE block (64 x 64, 128 x 32 tiles) multiplies unconditionally: a test per MFMA is a scalar
-          // branch per MFMA, with the fragment reads stuck in front of it — a ragged tile's waves ran ~25 % slower
-          // per k-tile than an interior tile's, and a launch is as slow as its slowest block.  What a wave outside
-          // the problem accumulates (clamped re-reads of valid data) is never stored.
-          if (!CL || MI * NI == 1 || (live >> (mi * NI + ni) & 1))
-            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[mi][j], bv[ni][j], acc[mi][ni], 0, 0, 0);
+    for (int j = 0; j < 4; ++j) multiply_step(av, bv, j);
   };
 
   if constexpr (!KCL && (ABL & 64)) {
@@ -930,18 +1004,7 @@ __device__ __forceinline__ void gemm_mainloop_dma(const GemmArgs& a, float* lds,
       db.issue(a, a.B, a.ldb, n_blk, k0, nxt + BK * BM, wave, lane, a.N, k_end);
     }
     if (KCL && k_tail != 0 && kt == nk - 1) {
-      // ragged end of K: the loaders re-read the last valid k for the missing ones; zero them on
-      // the A side so they contribute nothing
-      float* At = lds + cur * BUF;
-      const int width = BK - k_tail;
-      for (int e = tid; e < BM * width; e += NT) {
-        if (A_KC) {
-          const int r = e / width, k = k_tail + e % width;
-          At[r * BK + (((k >> 2) ^ DmaA::swizzle(r)) << 2) + (k & 3)] = 0.f;
-        } else {
-          At[k_tail * BM + e] = 0.f;
-        }
-      }
+      zero_k_tail<BM, BK, NT, A_KC>(lds + cur * BUF, k_tail, tid);  // ragged end of K
       __syncthreads();
     }
     const float* As = lds + cur * BUF;
@@ -988,25 +1051,16 @@ __device__ __forceinline__ void gemm_mainloop_dma_x(const GemmArgs& a, float* ld
   };
   if (nk > 0) issue(0);
   dma_publish_barrier();
-  // fragments of k-group pp of the tile at stage `st` (A / B interleaved: one read per k brings every block's value; the
-  // strip's A value and this wave's 32 columns of B for the ninth block)
+  // fragments of k-group pp of the tile at stage `st`: the tile's (A / B interleaved), then the strip's A value and this
+  // wave's 32 columns of B for the ninth block
   auto fragments = [&](int st, int pp, float (&av)[MI][4], float (&bv)[NI][4], float (&ax)[4], float (&bx)[4]) {
     const float* As = lds + st * BUF;
-    const float* Bs = As + BK * BM;
-    const float* Xs = xs + st * BK * 32;
+    read_fragments<BM, BN, BK, MI, NI, false, false, true, true>(As, pp, wm0, wn0, lane, av, bv);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int k = 8 * pp + j + 4 * hi;
-      typedef float vecA __attribute__((ext_vector_type(MI)));
-      typedef float vecB __attribute__((ext_vector_type(NI)));
-      const vecA va = *reinterpret_cast<const vecA*>(As + k * BM + wm0 + MI * i);
-      const vecB vb = *reinterpret_cast<const vecB*>(Bs + k * BN + wn0 + NI * i);
-#pragma unroll
-      for (int mi = 0; mi < MI; ++mi) av[mi][j] = va[mi];
-#pragma unroll
-      for (int ni = 0; ni < NI; ++ni) bv[ni][j] = vb[ni];
-      ax[j] = Xs[k * 32 + i];
-      bx[j] = Bs[k * BN + wave * 32 + i];
+      ax[j] = xs[st * BK * 32 + k * 32 + i];
+      bx[j] = As[BK * BM + k * BN + wave * 32 + i];
     }
   };
   auto multiply = [&](const float (&av)[MI][4], const float (&bv)[NI][4], const float (&ax)[4], const float (&bx)[4]) {
@@ -1051,45 +1105,32 @@ __device__ __forceinline__ void gemm_mainloop_dma_x(const GemmArgs& a, float* ld
   }
 }
 
-// MINB: blocks per CU the register allocator must leave room for (waves/SIMD = MINB * WAVES / 4).
-// EDGE kernels still run their interior tiles on the unpredicated loop.
-// DMA: interior tiles use the LDS-DMA loop (requires VEC == 4, BK in {16, 32}; with CONV the host
-// checks C % BK == 0).
-// CONV: 0 = plain operands, 1 = A is the im2col matrix of an NHWC image (forward convolution),
-// 2 = B is that matrix with k = output pixel, n = tap (filter-gradient contraction).
-template <int BM, int BN, int BK, int WM, int WN, bool A_KC, bool B_KC, int VEC, bool EDGE, int CONV, int ABL, bool DMA,
-          class Epi, bool XR = false>
-__device__ __forceinline__ void gemm_block_at(const GemmArgs& a, const int block_id) {
-  constexpr int WAVES_N = BN / WN;
-  constexpr int MI = WM / 32, NI = WN / 32;
-  constexpr int SA = LdsStride<BM, BK, A_KC>::value, SB = LdsStride<BN, BK, B_KC>::value;
+// ---- the block body of the tile kernels, in parts: decode, (W2), k loop, store --------------------------------------------
 
-  // (XR: + the strip's stages; a row product: two padded stages of parked rows + the 256 x 16 piece of W2 + one hand-over block)
-  constexpr bool RD = Epi::RD_N > 0;
-  constexpr int RD_FLOATS = RD ? 2 * (BM / WM) * 32 * (BN + 4) + BN * 16 + 4 * 64 * 4 : 0;
-  constexpr int OPERAND_FLOATS = 2 * BK * (SA + SB) + (XR ? 2 * BK * 32 : 0);
-  __shared__ __attribute__((aligned(16))) float lds[RD_FLOATS > OPERAND_FLOATS ? RD_FLOATS : OPERAND_FLOATS];
+// EG_GEMM_TRACE=1 (GemmArgs::trace): cycle stamp k of this wave; the last one (3) waits for the tile's stores first.
+// (Nothing of the trace stays live across the k loop: the pointer is re-read from the kernel arguments at every stamp —
+// kept in registers it cost the extra-row kernel, which has none to spare, 10 - 15 us.)
+template <int WAVES>
+__device__ __forceinline__ void trace_stamp(const GemmArgs& a, int wave, int lane, int k) {
+  if (k == 3 && a.trace) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  if (a.trace && lane == 0) a.trace[((long)blockIdx.x * WAVES + wave) * 4 + k] = __builtin_readcyclecounter();
+}
 
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = tid >> 6;
-  const int wm0 = (wave / WAVES_N) * WM;
-  const int wn0 = (wave % WAVES_N) * WN;
-  if (a.run_if && *(volatile const unsigned*)a.run_if != a.run_if_val) return;  // block-uniform, ahead of every barrier
-  if (a.prio) __builtin_amdgcn_s_setprio(3);
-  // (nothing of the trace stays live across the k loop: the pointer is re-read from the kernel arguments at every stamp —
-  // kept in registers it cost the extra-row kernel, which has none to spare, 10 - 15 us)
-  auto stamp = [&](int k) {
-    if (a.trace && lane == 0) a.trace[((long)blockIdx.x * (BM / WM) * WAVES_N + wave) * 4 + k] = __builtin_readcyclecounter();
-  };
-  stamp(0);
+// One work item of a launch: k-slice `split` (k_slice long) of the tile at (m_blk, n_blk).
+struct WorkItem {
+  int split;
+  long m_blk, n_blk, k_slice;
+  int tail_slab;  // >= 0: this block writes a whole-tile slab (GemmArgs::tail_tiles)
+};
 
-  // ---- tile coordinates: XCD-contiguous ids, then 8-row groups so co-resident tiles share
-  //      A row-panels and B column-panels inside one L2.
-  // Work items are (k-split, tile) pairs, split-major.  xcd_remap hands every XCD a contiguous
-  // range of them, so the tiles of one k-split — which all stream the same rows of A and B — run
-  // on one XCD at the same time and share its L2 (with the splits spread round-robin over the
-  // XCDs a weight-gradient contraction fetched its operands 4.9x: 1.65 GB for 339 MB).
+// Block id -> work item: XCD-contiguous ids, then 8-row groups so co-resident tiles share A row-panels and B
+// column-panels inside one L2.
+// Work items are (k-split, tile) pairs, split-major.  xcd_remap hands every XCD a contiguous
+// range of them, so the tiles of one k-split — which all stream the same rows of A and B — run
+// on one XCD at the same time and share its L2 (with the splits spread round-robin over the
+// XCDs a weight-gradient contraction fetched its operands 4.9x: 1.65 GB for 339 MB).
+template <int BM, int BN>
+__device__ __forceinline__ WorkItem decode_work(const GemmArgs& a, int block_id) {
   const int rows_m = a.edge_splits > 0 ? a.tiles_m - 1 : a.tiles_m;  // tile rows cut into a.splits slices
   const int nwg = rows_m * a.tiles_n;
   const int nsplit = a.splits > 1 ? a.splits : 1;
@@ -1103,100 +1144,99 @@ __device__ __forceinline__ void gemm_block_at(const GemmArgs& a, const int block
                               ? xcd_remap(block_id, tail_first)
                               : tail_first + xcd_remap(block_id - tail_first, a.tail_tiles * a.tail_splits))
                        : xcd_remap(block_id, nfull + a.tiles_n * a.edge_splits);
-  int split;
-  long m_blk, n_blk, k_slice;
-  int tail_slab = -1;  // >= 0: this block writes a whole-tile slab
+  WorkItem w;
+  w.tail_slab = -1;
   if (a.tail_tiles > 0) {
     if (work < tail_first) {
-      split = 0;
-      tile_origin<BM, BN>(work, rows_m, a.tiles_n, m_blk, n_blk);
-      k_slice = a.k_per_split;
+      w.split = 0;
+      tile_origin<BM, BN>(work, rows_m, a.tiles_n, w.m_blk, w.n_blk);
+      w.k_slice = a.k_per_split;
     } else {
-      const int w = work - tail_first;
-      const int t = w / a.tail_splits;
-      split = w - t * a.tail_splits;
-      tile_origin<BM, BN>(tail_first + t, rows_m, a.tiles_n, m_blk, n_blk);
-      k_slice = a.tail_k_per_split;
-      tail_slab = w;
+      w.tail_slab = work - tail_first;
+      const int t = w.tail_slab / a.tail_splits;
+      w.split = w.tail_slab - t * a.tail_splits;
+      tile_origin<BM, BN>(tail_first + t, rows_m, a.tiles_n, w.m_blk, w.n_blk);
+      w.k_slice = a.tail_k_per_split;
     }
   } else if (work < nfull) {
-    split = work / nwg;
-    tile_origin<BM, BN>(work - split * nwg, rows_m, a.tiles_n, m_blk, n_blk);
-    k_slice = a.k_per_split;
-  } else {
-    const int w = work - nfull;
-    split = w / a.tiles_n;
-    m_blk = (long)rows_m * BM;
-    n_blk = (long)(w - split * a.tiles_n) * BN;
-    k_slice = a.k_per_split_edge;
+    w.split = work / nwg;
+    tile_origin<BM, BN>(work - w.split * nwg, rows_m, a.tiles_n, w.m_blk, w.n_blk);
+    w.k_slice = a.k_per_split;
+  } else {  // a slice of the ragged last tile row (GemmArgs::edge_splits)
+    const int e = work - nfull;
+    w.split = e / a.tiles_n;
+    w.m_blk = (long)rows_m * BM;
+    w.n_blk = (long)(e - w.split * a.tiles_n) * BN;
+    w.k_slice = a.k_per_split_edge;
   }
+  return w;
+}
 
-  const long k_begin = (long)split * k_slice;
-  const long k_end = min(a.K, k_begin + k_slice);
-  const int nk = (int)((k_end - k_begin + BK - 1) / BK);
-
-  f32x16 acc[MI][NI];
+// A row product's piece of W2 (rows n_blk .. n_blk + BN, 16 columns) goes to LDS behind the two stages of parked
+// rows — outside the operand buffers, so it is fetched here, under the k loop's prologue, and published by the
+// barriers of the k loop: [k / 4][16][k % 4] (one ds_read_b128 per 16-k window and lane).
+template <class Epi, int BM, int BN, int WM, int WN>
+__device__ __forceinline__ void stage_row_product_weights(const GemmArgs& a, float* lds, long n_blk, int tid) {
+  constexpr int RT = (BM / WM) * 32, NT = Geometry<BM, BN, WM, WN>::NT;
+  float* w2s = lds + 2 * RT * (BN + 4);
+  const float* w2 = static_cast<const float*>(a.epi[Epi::RD_W]);
+  // (all loads first, then the stores: as one `w2s[...] = cond ? w2[...] : 0` loop the eight trips of a thread were eight
+  // dependent round trips to L2 — EG_GEMM_TRACE, round 6: the k loop of the fused forward product began 7 800 cycles after
+  // the wave's start, 1 600 in the plain kernel)
+  constexpr int TRIPS = (BN * 16 + NT - 1) / NT;
+  float wv[TRIPS];
 #pragma unroll
-  for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int j = 0; j < NI; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-  if constexpr (RD) {
-    // a row product's piece of W2 (rows n_blk .. n_blk + BN, 16 columns) goes to LDS behind the two stages of parked
-    // rows — outside the operand buffers, so it is fetched here, under the k loop's prologue, and published by the
-    // barriers of the k loop: [k / 4][16][k % 4] (one ds_read_b128 per 16-k window and lane)
-    constexpr int RT_ = (BM / WM) * 32, NTHREADS = Geometry<BM, BN, WM, WN>::NT;
-    float* w2s = lds + 2 * RT_ * (BN + 4);
-    const float* w2 = static_cast<const float*>(a.epi[Epi::RD_W]);
-    // (all loads first, then the stores: as one `w2s[...] = cond ? w2[...] : 0` loop the eight trips of a thread were eight
-    // dependent round trips to L2 — EG_GEMM_TRACE, round 6: the k loop of the fused forward product began 7 800 cycles after
-    // the wave's start, 1 600 in the plain kernel)
-    constexpr int TRIPS = (BN * 16 + NTHREADS - 1) / NTHREADS;
-    float wv[TRIPS];
-#pragma unroll
-    for (int t = 0; t < TRIPS; ++t) {
-      const int e = tid + t * NTHREADS, k = (e >> 4) < BN ? (e >> 4) : BN - 1, c = e & 15;
-      const float v = w2[(n_blk + k) * (long)Epi::RD_LDW + (c < Epi::RD_N ? c : 0)];
-      wv[t] = c < Epi::RD_N ? v : 0.f;
-    }
-#pragma unroll
-    for (int t = 0; t < TRIPS; ++t) {
-      const int e = tid + t * NTHREADS, k = e >> 4, c = e & 15;
-      if (e < BN * 16) w2s[(((k >> 2) * 16 + c) << 2) + (k & 3)] = wv[t];
-    }
+  for (int t = 0; t < TRIPS; ++t) {
+    const int e = tid + t * NT, k = (e >> 4) < BN ? (e >> 4) : BN - 1, c = e & 15;
+    const float v = w2[(n_blk + k) * (long)Epi::RD_LDW + (c < Epi::RD_N ? c : 0)];
+    wv[t] = c < Epi::RD_N ? v : 0.f;
   }
+#pragma unroll
+  for (int t = 0; t < TRIPS; ++t) {
+    const int e = tid + t * NT, k = e >> 4, c = e & 15;
+    if (e < BN * 16) w2s[(((k >> 2) * 16 + c) << 2) + (k & 3)] = wv[t];
+  }
+}
+
+// The k loop of one work item: picks among the LDS-DMA loop on whole tiles (interior), that loop plus the clamped last
+// k-tile, the clamped loops of a ragged tile, the register-staged loop and the extra-rows loop (which stores its strip).
+// Returns !EDGE || interior || k_tail_only — the tile is whole in M and N (its k range may end inside a k-tile): the
+// condition under which the LDS-DMA loops interleave accumulator rows / columns (see Interleaved), which the store needs.
+// DMA: interior tiles use the LDS-DMA loop (requires VEC == 4, BK in {16, 32}; with CONV the host checks C % BK == 0);
+// EDGE kernels still run their interior tiles on the unclamped, unpredicated loops.
+template <int BM, int BN, int BK, int WM, int WN, bool A_KC, bool B_KC, int VEC, bool EDGE, int CONV, int ABL, bool DMA, bool XR>
+__device__ __forceinline__ bool run_k_loop(const GemmArgs& a, float* lds, f32x16 (&acc)[WM / 32][WN / 32], const WorkItem& w,
+                                           long k_begin, long k_end, int tid, int wm0, int wn0) {
   static_assert(!DMA || VEC == 4, "LDS-DMA loop: 16-byte aligned operands");
+  const long m_blk = w.m_blk, n_blk = w.n_blk;
+  const int nk = (int)((k_end - k_begin + BK - 1) / BK);
   const bool whole_k = (k_end - k_begin) % BK == 0;
   const bool interior = m_blk + BM <= a.a_rows && n_blk + BN <= a.N && whole_k;
   // A tile that is whole in M and N but ends inside a k-tile (K = 4100: every tile) runs its whole k-tiles
   // on the interior loop and only the last one on the clamped loop (4096 x 4096 x 4100 took 1060 us with
   // every k-tile clamped, against 973 us for K = 4112).
   const bool k_tail_only = EDGE && DMA && CONV == 0 && !whole_k && k_end > k_begin && m_blk + BM <= a.a_rows && n_blk + BN <= a.N;
-  stamp(1);
-  bool done = false;
+  const bool il = !EDGE || interior || k_tail_only;
   if constexpr (XR) {
     // extra rows: the blocks of the last tile row multiply and store the strip [tiles_m * BM, M) as well (split-K only:
     // the strip goes to this block's slab)
     if (a.x_rows > 0 && m_blk == (long)(a.tiles_m - 1) * BM) {
+      const int lane = tid & 63, wave = tid >> 6;
       f32x16 accx;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) accx[r] = 0.f;
+      zero_acc(accx);
       gemm_mainloop_dma_x<BM, BN, BK, WM, WN>(a, lds, acc, accx, m_blk, n_blk, k_begin, nk, tid, wm0, wn0);
-      float* slab = a.partial + (long)split * a.M * a.N;
+      float* slab = a.partial + (long)w.split * a.M * a.N;
       const long n = n_blk + wave * 32 + (lane & 31);
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const long m = m_blk + BM + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        const long m = m_blk + BM + acc_row(r, lane);
         if (m < a.M) slab[m * a.N + n] = accx[r];
       }
-      done = true;
+      return il;
     }
   }
   if constexpr (DMA) {  // kernels without the DMA loop (tuning harness: BK = 8) never instantiate it
-    if (done) {
-    } else if (!EDGE || interior || k_tail_only) {
+    if (il) {
       const int n_main = (EDGE && k_tail_only) ? nk - 1 : nk;
       if (n_main > 0)
         gemm_mainloop_dma<BM, BN, BK, WM, WN, A_KC, B_KC, CONV, false, true, false, ABL>(a, lds, acc, m_blk, n_blk, k_begin, n_main, tid, wm0, wn0);
@@ -1205,7 +1245,7 @@ __device__ __forceinline__ void gemm_block_at(const GemmArgs& a, const int block
           gemm_mainloop_dma<BM, BN, BK, WM, WN, A_KC, B_KC, CONV, true, true>(a, lds, acc, m_blk, n_blk,
                                                                                k_begin + (long)n_main * BK, 1, tid, wm0, wn0, k_end);
       }
-      done = true;
+      return il;
     } else if (CONV != 1) {
       // ragged in M or N (and maybe K): still the LDS-DMA loop, with clamped addresses and a zeroed K tail.
       // Plain operands: the whole k-tiles on the loader with precomputed clamped offsets, the last, partial
@@ -1222,19 +1262,125 @@ __device__ __forceinline__ void gemm_block_at(const GemmArgs& a, const int block
         gemm_mainloop_dma<BM, BN, BK, WM, WN, A_KC, B_KC, CONV, true>(a, lds, acc, m_blk, n_blk, k_begin, nk, tid, wm0, wn0,
                                                                         k_end);
       }
-      done = true;
+      return il;
     }
   }
   if constexpr (!DMA || (EDGE && CONV == 1)) {  // register-staged loop: unaligned operands, ragged im2col tiles
-    if (!done) {
-      if (EDGE && !interior)
-        gemm_mainloop<BM, BN, BK, WM, WN, A_KC, B_KC, VEC, true, CONV, ABL>(a, lds, acc, m_blk, n_blk, k_begin, k_end, nk,
-                                                                           tid, wm0, wn0);
-      else
-        gemm_mainloop<BM, BN, BK, WM, WN, A_KC, B_KC, VEC, false, CONV, ABL>(a, lds, acc, m_blk, n_blk, k_begin, k_end, nk,
-                                                                            tid, wm0, wn0);
+    if (EDGE && !interior)
+      gemm_mainloop<BM, BN, BK, WM, WN, A_KC, B_KC, VEC, true, CONV, ABL>(a, lds, acc, m_blk, n_blk, k_begin, k_end, nk,
+                                                                         tid, wm0, wn0);
+    else
+      gemm_mainloop<BM, BN, BK, WM, WN, A_KC, B_KC, VEC, false, CONV, ABL>(a, lds, acc, m_blk, n_blk, k_begin, k_end, nk,
+                                                                          tid, wm0, wn0);
+  }
+  return il;
+}
+
+// The row product of a generated epilogue (Epi::RD_N > 0, see above EpiNone) inside the wide-store pass of a 256 x 256 tile:
+// its per-wave state, the 16x16x4 MFMA block over one pass's parked rows, and the atomics that send a pass's sums off.
+template <class Epi, int BM, int BN, int WM, int MI>
+struct RowProduct {
+  typedef float rd4 __attribute__((ext_vector_type(4)));
+  static constexpr int RT = (BM / WM) * 32, PS = BN + 4;
+  float half[4] = {0.f, 0.f, 0.f, 0.f};  // this wave's half of the row product of the previous pass
+  float bias2 = 0.f;
+  float* w2s;  // W2[n_blk .. n_blk + BN) x 16 as [k / 4][16][k % 4], staged before the k loop
+  float* rdx;  // [4 blocks][64 lanes][4]: the second column half, waves 4 .. 7 -> 0 .. 3
+
+  // (the second layer's bias: loaded ONCE per tile here, not in front of the atomics of every pass — waves 0 .. 3 waited
+  // a memory round trip per pass for it and the other four waited for them at the pass's barrier)
+  __device__ __forceinline__ void init(const GemmArgs& a, float* lds, long n_blk, int wave, int lane) {
+    w2s = lds + 2 * RT * PS;
+    rdx = w2s + BN * 16;
+    if (Epi::RD_BIAS >= 0 && n_blk == 0 && wave < 4 && (lane & 15) < Epi::RD_N)
+      bias2 = static_cast<const float*>(a.epi[Epi::RD_BIAS >= 0 ? Epi::RD_BIAS : 0])[lane & 15];
+  }
+  // out2 += partial product of pass `pass` (+ bias from the first N-tile).  Lane l of wave w < 4 holds column l % 16 of
+  // staged rows 16 w + 4 (l / 16) + v.  Float atomics without return — nothing waits for them (a compare-and-swap loop
+  // costs a memory round trip behind the tile's own store burst: +14 us per tile).  gfx950's global_atomic_add_f32
+  // honours the denormal mode (tests/test_gpu_epilogue.py holds a denormal result to the bit).
+  __device__ __forceinline__ void send(const GemmArgs& a, int pass, long m_blk, bool ail, int wave, int lane) const {
+    const int r = lane & 15, g = lane >> 4;
+    if (wave < 4 && r < Epi::RD_N) {
+      const rd4 other = *reinterpret_cast<const rd4*>(rdx + (wave * 64 + lane) * 4);
+      float* out2 = static_cast<float*>(a.epi[Epi::RD_OUT]);
+#pragma unroll
+      for (int v = 0; v < 4; ++v) {
+        const int srow = wave * 16 + 4 * g + v;
+        const long m = m_blk + (long)(srow >> 5) * WM + sub_index<MI>(ail, pass, srow & 31);
+        atomicAdd(out2 + m * (long)Epi::RD_LDO + r, (half[v] + other[v]) + bias2);
+      }
     }
   }
+  // Row product of the RT = 64 rows of one pass: wave w takes the 16 rows of block w % 4 and the column half w / 4,
+  // v_mfma_f32_16x16x4_f32 over 16-wide windows — lane (r = l % 16, g = l / 16) reads res[row r][16 s + 4 g .. + 3]
+  // and W2[16 s + 4 g .. + 3][column r] as one ds_read_b128 each (stride BN + 4: 4 r + g covers the 64 banks once);
+  // MFMA j of a window multiplies k = 16 s + 4 g + j on both sides.  Two accumulators, windows alternating.
+  // Waves 4 .. 7 hand their half over through LDS (rdx); waves 0 .. 3 pick it up behind the NEXT barrier every wave
+  // passes anyway (the one that publishes the next pass's parked rows) and send the sums off there.
+  __device__ __forceinline__ void multiply(const float* park, int wave, int lane) {
+    const int r = lane & 15, g = lane >> 4, mb = wave & 3, kh = wave >> 2;
+    const float* arow = park + (mb * 16 + r) * PS + 4 * g + kh * (BN / 2);
+    const float* brow = w2s + ((g * 16 + r) << 2) + kh * (BN / 2) * 16;
+    // (four accumulators — two windows x even / odd k of a window: a chain of 8 dependent MFMAs each instead of 16; the
+    // instruction's result is not ready for the next one of its chain when that is the next but one in line)
+    rd4 d0 = {0.f, 0.f, 0.f, 0.f}, d1 = {0.f, 0.f, 0.f, 0.f}, d2 = {0.f, 0.f, 0.f, 0.f}, d3 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int s2 = 0; s2 < BN / 32; s2 += 2) {
+      const rd4 a0 = *reinterpret_cast<const rd4*>(arow + 16 * s2);
+      const rd4 b0 = *reinterpret_cast<const rd4*>(brow + 256 * s2);
+      const rd4 a1 = *reinterpret_cast<const rd4*>(arow + 16 * s2 + 16);
+      const rd4 b1 = *reinterpret_cast<const rd4*>(brow + 256 * s2 + 256);
+#pragma unroll
+      for (int j = 0; j < 4; j += 2) {
+        d0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[j], b0[j], d0, 0, 0, 0);
+        d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[j], b1[j], d1, 0, 0, 0);
+        d2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[j + 1], b0[j + 1], d2, 0, 0, 0);
+        d3 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[j + 1], b1[j + 1], d3, 0, 0, 0);
+      }
+    }
+#pragma unroll
+    for (int v = 0; v < 4; ++v) half[v] = (d0[v] + d2[v]) + (d1[v] + d3[v]);
+    if (kh == 1) *reinterpret_cast<rd4*>(rdx + (mb * 64 + lane) * 4) = rd4{half[0], half[1], half[2], half[3]};
+  }
+};
+
+// One work item of a tile kernel, top to bottom: decode, zero, (W2), k loop, store.
+// MINB (of the kernels below): blocks per CU the register allocator must leave room for (waves/SIMD = MINB * WAVES / 4).
+// CONV: 0 = plain operands, 1 = A is the im2col matrix of an NHWC image (forward convolution),
+// 2 = B is that matrix with k = output pixel, n = tap (filter-gradient contraction).
+template <int BM, int BN, int BK, int WM, int WN, bool A_KC, bool B_KC, int VEC, bool EDGE, int CONV, int ABL, bool DMA,
+          class Epi, bool XR = false>
+__device__ __forceinline__ void gemm_block_at(const GemmArgs& a, const int block_id) {
+  constexpr int WAVES = Geometry<BM, BN, WM, WN>::WAVES, WAVES_N = BN / WN;
+  constexpr int MI = WM / 32, NI = WN / 32;
+  constexpr int SA = LdsStride<BM, BK, A_KC>::value, SB = LdsStride<BN, BK, B_KC>::value;
+
+  // (XR: + the strip's stages; a row product: two padded stages of parked rows + the 256 x 16 piece of W2 + one hand-over block)
+  constexpr bool RD = Epi::RD_N > 0;
+  constexpr int RD_FLOATS = RD ? 2 * (BM / WM) * 32 * (BN + 4) + BN * 16 + 4 * 64 * 4 : 0;
+  constexpr int OPERAND_FLOATS = 2 * BK * (SA + SB) + (XR ? 2 * BK * 32 : 0);
+  __shared__ __attribute__((aligned(16))) float lds[RD_FLOATS > OPERAND_FLOATS ? RD_FLOATS : OPERAND_FLOATS];
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const int wm0 = (wave / WAVES_N) * WM;
+  const int wn0 = (wave % WAVES_N) * WN;
+  if (a.run_if && *(volatile const unsigned*)a.run_if != a.run_if_val) return;  // block-uniform, ahead of every barrier
+  if (a.prio) __builtin_amdgcn_s_setprio(3);
+  trace_stamp<WAVES>(a, wave, lane, 0);
+
+  const WorkItem w = decode_work<BM, BN>(a, block_id);
+  const long m_blk = w.m_blk, n_blk = w.n_blk;
+  const long k_begin = (long)w.split * w.k_slice;
+  const long k_end = min(a.K, k_begin + w.k_slice);
+
+  f32x16 acc[MI][NI];
+  zero_acc(acc);
+  if constexpr (RD) stage_row_product_weights<Epi, BM, BN, WM, WN>(a, lds, n_blk, tid);
+  trace_stamp<WAVES>(a, wave, lane, 1);
+  const bool il = run_k_loop<BM, BN, BK, WM, WN, A_KC, B_KC, VEC, EDGE, CONV, ABL, DMA, XR>(a, lds, acc, w, k_begin, k_end, tid, wm0, wn0);
 
   if constexpr ((ABL & 128) != 0) {
     // tuning harness only: no epilogue at all (the accumulators are folded into one value that is never equal to the
@@ -1249,229 +1395,151 @@ __device__ __forceinline__ void gemm_block_at(const GemmArgs& a, const int block
     if (s == 1.2345678e-30f) a.C[0] = s;
     return;
   }
-  stamp(2);
-  // ---- epilogue.  32x32 accumulator block: register r of lane l holds
-  //      row = (r & 3) + 8 * (r >> 2) + 4 * (l >> 5), col = l & 31.
-  const bool to_partial = a.tail_tiles > 0 ? tail_slab >= 0 : a.partial != nullptr;
-  // a tail block's slab is addressed with global (m, n) like C: slab[(m - m_blk) * BN + (n - n_blk)]
-  float* out = tail_slab >= 0 ? a.partial + (long)tail_slab * BM * BN - (m_blk * BN + n_blk)
-                              : (to_partial ? a.partial + (long)split * a.M * a.N : a.C);
-  const long ldo = tail_slab >= 0 ? BN : (to_partial ? a.N : a.ldc);
+  trace_stamp<WAVES>(a, wave, lane, 2);
+
+  // ---- store: to C, to the slab of this k-slice, or to the tail slab, which is addressed with global (m, n) like C:
+  //      slab[(m - m_blk) * BN + (n - n_blk)]
+  const bool to_partial = a.tail_tiles > 0 ? w.tail_slab >= 0 : a.partial != nullptr;
+  float* out = w.tail_slab >= 0 ? a.partial + (long)w.tail_slab * BM * BN - (m_blk * BN + n_blk)
+                                : (to_partial ? a.partial + (long)w.split * a.M * a.N : a.C);
+  const long ldo = w.tail_slab >= 0 ? BN : (to_partial ? a.N : a.ldc);
   const bool accumulate = !to_partial && a.accumulate;
   const bool has_bias = !to_partial && a.bias != nullptr;
   const bool whole_tile = m_blk + BM <= a.M && n_blk + BN <= a.N;
-  // rows / columns of the wave sub-tile that block (i, j) register r of this lane holds (see Interleaved)
-  const bool ail = Interleaved<A_KC, MI>::value && (!EDGE || interior || k_tail_only);  // block-uniform
-  const bool bil = Interleaved<B_KC, NI>::value && (!EDGE || interior || k_tail_only);
-  if (a.wide_store && (!EDGE || whole_tile)) {  // block-uniform
-    // ---- whole tile, through LDS (GemmArgs::wide_store).  Pass i: every wave parks block row i of its
-    // sub-tile (32 rows x WN columns) at [wave row * 32 + row][wn0 + col]; then all threads walk the
-    // (BM / WM) * 32 staged rows in 16-byte chunks, one full tile row per wave instruction.
-    constexpr int WAVES_M = BM / WM;
-    constexpr int RT = WAVES_M * 32;            // staged rows per pass
-    constexpr int C4 = BN / 4;                  // 16-byte chunks per staged row
-    constexpr int NT_ = WAVES_M * WAVES_N * 64;
-    static_assert(RD || RT * BN <= 2 * BK * (SA + SB), "the staged rows fit the operand buffers");
-    static_assert(!RD || (BM == 256 && BN == 256 && WAVES_M * WAVES_N == 8), "row products ride on the 256 x 256 tile");
-    constexpr int PS = RD ? BN + 4 : BN;        // row stride of the parked rows (padded: the row product reads them as MFMA fragments)
-    float* w2s = lds + 2 * RT * PS;             // RD: W2[n_blk .. n_blk + BN) x 16 as [k / 4][16][k % 4], staged before the k loop
-    const int wmi = wave / WAVES_N;
-    static_assert(NT_ % C4 == 0, "a thread keeps its column chunk");
-    constexpr int NQ = (RT * C4 + NT_ - 1) / NT_;  // chunks per thread and pass
-    const int c4 = tid % C4;
-    const long n = n_blk + c4 * 4;
-    f32x4 b4 = {0.f, 0.f, 0.f, 0.f};
-    if (has_bias) b4 = *reinterpret_cast<const f32x4*>(a.bias + n);
-    float rd_half[4] = {0.f, 0.f, 0.f, 0.f};  // RD: this wave's half of the row product of the previous pass
-    float* rdx = w2s + BN * 16;                 // RD: [4 blocks][64 lanes][4]: the second column half, waves 4 .. 7 -> 0 .. 3
-    // out2 += partial product of pass `pass` (+ bias from the first N-tile).  Lane l of wave w < 4 holds column l % 16 of
-    // staged rows 16 w + 4 (l / 16) + v.  Float atomics without return — nothing waits for them (a compare-and-swap loop
-    // costs a memory round trip behind the tile's own store burst: +14 us per tile).  gfx950's global_atomic_add_f32
-    // honours the denormal mode (tests/test_gpu_epilogue.py holds a denormal result to the bit).
-    // (the second layer's bias: loaded ONCE per tile here, not in front of the atomics of every pass — waves 0 .. 3 waited
-    // a memory round trip per pass for it and the other four waited for them at the pass's barrier)
-    float bias2 = 0.f;
-    if constexpr (RD) {
-      if (Epi::RD_BIAS >= 0 && n_blk == 0 && wave < 4 && (lane & 15) < Epi::RD_N)
-        bias2 = static_cast<const float*>(a.epi[Epi::RD_BIAS >= 0 ? Epi::RD_BIAS : 0])[lane & 15];
-    }
-    auto rd_send = [&](int pass) {
-      if constexpr (RD) {
-        const int r = lane & 15, g = lane >> 4;
-        if (wave < 4 && r < Epi::RD_N) {
-          typedef float rd4 __attribute__((ext_vector_type(4)));
-          const rd4 other = *reinterpret_cast<const rd4*>(rdx + (wave * 64 + lane) * 4);
-          float* out2 = static_cast<float*>(a.epi[Epi::RD_OUT]);
+  // the accumulator map of this tile (block-uniform): interleaved where run_k_loop's condition holds
+  const bool ail = Interleaved<A_KC, MI>::value && il, bil = Interleaved<B_KC, NI>::value && il;
+  // ---- whole tile, through LDS (GemmArgs::wide_store).  Pass i: every wave parks block row i of its sub-tile (32 rows x WN
+  // columns) at [wave row * 32 + row][wn0 + col]; then all threads walk the (BM / WM) * 32 staged rows in 16-byte chunks,
+  // one full tile row per wave instruction, and store them (+ bias, onto the old values, or through the generated epilogue,
+  // whose predicate bits leave as packed words where they can).  A row product (RowProduct) runs on the rows of pass i while
+  // pass i + 1 parks: its passes alternate between two padded stages.
+  // (This pass stays in the block body: as a function of its own — same text, every call inlined — the compiler allocated the
+  // 256 x 256 kernels more than their 256 registers, 300 - 1100 bytes of scratch, and spilled in the 128 x 128 ones.)
+  // It is instantiated only where the staged rows fit the operand buffers: true for every tile the library builds.
+  if constexpr (RD || (BM / WM) * 32 * BN <= 2 * BK * (SA + SB)) {
+    if (a.wide_store && (!EDGE || whole_tile)) {  // block-uniform
+      constexpr int WAVES_M = BM / WM, NT_ = WAVES * 64;
+      static_assert(!RD || (BM == 256 && BN == 256 && WAVES_M * WAVES_N == 8), "row products ride on the 256 x 256 tile");
+      constexpr int RT = WAVES_M * 32;  // staged rows per pass
+      constexpr int C4 = BN / 4;        // 16-byte chunks per staged row
+      constexpr int PS = RD ? BN + 4 : BN;  // row stride of the parked rows (padded: the row product reads them as MFMA fragments)
+      static_assert(NT_ % C4 == 0, "a thread keeps its column chunk");
+      constexpr int NQ = (RT * C4 + NT_ - 1) / NT_;  // chunks per thread and pass
+      const int wmi = wave / WAVES_N;
+      const int c4 = tid % C4;
+      const long n = n_blk + c4 * 4;
+      f32x4 b4 = {0.f, 0.f, 0.f, 0.f};
+      if (has_bias) b4 = *reinterpret_cast<const f32x4*>(a.bias + n);
+      RowProduct<Epi, BM, BN, WM, MI> rd;
+      if constexpr (RD) rd.init(a, lds, n_blk, wave, lane);
 #pragma unroll
-          for (int v = 0; v < 4; ++v) {
-            const int srow = wave * 16 + 4 * g + v;
-            const long m = m_blk + (long)(srow >> 5) * WM + sub_index<MI>(ail, pass, srow & 31);
-            atomicAdd(out2 + m * (long)Epi::RD_LDO + r, (rd_half[v] + other[v]) + bias2);
-          }
+      for (int i = 0; i < MI; ++i) {
+        float* park = lds + (RD ? (i & 1) * RT * PS : 0);
+        park_block_row<NI, PS>(park, acc[i], bil, wmi * 32, wn0, lane);
+        __syncthreads();
+        if constexpr (RD) {
+          if (i > 0) rd.send(a, i - 1, m_blk, ail, wave, lane);
         }
-      }
-    };
+        // A thread's chunks of one pass: q = q0 + tid, q0 a multiple of the block size — the same 16-byte column chunk c4 of
+        // NQ different rows (C4 divides the block size), so the bias chunk is loaded once.  The loads of all NQ chunks (a
+        // generated epilogue's operands, an accumulating launch's old values) are issued BEFORE the first store: loads and
+        // stores share vmcnt on gfx9, so a load issued behind a store makes its consumer wait for that store as well —
+        // chunk by chunk (load, wait, store, load, ...) a tile's stores went out one store latency apart.
+        auto index_of = [&](int c) {  // flat output index of this thread's chunk c of pass i
+          const int row = (c * NT_ + tid) / C4;
+          return (m_blk + (long)(row >> 5) * WM + sub_index<MI>(ail, i, row & 31)) * ldo + n;
+        };
+        // (the 256 x 256 tile has the registers to hold a whole pass; tiles that run four waves per SIMD batch four chunks)
+        constexpr int GROUP = BM * BN >= 256 * 256 ? NQ : (NQ < 4 ? NQ : 4);
+        const bool packed = C4 % 8 == 0 && (ldo & 31) == 0;  // predicate bits: eight neighbouring lanes hold one 32-bit word
 #pragma unroll
-    for (int i = 0; i < MI; ++i) {
-      // (RD: passes alternate between two stages, so the row product of pass i reads its rows while pass i + 1 parks)
-      float* park = lds + (RD ? (i & 1) * RT * PS : 0);
-      if (bil) {  // the lane's NI columns are adjacent: one 8- / 16-byte LDS write per row
+        for (int g0 = 0; g0 < NQ; g0 += GROUP) {
+          f32x4 x4[GROUP][Epi::NX];
+          f32x4 old[GROUP];
+          unsigned nibs[GROUP];  // predicate bits of the group's chunks (packed words: folded behind the loop, all chunks together)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          typedef float vecN __attribute__((ext_vector_type(NI)));
-          vecN v;
+          for (int c = 0; c < GROUP; ++c) nibs[c] = 0;
 #pragma unroll
-          for (int j = 0; j < NI; ++j) v[j] = acc[i][j][r];
-          *reinterpret_cast<vecN*>(&park[(wmi * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * PS + wn0 + NI * (lane & 31)]) = v;
-        }
-      } else {
-#pragma unroll
-        for (int j = 0; j < NI; ++j)
-#pragma unroll
-          for (int r = 0; r < 16; ++r)
-            park[(wmi * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * PS + wn0 + j * 32 + (lane & 31)] = acc[i][j][r];
-      }
-      __syncthreads();
-      if (RD && i > 0) rd_send(i - 1);
-      // A thread's chunks of one pass: q = q0 + tid, q0 a multiple of the block size — the same 16-byte column chunk c4 of
-      // NQ different rows (C4 divides the block size), so the bias chunk is loaded once.  The loads of all NQ chunks (a
-      // generated epilogue's operands, an accumulating launch's old values) are issued BEFORE the first store: loads and
-      // stores share vmcnt on gfx9, so a load issued behind a store makes its consumer wait for that store as well —
-      // chunk by chunk (load, wait, store, load, ...) a tile's stores went out one store latency apart.
-      auto index_of = [&](int c) {  // flat output index of this thread's chunk c of pass i
-        const int row = (c * NT_ + tid) / C4;
-        return (m_blk + (long)(row >> 5) * WM + sub_index<MI>(ail, i, row & 31)) * ldo + n;
-      };
-      // (the 256 x 256 tile has the registers to hold a whole pass; tiles that run four waves per SIMD batch four chunks)
-      constexpr int GROUP = BM * BN >= 256 * 256 ? NQ : (NQ < 4 ? NQ : 4);
-      const bool packed = C4 % 8 == 0 && (ldo & 31) == 0;  // predicate bits: eight neighbouring lanes hold one 32-bit word
-#pragma unroll
-      for (int g0 = 0; g0 < NQ; g0 += GROUP) {
-      f32x4 x4[GROUP][Epi::NX];
-      f32x4 old[GROUP];
-      unsigned nibs[GROUP];   // predicate bits of the group's chunks (packed words: folded behind the loop, all chunks together)
-#pragma unroll
-      for (int c = 0; c < GROUP; ++c) nibs[c] = 0;
-#pragma unroll
-      for (int c = g0; c < g0 + GROUP && c < NQ; ++c) {
-        if ((RT * C4) % NT_ != 0 && c * NT_ + tid >= RT * C4) break;
-        if (Epi::ACTIVE) Epi::prefetch4(a, index_of(c), x4[c - g0]);
-        else if (accumulate) old[c - g0] = *reinterpret_cast<const f32x4*>(out + index_of(c));
-      }
-#pragma unroll
-      for (int c = g0; c < g0 + GROUP && c < NQ; ++c) {
-        if ((RT * C4) % NT_ != 0 && c * NT_ + tid >= RT * C4) break;
-        const int row = (c * NT_ + tid) / C4;
-        const long idx = index_of(c);
-        f32x4 v = *reinterpret_cast<const f32x4*>(&park[row * PS + c4 * 4]);
-        if (Epi::ACTIVE) {
-          f32x4 res;
-          unsigned nibble = 0;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            float x[Epi::NX];
-#pragma unroll
-            for (int o = 0; o < Epi::NX; ++o) x[o] = x4[c - g0][o][e];
-            v[e] = v[e] + b4[e];
-            res[e] = Epi::compute(a, idx + e, v[e], x);
-            if constexpr (Epi::PRED >= 0) nibble |= (Epi::predicate(v[e]) ? 1u : 0u) << e;
+          for (int c = g0; c < g0 + GROUP && c < NQ; ++c) {
+            if ((RT * C4) % NT_ != 0 && c * NT_ + tid >= RT * C4) break;
+            if (Epi::ACTIVE) Epi::prefetch4(a, index_of(c), x4[c - g0]);
+            else if (accumulate) old[c - g0] = *reinterpret_cast<const f32x4*>(out + index_of(c));
           }
-          if constexpr (Epi::PRED >= 0) {
-            unsigned* bits = static_cast<unsigned*>(a.epi[Epi::PRED]);
-            if (packed) {
-              nibs[c - g0] = nibble;   // (folded below)
-            } else if (nibble) {
-              atomicOr(bits + (idx >> 5), nibble << (idx & 31));  // (idx is a multiple of 4: a nibble never straddles words)
+#pragma unroll
+          for (int c = g0; c < g0 + GROUP && c < NQ; ++c) {
+            if ((RT * C4) % NT_ != 0 && c * NT_ + tid >= RT * C4) break;
+            const int row = (c * NT_ + tid) / C4;
+            const long idx = index_of(c);
+            f32x4 v = *reinterpret_cast<const f32x4*>(&park[row * PS + c4 * 4]);
+            if (Epi::ACTIVE) {
+              f32x4 res;
+              unsigned nibble = 0;
+#pragma unroll
+              for (int e = 0; e < 4; ++e) {
+                float x[Epi::NX];
+#pragma unroll
+                for (int o = 0; o < Epi::NX; ++o) x[o] = x4[c - g0][o][e];
+                v[e] = v[e] + b4[e];
+                res[e] = Epi::compute(a, idx + e, v[e], x);
+                if constexpr (Epi::PRED >= 0) nibble |= (Epi::predicate(v[e]) ? 1u : 0u) << e;
+              }
+              if constexpr (Epi::PRED >= 0) {
+                if (packed) {
+                  nibs[c - g0] = nibble;  // (folded below)
+                } else if (nibble) {  // (idx is a multiple of 4: a nibble never straddles words)
+                  atomicOr(static_cast<unsigned*>(a.epi[Epi::PRED]) + (idx >> 5), nibble << (idx & 31));
+                }
+              }
+              if constexpr (RD) *reinterpret_cast<f32x4*>(&park[row * PS + c4 * 4]) = res;  // (this thread's own chunk)
+              if (a.nt_store) {
+                if (Epi::STORE_C) __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(a.C + idx));
+                __builtin_nontemporal_store(res, reinterpret_cast<f32x4*>(static_cast<float*>(a.epi[Epi::OUT]) + idx));
+              } else {
+                if (Epi::STORE_C) *reinterpret_cast<f32x4*>(a.C + idx) = v;
+                *reinterpret_cast<f32x4*>(static_cast<float*>(a.epi[Epi::OUT]) + idx) = res;
+              }
+            } else {
+              f32x4* p = reinterpret_cast<f32x4*>(out + idx);
+              if (accumulate) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = (old[c - g0][e] + v[e]) + b4[e];
+              } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = v[e] + b4[e];
+              }
+              if (a.nt_store) __builtin_nontemporal_store(v, p);
+              else *p = v;
             }
           }
-          if constexpr (RD) *reinterpret_cast<f32x4*>(&park[row * PS + c4 * 4]) = res;  // (this thread's own chunk)
-          if (a.nt_store) {
-            if (Epi::STORE_C) __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(a.C + idx));
-            __builtin_nontemporal_store(res, reinterpret_cast<f32x4*>(static_cast<float*>(a.epi[Epi::OUT]) + idx));
-          } else {
-            if (Epi::STORE_C) *reinterpret_cast<f32x4*>(a.C + idx) = v;
-            *reinterpret_cast<f32x4*>(static_cast<float*>(a.epi[Epi::OUT]) + idx) = res;
-          }
-        } else {
-          f32x4* p = reinterpret_cast<f32x4*>(out + idx);
-          if (accumulate) {
+          if constexpr (Epi::ACTIVE && Epi::PRED >= 0) {
+            if (packed) {  // (whole tiles: n_blk and the rows' starts are multiples of 32) one lane of eight stores the word
+              unsigned* bits = static_cast<unsigned*>(a.epi[Epi::PRED >= 0 ? Epi::PRED : 0]);
+              fold_pred_nibbles(nibs, tid);
+              if ((tid & 7) == 0) {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = (old[c - g0][e] + v[e]) + b4[e];
-          } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = v[e] + b4[e];
-          }
-          if (a.nt_store) __builtin_nontemporal_store(v, p);
-          else *p = v;
-        }
-      }
-      if constexpr (Epi::ACTIVE && Epi::PRED >= 0) {
-        if (packed) {
-          // (whole tiles: n_blk and the rows' starts are multiples of 32) eight neighbouring lanes hold the eight nibbles of a
-          // 32-bit word: three butterfly steps, one lane stores the word.  The steps run over ALL chunks of the group together
-          // (round 6: chunk by chunk, each behind its guarded store, every one of the 3 x 8 crossbar shuffles of a pass
-          // waited out its own latency — the pattern EG_ROW_TRACE found in the row groups).
-          unsigned* bits = static_cast<unsigned*>(a.epi[Epi::PRED >= 0 ? Epi::PRED : 0]);
-          unsigned w[GROUP];
-#pragma unroll
-          for (int c = 0; c < GROUP; ++c) w[c] = nibs[c] << (4 * (tid & 7));
-#pragma unroll
-          for (int step = 1; step <= 4; step <<= 1)
-#pragma unroll
-            for (int c = 0; c < GROUP; ++c) w[c] |= __shfl_xor(w[c], step, 64);
-          if ((tid & 7) == 0) {
-#pragma unroll
-            for (int c = g0; c < g0 + GROUP && c < NQ; ++c) {
-              if ((RT * C4) % NT_ != 0 && c * NT_ + tid >= RT * C4) break;
-              bits[index_of(c) >> 5] = w[c - g0];
+                for (int c = g0; c < g0 + GROUP && c < NQ; ++c) {
+                  if ((RT * C4) % NT_ != 0 && c * NT_ + tid >= RT * C4) break;
+                  bits[index_of(c) >> 5] = nibs[c - g0];
+                }
+              }
             }
           }
         }
+        __syncthreads();
+        if constexpr (RD) rd.multiply(park, wave, lane);
       }
-      }
-      __syncthreads();
       if constexpr (RD) {
-        // Row product of the RT = 64 rows of this pass: wave w takes the 16 rows of block w % 4 and the column half w / 4,
-        // v_mfma_f32_16x16x4_f32 over 16-wide windows — lane (r = l % 16, g = l / 16) reads res[row r][16 s + 4 g .. + 3]
-        // and W2[16 s + 4 g .. + 3][column r] as one ds_read_b128 each (stride BN + 4: 4 r + g covers the 64 banks once);
-        // MFMA j of a window multiplies k = 16 s + 4 g + j on both sides.  Two accumulators, windows alternating.
-        // Waves 4 .. 7 hand their half over through LDS (rdx); waves 0 .. 3 pick it up behind the NEXT barrier every wave
-        // passes anyway (the one that publishes the next pass's parked rows) and send the sums off there.
-        typedef float rd4 __attribute__((ext_vector_type(4)));
-        const int r = lane & 15, g = lane >> 4, mb = wave & 3, kh = wave >> 2;
-        const float* arow = park + (mb * 16 + r) * PS + 4 * g + kh * (BN / 2);
-        const float* brow = w2s + ((g * 16 + r) << 2) + kh * (BN / 2) * 16;
-        // (four accumulators — two windows x even / odd k of a window: a chain of 8 dependent MFMAs each instead of 16; the
-        // instruction's result is not ready for the next one of its chain when that is the next but one in line)
-        rd4 d0 = {0.f, 0.f, 0.f, 0.f}, d1 = {0.f, 0.f, 0.f, 0.f}, d2 = {0.f, 0.f, 0.f, 0.f}, d3 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int s2 = 0; s2 < BN / 32; s2 += 2) {
-          const rd4 a0 = *reinterpret_cast<const rd4*>(arow + 16 * s2);
-          const rd4 b0 = *reinterpret_cast<const rd4*>(brow + 256 * s2);
-          const rd4 a1 = *reinterpret_cast<const rd4*>(arow + 16 * s2 + 16);
-          const rd4 b1 = *reinterpret_cast<const rd4*>(brow + 256 * s2 + 256);
-#pragma unroll
-          for (int j = 0; j < 4; j += 2) {
-            d0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[j], b0[j], d0, 0, 0, 0);
-            d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[j], b1[j], d1, 0, 0, 0);
-            d2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[j + 1], b0[j + 1], d2, 0, 0, 0);
-            d3 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[j + 1], b1[j + 1], d3, 0, 0, 0);
-          }
-        }
-#pragma unroll
-        for (int v = 0; v < 4; ++v) rd_half[v] = (d0[v] + d2[v]) + (d1[v] + d3[v]);
-        if (kh == 1) *reinterpret_cast<rd4*>(rdx + (mb * 64 + lane) * 4) = rd4{rd_half[0], rd_half[1], rd_half[2], rd_half[3]};
+        __syncthreads();
+        rd.send(a, MI - 1, m_blk, ail, wave, lane);
       }
+      trace_stamp<WAVES>(a, wave, lane, 3);
+      return;
     }
-    if constexpr (RD) {
-      __syncthreads();
-      rd_send(MI - 1);
-    }
-    if (a.trace) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    stamp(3);
-    return;
   }
   if constexpr (RD) __builtin_trap();  // the host launches a row product only where every tile takes the wide-store pass
+  // ---- per-lane store: ragged tiles, unaligned outputs, EG_GEMM_NO_WIDE_STORE=1.  Four copies of the loop (guarded x
+  // accumulate) stay written out: as one body instantiated four times the compiler shared the row addresses between the
+  // copies and held them in registers — the ragged 128 x 128 kernels went from 112 to 128 registers and spilled.
 #pragma unroll
   for (int i = 0; i < MI; ++i) {
 #pragma unroll
@@ -1480,7 +1548,7 @@ __device__ __forceinline__ void gemm_block_at(const GemmArgs& a, const int block
       const bool n_ok = !EDGE || n < a.N;
       float bias = 0.f;
       if (has_bias && n_ok) bias = a.bias[n];
-      // row of register r: m_base + RS * ((r & 3) + 8 * (r >> 2))
+      // row of register r: m_base + RS * acc_reg_row(r)
       const int RS = ail ? MI : 1;
       const long m_base = m_blk + wm0 + (ail ? i + MI * 4 * (lane >> 5) : i * 32 + 4 * (lane >> 5));
       float* col = out + n;
@@ -1488,14 +1556,14 @@ __device__ __forceinline__ void gemm_block_at(const GemmArgs& a, const int block
         float x[16][Epi::NX];
         if (!EDGE || whole_tile) {  // whole tile inside: branch-free, loads batched
 #pragma unroll
-          for (int r = 0; r < 16; ++r) Epi::prefetch(a, (m_base + RS * ((r & 3) + 8 * (r >> 2))) * ldo + n, x[r]);
+          for (int r = 0; r < 16; ++r) Epi::prefetch(a, (m_base + RS * acc_reg_row(r)) * ldo + n, x[r]);
 #pragma unroll
           for (int r = 0; r < 16; ++r)
-            epi_apply<Epi>(a, (m_base + RS * ((r & 3) + 8 * (r >> 2))) * ldo + n, acc[i][j][r] + bias, x[r]);
+            epi_apply<Epi>(a, (m_base + RS * acc_reg_row(r)) * ldo + n, acc[i][j][r] + bias, x[r]);
         } else {
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
-            const long m = m_base + RS * ((r & 3) + 8 * (r >> 2));
+            const long m = m_base + RS * acc_reg_row(r);
             if (m >= a.M || !n_ok) continue;
             Epi::prefetch(a, m * ldo + n, x[r]);
             epi_apply<Epi>(a, m * ldo + n, acc[i][j][r] + bias, x[r]);
@@ -1505,32 +1573,31 @@ __device__ __forceinline__ void gemm_block_at(const GemmArgs& a, const int block
         if (accumulate) {
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
-            const long m = m_base + RS * ((r & 3) + 8 * (r >> 2));
+            const long m = m_base + RS * acc_reg_row(r);
             col[m * ldo] = (col[m * ldo] + acc[i][j][r]) + bias;
           }
         } else {
 #pragma unroll
-          for (int r = 0; r < 16; ++r) col[(m_base + RS * ((r & 3) + 8 * (r >> 2))) * ldo] = acc[i][j][r] + bias;
+          for (int r = 0; r < 16; ++r) col[(m_base + RS * acc_reg_row(r)) * ldo] = acc[i][j][r] + bias;
         }
       } else if (accumulate) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const long m = m_base + RS * ((r & 3) + 8 * (r >> 2));
+          const long m = m_base + RS * acc_reg_row(r);
           if (m >= a.M || !n_ok) continue;
           col[m * ldo] = (col[m * ldo] + acc[i][j][r]) + bias;
         }
       } else {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const long m = m_base + RS * ((r & 3) + 8 * (r >> 2));
+          const long m = m_base + RS * acc_reg_row(r);
           if (m >= a.M || !n_ok) continue;
           col[m * ldo] = acc[i][j][r] + bias;
         }
       }
     }
   }
-  if (a.trace) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  stamp(3);
+  trace_stamp<WAVES>(a, wave, lane, 3);
 }
 
 // The block of a launch whose grid is the contraction's work items.  (gemm_block_at: the batched kernel of gemm_batched.hip
@@ -1584,13 +1651,11 @@ __global__ __launch_bounds__(256, 4) void gemm_streamk_kernel(GemmArgs a) {
   const long tiles = (long)a.tiles_m * a.tiles_n, tiles_dp = (long)rounds * gridDim.x;
   // (blocks in XCD-contiguous order: neighbouring tiles / unit ranges share an L2)
   const long b = xcd_remap(blockIdx.x, gridDim.x);
-  // register r of lane l: row (r & 3) + 8 (r >> 2) + 4 (l >> 5), column l & 31 of the wave's 32 x 32 block
   auto piece = [&](int tile, int k0, int cnt, float* slab) {
     long m_blk, n_blk;
     tile_origin<BM, BN>(tile, a.tiles_m, a.tiles_n, m_blk, n_blk);
     f32x16 acc[1][1];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[0][0][r] = 0.f;
+    zero_acc(acc);
     gemm_mainloop_dma<BM, BN, BK, WM, WN, A_KC, B_KC, 0, false, true, false, 0>(a, lds, acc, m_blk, n_blk, (long)k0 * BK, cnt, tid, wm0, wn0);
     if (slab == nullptr) {
       float* col = a.C + (m_blk + wm0 + 4 * hi) * a.ldc + n_blk + wn0 + i;
@@ -1598,17 +1663,17 @@ __global__ __launch_bounds__(256, 4) void gemm_streamk_kernel(GemmArgs a) {
       if (a.accumulate) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          float* p = col + (long)((r & 3) + 8 * (r >> 2)) * a.ldc;
+          float* p = col + (long)acc_reg_row(r) * a.ldc;
           *p = (*p + acc[0][0][r]) + bias;
         }
       } else {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) col[(long)((r & 3) + 8 * (r >> 2)) * a.ldc] = acc[0][0][r] + bias;
+        for (int r = 0; r < 16; ++r) col[(long)acc_reg_row(r) * a.ldc] = acc[0][0][r] + bias;
       }
     } else {
       float* dst = slab + (wm0 + 4 * hi) * BN + wn0 + i;
 #pragma unroll
-      for (int r = 0; r < 16; ++r) dst[((r & 3) + 8 * (r >> 2)) * BN] = acc[0][0][r];
+      for (int r = 0; r < 16; ++r) dst[acc_reg_row(r) * BN] = acc[0][0][r];
     }
   };
   for (int r = 0; r < rounds; ++r) piece((int)((long)r * gridDim.x + b), 0, nk, nullptr);
@@ -1640,13 +1705,7 @@ static __global__ __launch_bounds__(256) void gemm_streamk_fixup_kernel(const fl
   if (b_first == b_last) return;   // one block owned the whole tile and stored it
   const int tile = (int)(tiles_dp + t);
   long m_blk, n_blk;
-  {
-    constexpr int GROUP = 8;
-    const int per_group = GROUP * tiles_n, group = tile / per_group, first_m = group * GROUP;
-    const int gsize = tiles_m - first_m < GROUP ? tiles_m - first_m : GROUP, in_group = tile % per_group;
-    m_blk = (long)(first_m + in_group % gsize) * BM;
-    n_blk = (long)(in_group / gsize) * BN;
-  }
+  tile_origin<BM, BN>(tile, tiles_m, tiles_n, m_blk, n_blk);
   typedef float v4 __attribute__((ext_vector_type(4)));
   for (int e = threadIdx.x; e < BM * BN / 4; e += 256) {
     v4 s = {0.f, 0.f, 0.f, 0.f};
@@ -1754,11 +1813,9 @@ __device__ __forceinline__ void gemm_narrow_k_block(const GemmArgs& a) {
       if constexpr (Epi::PRED >= 0) {
         unsigned* bits = static_cast<unsigned*>(a.epi[Epi::PRED >= 0 ? Epi::PRED : 0]);
         if (packed) {
-          unsigned word = nibble << (4 * (tid & 7));
-          word |= __shfl_xor(word, 1, 64);
-          word |= __shfl_xor(word, 2, 64);
-          word |= __shfl_xor(word, 4, 64);
-          if ((tid & 7) == 0) bits[idx >> 5] = word;
+          unsigned word[1] = {nibble};
+          fold_pred_nibbles(word, tid);
+          if ((tid & 7) == 0) bits[idx >> 5] = word[0];
         } else if (nibble) {
           atomicOr(bits + (idx >> 5), nibble << (idx & 31));
         }

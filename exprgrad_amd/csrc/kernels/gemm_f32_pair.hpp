@@ -69,7 +69,6 @@ gemm_pair_kernel(GemmArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int sub = wave / KW, kw = wave % KW;
   const int wm0 = (sub / WAVES_N) * WM, wn0 = (sub % WAVES_N) * WN;
-  const int i = lane & 31, hi = lane >> 5;
   if (a.prio) __builtin_amdgcn_s_setprio(3);
 
   long m_blk, n_blk;
@@ -78,12 +77,7 @@ gemm_pair_kernel(GemmArgs a) {
   const int nk = (int)(a.K / BK);                         // whole k-tiles: the loop
 
   f32x16 acc[MI][NI];
-#pragma unroll
-  for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
+  zero_acc(acc);
 
   DmaA da;
   DmaB db;
@@ -94,54 +88,8 @@ gemm_pair_kernel(GemmArgs a) {
     da.issue(a, a.A, a.lda, m_blk, (long)kt * BK, s, wave, lane, a.a_rows, a.K);
     db.issue(a, a.B, a.ldb, n_blk, (long)kt * BK, s + BK * BM, wave, lane, a.N, a.K);
   };
-  // fragments of k-group pp (8 k) of the tile at As, as in gemm_mainloop_dma: av[mi][j] / bv[ni][j] = this lane's A / B
-  // value of block mi / ni for MFMA k-step j (k = 8 pp + j in lanes 0 - 31, 8 pp + 4 + j in lanes 32 - 63)
-  auto fragments = [&](const float* As, int pp, float (&av)[MI][4], float (&bv)[NI][4]) {
-    const float* Bs = As + BK * BM;
-    if constexpr (AIL) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        typedef float vecA __attribute__((ext_vector_type(MI)));
-        const vecA v = *reinterpret_cast<const vecA*>(As + (8 * pp + j + 4 * hi) * BM + wm0 + MI * i);
-#pragma unroll
-        for (int mi = 0; mi < MI; ++mi) av[mi][j] = v[mi];
-      }
-    } else {
-#pragma unroll
-      for (int mi = 0; mi < MI; ++mi) {
-        const int row = wm0 + mi * 32 + i;
-        if constexpr (A_KC) {
-          const f32x4 v = *reinterpret_cast<const f32x4*>(As + row * BK + (((2 * pp + hi) ^ DmaA::swizzle(row)) << 2));
-#pragma unroll
-          for (int j = 0; j < 4; ++j) av[mi][j] = v[j];
-        } else {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) av[mi][j] = As[(8 * pp + j + 4 * hi) * BM + row];
-        }
-      }
-    }
-    if constexpr (BIL) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        typedef float vecB __attribute__((ext_vector_type(NI)));
-        const vecB v = *reinterpret_cast<const vecB*>(Bs + (8 * pp + j + 4 * hi) * BN + wn0 + NI * i);
-#pragma unroll
-        for (int ni = 0; ni < NI; ++ni) bv[ni][j] = v[ni];
-      }
-    } else {
-#pragma unroll
-      for (int ni = 0; ni < NI; ++ni) {
-        const int col = wn0 + ni * 32 + i;
-        if constexpr (B_KC) {
-          const f32x4 v = *reinterpret_cast<const f32x4*>(Bs + col * BK + (((2 * pp + hi) ^ DmaB::swizzle(col)) << 2));
-#pragma unroll
-          for (int j = 0; j < 4; ++j) bv[ni][j] = v[j];
-        } else {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) bv[ni][j] = Bs[(8 * pp + j + 4 * hi) * BN + col];
-        }
-      }
-    }
+  auto fragments = [&](const float* As, int pp, float (&av)[MI][4], float (&bv)[NI][4]) {  // k-group pp of the tile at As
+    read_fragments<BM, BN, BK, MI, NI, A_KC, B_KC, AIL, BIL>(As, pp, wm0, wn0, lane, av, bv);
   };
   auto multiply = [&](const float (&av)[MI][4], const float (&bv)[NI][4]) {
 #pragma unroll
@@ -228,15 +176,7 @@ gemm_pair_kernel(GemmArgs a) {
   if (EDGE && k_tail != 0) {   // (block-uniform) the last, partial k-tile: landed long ago (prologue)
     float* At = lds + S * BUF;
     __syncthreads();   // (K < BK: nothing has waited for the tile yet)
-    const int width = BK - k_tail;
-    for (int e = tid; e < BM * width; e += NT) {
-      if (A_KC) {
-        const int r = e / width, k = k_tail + e % width;
-        At[r * BK + (((k >> 2) ^ DmaA::swizzle(r)) << 2) + (k & 3)] = 0.f;
-      } else {
-        At[k_tail * BM + e] = 0.f;
-      }
-    }
+    zero_k_tail<BM, BK, NT, A_KC>(At, k_tail, tid);
     __syncthreads();
 #pragma unroll
     for (int g = 0; g < GW; ++g) {
@@ -264,21 +204,7 @@ gemm_pair_kernel(GemmArgs a) {
 #pragma unroll
   for (int mi = 0; mi < MI; ++mi) {
     if (mi > 0) __syncthreads();
-    if (BIL) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        typedef float vecN __attribute__((ext_vector_type(NI)));
-        vecN v;
-#pragma unroll
-        for (int ni = 0; ni < NI; ++ni) v[ni] = acc[mi][ni][r];
-        *reinterpret_cast<vecN*>(&park[(wmi * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi) * BN + wn0 + NI * i]) = v;
-      }
-    } else {
-#pragma unroll
-      for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) park[(wmi * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi) * BN + wn0 + ni * 32 + i] = acc[mi][ni][r];
-    }
+    park_block_row<NI, BN>(park, acc[mi], BIL, wmi * 32, wn0, lane);
     __syncthreads();
     f32x4 old[NQ];
     long idx[NQ];

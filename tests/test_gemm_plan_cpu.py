@@ -54,3 +54,29 @@ def test_table_covers_every_route_and_both_verdicts():
     assert verdicts == {0, 1}
     forced = {c["switches"].split("=")[0] for c in cases}
     assert {"no_pair", "no_t96", "no_streamk", "no_xrow", "no_bk32", "force_tile"} <= forced
+
+
+def test_wide_and_direct_store_cases_differ_in_the_store_alone(tmp_path):
+    """tests/test_gpu_ops.py::test_wide_and_direct_stores_agree_bit_for_bit compares a run with EG_GEMM_NO_WIDE_STORE=1 to one
+    without, bit for bit.  That only says something about the two stores while both runs launch the same kernel: for every
+    case the two plans must agree in every field — route, tile, k-slices, second pass — except `wide_store`, 1 and 0, and
+    be the plan the case was chosen for."""
+    from wide_store_cases import CASES, SWITCHES, case_id
+    assert set(SWITCHES) == {"EG_GEMM_NO_PAIR", "EG_GEMM_NO_T96", "EG_GEMM_NO_STREAMK"}
+    lines = []
+    for M, N, K, layout, tile, _ in CASES:
+        ta, tb = int(layout[0] == "t"), int(layout[1] == "t")
+        for direct in (False, True):
+            switches = "no_pair,no_t96,no_streamk" + (",force_tile=%dx%d" % tile if tile else "") + (",no_wide_store" if direct else "")
+            lines.append(dict(mode="exact", M=M, N=N, K=K, ta=ta, tb=tb, lda=M if ta else K, ldb=K if tb else N, ldc=N, a=1, b=1, c=1, bias=1,
+                              vec=0, switches=switches))
+    plans = _plans(tmp_path, lines)
+    for n, case in enumerate(CASES):
+        wide, direct = plans[2 * n], plans[2 * n + 1]
+        assert (wide["wide_store"], direct["wide_store"]) == ("1", "0"), case_id(case)
+        assert {k: v for k, v in wide.items() if k != "wide_store"} == {k: v for k, v in direct.items() if k != "wide_store"}, case_id(case)
+        expect = dict(case[5], route=case[5].get("route", "generic"))
+        if case[4]:
+            expect.update(bm=case[4][0], bn=case[4][1])
+        for k, want in expect.items():
+            assert wide[k] == str(want), (case_id(case), k, wide[k], want)

@@ -11,6 +11,7 @@ import pytest
 import exprgrad_amd as eg
 from exprgrad_amd import ops
 from conftest import TOL, rel_err
+from wide_store_cases import CASES as WIDE_STORE_CASES, SWITCHES as WIDE_STORE_SWITCHES, case_id as wide_store_case_id
 
 pytestmark = pytest.mark.gpu
 
@@ -566,3 +567,42 @@ def test_stream_k_blocks_against_the_exact_product_and_one_block_per_tile(gpu_ct
     dc.write(np.full((M, N), np.nan, dtype=np.float32))         # a chunk the blocks or the fix-up skipped would show
     ops.sgemm(gpu_ctx, M, N, K, da, a.shape[1], db, b.shape[1], dc, N, trans_a=ta, trans_b=tb)
     assert rel_err(dc.read(), exact) <= TOL
+
+
+@pytest.mark.parametrize("case", WIDE_STORE_CASES, ids=wide_store_case_id)
+def test_wide_and_direct_stores_agree_bit_for_bit(gpu_ctx, monkeypatch, case):
+    """gemm_f32_mfma.hpp: a whole tile leaves through LDS as whole rows (the wide-store pass) or lane by lane (the per-lane store, all
+    of it under EG_GEMM_NO_WIDE_STORE=1).  Both compute acc + bias, or (old + acc) + bias, per element in the same order, so the
+    two runs must agree to the bit: plainly and onto a seeded C, on the four-wave tile kernels (tests/wide_store_cases.py;
+    tests/test_gemm_plan_cpu.py holds that the two plans differ in `wide_store` alone), and each must meet the float64 product
+    within the bound of test_random_contraction_shapes."""
+    M, N, K, layout, tile, _ = case
+    ta, tb = layout[0] == "t", layout[1] == "t"
+    rng = np.random.default_rng(M + N + K)
+    a = (rng.random((K, M) if ta else (M, K), dtype=np.float32) - 0.5).astype(np.float32)
+    b = (rng.random((N, K) if tb else (K, N), dtype=np.float32) - 0.5).astype(np.float32)
+    bias = (rng.random((N,), dtype=np.float32) - 0.5).astype(np.float32)
+    base = rng.random((M, N), dtype=np.float32)
+    da, db, dbias = dev(gpu_ctx, a), dev(gpu_ctx, b), dev(gpu_ctx, bias)
+    dc = gpu_ctx.allocTensor((M, N))
+    for k, v in WIDE_STORE_SWITCHES.items():
+        monkeypatch.setenv(k, v)
+    if tile:
+        monkeypatch.setenv("EG_GEMM_FORCE_TILE", "%d,%d" % tile)
+    outs = {}
+    for direct in (False, True):
+        if direct:
+            monkeypatch.setenv("EG_GEMM_NO_WIDE_STORE", "1")
+        for acc in (False, True):
+            dc.write(base if acc else np.full((M, N), np.nan, dtype=np.float32))
+            ops.sgemm(gpu_ctx, M, N, K, da, a.shape[1], db, b.shape[1], dc, N, trans_a=ta, trans_b=tb, accumulate=acc, bias=dbias)
+            outs[direct, acc] = dc.read()
+    exact = (a.T if ta else a).astype(np.float64) @ (b.T if tb else b).astype(np.float64) + bias
+    for acc in (False, True):
+        want = exact + base if acc else exact
+        scale = max(np.abs(want).max(), 0.25 * np.sqrt(K) * 0.3)      # every output is a sum of K products of magnitude <= 0.25
+        for direct in (False, True):
+            err = np.abs(outs[direct, acc] - want).max()
+            print(case[:5], "direct" if direct else "wide", "accumulate" if acc else "plain", err / scale)
+            assert err <= TOL * scale, (case[:5], direct, acc)
+        assert np.array_equal(outs[False, acc], outs[True, acc]), (case[:5], acc)
