@@ -136,6 +136,9 @@ _SIGS = {
                          c_void_p, c_i64, c_int, c_void_p]),
     "eg_dgemm_batched": (c_int, [c_void_p, c_int, c_int, c_i64, c_i64, c_i64, c_i64, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_i64,
                                  c_void_p, c_i64, c_i64, c_int, c_void_p]),
+    "eg_conv2_nhwc_f64": (c_int, [c_void_p] + [c_i64] * 7 + [c_void_p, c_void_p, c_void_p, c_int]),
+    "eg_conv2_nhwc_grad_filter_f64": (c_int, [c_void_p] + [c_i64] * 7 + [c_void_p, c_void_p, c_void_p, c_int]),
+    "eg_conv2_nhwc_grad_image_f64": (c_int, [c_void_p] + [c_i64] * 7 + [c_void_p, c_void_p, c_void_p, c_int]),
     "eg_colsum_f64": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_int]),
     "eg_fill_f64": (c_int, [c_void_p, c_i64, c_f64, c_void_p]),
     "eg_fill_uniform_f64": (c_int, [c_void_p, c_i64, c_f64, c_f64, c_void_p, ctypes.c_uint64, c_void_p]),

@@ -146,6 +146,11 @@ int conv2_band_grad_filter_try(eg_ctx* ctx, bool f64, long N, long H, long W, lo
                                int accumulate, bool* launched);
 int conv2_direct_f64_try(eg_ctx* ctx, long N, long H, long W, long C, long F, long FH, long FW, const double* img, const double* flt,
                          double* out, int accumulate, bool* launched);
+// kernels/conv2_f64_mfma.hip: float64 convolutions of any width as an implicit GEMM on the float64 matrix cores.  role: 1 forward
+// (a = image, b = filters), 2 image gradient (a = filters, b = output gradient), 3 filter gradient (a = image, b = output
+// gradient).  Refuses nothing but an empty extent and EG_CONV_NO_MFMA64 (*launched stays false); *kernel: the kernel's name.
+int conv2_f64_mfma(eg_ctx* ctx, int role, long N, long H, long W, long C, long F, long FH, long FW, const double* a, const double* b, double* out,
+                   int accumulate, bool* launched, const char** kernel);
 int conv2_direct_grad_filter_try(eg_ctx* ctx, long N, long H, long W, long C, long F, long FH, long FW, const float* img,
                                  const float* gout, float* gflt, int accumulate, bool* launched);
 // LDS-halo convolution (kernels/conv2_halo.hip); *launched = false when the problem does not suit it.

@@ -287,12 +287,14 @@ const char* eg_model_launch_text(eg_model* m, const char* target) {
         os << "generated(map) kernel " << L.lowered << " -> t" << L.c_tensor;
         if (L.conv_direct64) os << " | " << (L.conv_direct64 == 1 ? "convolution" : L.conv_direct64 == 2 ? "convolution's image gradient" : "convolution's filter gradient")
                                  << ": the float64 matrix-core kernel (eg_conv_band_f64_* / eg_conv_mfma64_*) when the shape suits it";
+        if (L.conv64_kernel) os << " | ran as " << L.conv64_kernel;
         if (L.consumer >= 0) os << " (with its consumer, kernel " << L.consumer << ")";
         os << route_words(L);
         break;
       case StepKind::GenericB:
         os << "generated(split-reduce) kernel " << L.lowered << " -> t" << L.c_tensor << route_words(L) << " tx=" << L.generic->src.tx
            << " chunks=" << L.partial_rows;
+        if (L.conv64_kernel) os << " | ran as " << L.conv64_kernel;
         break;
       case StepKind::RowFused: {
         const PlanRowGroup& pg = *plan.row_groups[L.row_group];

@@ -111,8 +111,10 @@ struct Launch {
   int fold_of = -1;                         // SmallFused: index of that sample group's launch
   // float64 programs: a generated kernel that is a convolution or one of its two gradients (match_conv) first offers itself
   // to the matrix-core kernels over double (kernels/conv2_band.cpp, kernels/conv2_direct.cpp; the conv fields above are
-  // filled in); what those decline runs as the generated kernel.
+  // filled in); what those decline runs on the implicit-GEMM kernel (kernels/conv2_f64_mfma.hip), and as the generated kernel
+  // only under EG_CONV_NO_MFMA64.
   int conv_direct64 = 0;  // 1 forward, 2 image gradient, 3 filter gradient
+  const char* conv64_kernel = nullptr;   // the implicit-GEMM kernel the last run of this launch took (eg_model_launch_text)
 };
 
 // A run of per-sample kernels fused into one generated kernel (rowfuse.hpp), built per plan.

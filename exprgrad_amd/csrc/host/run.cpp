@@ -256,6 +256,11 @@ int run_launch(eg_model* m, TargetState& ts, Plan& plan, Launch& L) {
           rc = eg::conv2_band_grad_filter_try(ctx, true, L.cN, L.cH, L.cW, L.cC, L.cF, L.cFH, L.cFW, dp(L.a_tensor), dp(L.b_tensor), dp(L.c_tensor), L.accumulate, &launched);
         }
         if (rc || launched) return rc;
+        // what band and direct decline: the implicit GEMM on the float64 matrix cores, any shape (the generated kernel under EG_CONV_NO_MFMA64)
+        L.conv64_kernel = nullptr;
+        rc = eg::conv2_f64_mfma(ctx, L.conv_direct64, L.cN, L.cH, L.cW, L.cC, L.cF, L.cFH, L.cFW, dp(L.a_tensor), dp(L.b_tensor), dp(L.c_tensor), L.accumulate,
+                                &launched, &L.conv64_kernel);
+        if (rc || launched) return rc;
       }
       const GenericSource& src = L.generic->src;
       std::vector<void*> args;

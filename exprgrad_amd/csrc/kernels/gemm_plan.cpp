@@ -757,6 +757,69 @@ DgemmBatchedLaunch dgemm_batched_launch(const DgemmBatchedPlan& plan, long batch
   return l;
 }
 
+// ---- float64 convolutions ------------------------------------------------------------------------------------------------
+// Tile: the cheaper of 128 x 128 and 64 x 64 by plan_dgemm's time model (the same loop, the same blocks per CU).
+// GradFilter: the output has few tiles (64 -> 64 channels, 3 x 3: 1 x 9 of 64 x 64), so the P pixels are cut until the
+// launch has CONV64_SLICE_BLOCKS_PER_CU blocks per CU (two eight-wave blocks: four waves per SIMD, dgemm_rate's plateau),
+// but no slice below CONV64_MIN_SLICE_PIXELS pixels: a slab costs 16 bytes per output element to write and read back, the
+// matrix work of about 8 pixels, so a slice of 256 keeps the slabs a few per cent of the launch.
+// NEITHER NUMBER HAS BEEN MEASURED AGAINST ALTERNATIVES: tools/conv64_general_bench.py reports the kernel as planned.
+constexpr long CONV64_SLICE_BLOCKS_PER_CU = 2;
+constexpr long CONV64_MIN_SLICE_PIXELS = 256;
+
+Conv64Plan plan_conv64(const Conv64Problem& p) {
+  Conv64Plan r;
+  const long Ho = p.H - p.FH + 1, Wo = p.W - p.FW + 1;
+  const long P = p.N * Ho * Wo;
+  long terms = 0;
+  switch (p.role) {
+    case Conv64Role::Forward:
+      r.M = P, r.Ncols = p.F, r.K = p.FH * p.FW * p.C, terms = r.K;
+      r.vec_a = p.C % 2 == 0 && p.img_aligned;     // two taps of one pixel: neighbours in memory when they share (dy, dx) or the row run
+      r.vec_b = r.K % 2 == 0 && p.flt_aligned;     // bank rows [F][K]
+      break;
+    case Conv64Role::GradImage:
+      r.M = p.N * p.H * p.W, r.Ncols = p.C, r.K = p.FH * p.FW * p.F, terms = r.K;
+      r.vec_a = p.F % 2 == 0 && p.gout_aligned;    // a pair never straddles two positions, whose border tests may differ
+      r.vec_b = r.K % 2 == 0;                      // the flipped bank lies in the context's scratch, which is aligned
+      r.aux_doubles = p.C * r.K;
+      break;
+    case Conv64Role::GradFilter:
+      r.M = p.F, r.Ncols = p.FH * p.FW * p.C, r.K = P, terms = r.Ncols;
+      r.vec_a = p.F % 2 == 0 && p.gout_aligned;    // gout [P][F], two filters of one pixel
+      r.vec_b = p.C % 2 == 0 && p.img_aligned;
+      break;
+  }
+  if (r.M >= CONV64_MAX_INDEX || r.Ncols >= CONV64_MAX_INDEX || r.K >= CONV64_MAX_INDEX || terms >= CONV64_MAX_INDEX) return r;
+  r.ok = true;
+  const long cus = std::max(p.cus, 1);
+  r.config = dgemm_cost(kDgemmCfgs[0], r.M, r.Ncols, r.K, cus, 1) < dgemm_cost(kDgemmCfgs[2], r.M, r.Ncols, r.K, cus, 1) ? 0 : 2;
+  const DgemmCfg& cfg = kDgemmCfgs[r.config];
+  r.bm = cfg.bm, r.bn = cfg.bn, r.wr = cfg.wr, r.wc = cfg.wc;
+  r.tiles_m = (int)((r.M + r.bm - 1) / r.bm);
+  r.tiles_n = (int)((r.Ncols + r.bn - 1) / r.bn);
+  r.grid_x = (long)r.tiles_m * r.tiles_n;
+  r.remap = dgemm_remap(r.grid_x);
+  r.pixels_per_slice = dgemm_k_unsliced(r.K);
+  if (p.role == Conv64Role::GradFilter && r.grid_x > 0) {
+    long want = (CONV64_SLICE_BLOCKS_PER_CU * cus + r.grid_x - 1) / r.grid_x;
+    want = std::min(want, std::min(r.K / CONV64_MIN_SLICE_PIXELS, 65535L));
+    if (want > 1) {
+      long per = (r.K + want - 1) / want;
+      per = ((per + BK - 1) / BK) * BK;
+      const long slices = (r.K + per - 1) / per;
+      if (slices > 1) {
+        r.slices = (int)slices;
+        r.pixels_per_slice = per;
+        r.workspace_doubles = slices * r.M * r.Ncols;
+        r.reduce = true;
+      }
+    }
+  }
+  r.grid_y = r.slices;
+  return r;
+}
+
 bool exact_single_launch(const GemmPlan& p) {
   return p.route == Route::Bk32 || (p.route == Route::Generic && p.bm == 256 && p.bn == 256 && !p.edge && p.splits <= 1 &&
                                     p.tail_tiles == 0 && p.second == Second::None);

@@ -196,6 +196,46 @@ bool dgemm_batched_runs_as_loop(long M, long N, long K, int cus);
 DgemmBatchedPlan plan_dgemm_batched(const DgemmBatchedProblem& p);
 DgemmBatchedLaunch dgemm_batched_launch(const DgemmBatchedPlan& plan, long batch, long index);
 
+// ---- float64: convolutions of any width (conv2_f64_mfma.hip) --------------------------------------------------------
+// One convolution launch as the planner sees it.  The three roles are contractions over a gathered window operand:
+//   Forward         out [P, F]       = window(img) [P, FH*FW*C] * flt [F, FH*FW*C]^T          P = N*Ho*Wo pixels
+//   GradImage       gimg [N*H*W, C]  = window(gout, zero border) [N*H*W, FH*FW*F] * flipped [C, FH*FW*F]^T
+//   GradFilter      gflt [F, FH*FW*C] = gout [P, F]^T * window(img) [P, FH*FW*C]               summed over the P pixels
+enum class Conv64Role { Forward = 1, GradImage = 2, GradFilter = 3 };
+
+struct Conv64Problem {
+  Conv64Role role = Conv64Role::Forward;
+  long N = 0, H = 0, W = 0, C = 0, F = 0, FH = 1, FW = 1;
+  // 16-byte aligned base pointers: img (Forward, GradFilter), flt (Forward; GradImage reads the flipped copy in the
+  // context's aligned scratch), gout (GradImage, GradFilter)
+  bool img_aligned = true, flt_aligned = true, gout_aligned = true;
+  int cus = 256;
+};
+
+// The kernels index pixels and taps with 32-bit integers (addresses are 64-bit): the host refuses a call whose contraction
+// has 2^31 or more rows, columns or terms.
+constexpr long CONV64_MAX_INDEX = 1L << 31;
+
+struct Conv64Plan {
+  bool ok = false;           // false: an extent of the contraction reaches CONV64_MAX_INDEX (nothing else is filled in)
+  long M = 0, Ncols = 0, K = 0;   // the contraction: M x Ncols outputs, K terms each
+  int config = 2;            // 0: 128 x 128, 2: 64 x 64 (plan_dgemm's table; both eight waves as 2 x 4)
+  int bm = 0, bn = 0, wr = 0, wc = 0;
+  bool vec_a = false, vec_b = false;   // 16-byte loads of the A / B operand (A: window or gout; B: bank or window)
+  int tiles_m = 0, tiles_n = 0;
+  bool remap = false;        // dgemm_remap of the tiles
+  long grid_x = 0, grid_y = 1;
+  // GradFilter: the pixels are cut into `slices` ranges of pixels_per_slice (a multiple of 16; the last may be shorter, none
+  // is empty); each writes a slab of F*FH*FW*C doubles and a second launch folds the slabs in ascending order.
+  int slices = 1;
+  long pixels_per_slice = 0;
+  long workspace_doubles = 0;
+  bool reduce = false;
+  long aux_doubles = 0;      // GradImage: the flipped bank [C][FH][FW][F]
+};
+
+Conv64Plan plan_conv64(const Conv64Problem& p);
+
 // Is the plan ONE launch of the whole-tile 256 x 256 kernel (no k-slices, tail slices or second pass)?  Only such a launch
 // can stand behind the split-bf16 product as its fallback: GemmArgs::run_if gates the tile kernel, not the reduce kernels.
 bool exact_single_launch(const GemmPlan& p);

@@ -65,6 +65,7 @@ const Row kSwitches[] = {
     {"EG_CONV_NO_HALO", "execution", "3 x 3-class convolutions on the implicit-GEMM route"},
     {"EG_CONV_NO_DIRECT", "execution", "few-channel convolutions on the implicit-GEMM route"},
     {"EG_CONV_NO_BAND", "execution", "small-channel convolutions on the routes the band kernels replaced"},
+    {"EG_CONV_NO_MFMA64", "execution", "float64 convolutions that the band and direct kernels decline: generated kernels in a model, refused by the eg_conv2_nhwc*_f64 entry points"},
     {"EG_NO_STAGED_COPY", "execution", "downloads into pageable memory as one runtime copy"},
     {"EG_FIT_NO_DIRECT", "execution", "fit copies every batch into the inputs' staging buffers"},
     {"EG_DP_REAGREE_STEPS", "data-parallel", "steps between two negotiations of the exchange schedule (default 256; 0: only the first)"},

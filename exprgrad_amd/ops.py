@@ -88,3 +88,18 @@ def conv2_nhwc_grad_filter(ctx, N, H, W, C, F, FH, FW, img, gout, gflt, accumula
 def conv2_nhwc_grad_image(ctx, N, H, W, C, F, FH, FW, flt, gout, gimg, accumulate=False):
     """gimg[n,y+dy,x+dx,c] (+)= sum gout[n,y,x,f] * flt[f,dy,dx,c]  (derived from dnn.nim:45-49)."""
     call("eg_conv2_nhwc_grad_image", ctx.handle, N, H, W, C, F, FH, FW, _p(flt), _p(gout), _p(gimg), int(accumulate))
+
+
+def conv2_nhwc_f64(ctx, N, H, W, C, F, FH, FW, img, flt, out, accumulate=False):
+    """conv2_nhwc over float64 tensors, any channel count."""
+    call("eg_conv2_nhwc_f64", ctx.handle, N, H, W, C, F, FH, FW, _p(img), _p(flt), _p(out), int(accumulate))
+
+
+def conv2_nhwc_grad_filter_f64(ctx, N, H, W, C, F, FH, FW, img, gout, gflt, accumulate=False):
+    """conv2_nhwc_grad_filter over float64 tensors."""
+    call("eg_conv2_nhwc_grad_filter_f64", ctx.handle, N, H, W, C, F, FH, FW, _p(img), _p(gout), _p(gflt), int(accumulate))
+
+
+def conv2_nhwc_grad_image_f64(ctx, N, H, W, C, F, FH, FW, flt, gout, gimg, accumulate=False):
+    """conv2_nhwc_grad_image over float64 tensors."""
+    call("eg_conv2_nhwc_grad_image_f64", ctx.handle, N, H, W, C, F, FH, FW, _p(flt), _p(gout), _p(gimg), int(accumulate))

@@ -262,6 +262,27 @@ int eg_dgemm(eg_ctx* ctx, int trans_a, int trans_b, int64_t M, int64_t N, int64_
 int eg_dgemm_batched(eg_ctx* ctx, int trans_a, int trans_b, int64_t batch, int64_t M, int64_t N, int64_t K,
                      const double* A, int64_t lda, int64_t stride_a, const double* B, int64_t ldb, int64_t stride_b,
                      double* C, int64_t ldc, int64_t stride_c, int accumulate, const double* bias);
+/* eg_conv2_nhwc_f64 and its two gradients: the float64 forms of eg_conv2_nhwc, eg_conv2_nhwc_grad_filter and
+ * eg_conv2_nhwc_grad_image, with their formulas, layouts, argument checks, error codes and empty-extent behaviour word for
+ * word: EG_ERR_INVALID for a NULL ctx, a bad extent or a NULL tensor of a non-empty call, EG_ERR_SHAPE for a filter
+ * larger than the image; empty outputs succeed and launch nothing; a gradient whose sum is empty (grad_filter without
+ * pixels, grad_image with F == 0 or an empty gout) zero-fills its destination when accumulate == 0.
+ * Routes, in order: a 1 x 1 filter is a plain product (eg_dgemm); C, F <= 16: the band kernels; forward with F <= 16 and
+ * few taps: the direct kernel; everything else: an implicit GEMM on `v_mfma_f64_16x16x4_f64` (kernels/conv2_f64_mfma.hip),
+ * any channel count, any filter.  Exact float64 multiply-adds; forward and grad_image sum every output element as one
+ * chain in tap order, so an image has the same bits whatever batch it is part of; grad_filter sums slices of the pixels
+ * in a fixed order (no atomics: runs are bit-equal).
+ * No alignment is required of any pointer (16-byte loads are taken when the channel count of the gathered tensor is even
+ * and it is 16-byte aligned).  Only elements of the dense tensors are read: img [N,H,W,C], flt [F,FH,FW,C],
+ * gout [N,H-FH+1,W-FW+1,F]; only elements of the destination are written; with accumulate == 0 it is not read.
+ * EG_ERR_INVALID as well: an implicit GEMM with 2^31 or more rows (pixels), columns or terms, and — under
+ * EG_CONV_NO_MFMA64 — every shape that only the implicit GEMM takes. */
+int eg_conv2_nhwc_f64(eg_ctx* ctx, int64_t N, int64_t H, int64_t W, int64_t C, int64_t F, int64_t FH,
+                      int64_t FW, const double* img, const double* flt, double* out, int accumulate);
+int eg_conv2_nhwc_grad_filter_f64(eg_ctx* ctx, int64_t N, int64_t H, int64_t W, int64_t C, int64_t F, int64_t FH,
+                                  int64_t FW, const double* img, const double* gout, double* gflt, int accumulate);
+int eg_conv2_nhwc_grad_image_f64(eg_ctx* ctx, int64_t N, int64_t H, int64_t W, int64_t C, int64_t F, int64_t FH,
+                                 int64_t FW, const double* flt, const double* gout, double* gimg, int accumulate);
 int eg_colsum_f64(eg_ctx* ctx, int64_t rows, int64_t cols, const double* in, double* out, int accumulate);
 int eg_fill_f64(eg_ctx* ctx, int64_t n, double value, double* out);
 int eg_fill_uniform_f64(eg_ctx* ctx, int64_t n, double lo, double hi, const uint64_t* state, uint64_t stream, double* out);
