@@ -103,8 +103,7 @@ struct InitState {
 };
 
 int init_with_watchdog(int device, int world, const UniqueId& id, int rank, Comm* out) {
-  double timeout_s = 180;
-  if (const char* e = eg::sw::raw("EG_DP_INIT_TIMEOUT_S")) timeout_s = atof(e);
+  const double timeout_s = eg::sw::real(eg::Sw::DP_INIT_TIMEOUT_S, 180);
   auto st = std::make_shared<InitState>();
   std::thread([st, device, world, id, rank] {
     hipSetDevice(device);
@@ -128,11 +127,6 @@ int init_with_watchdog(int device, int world, const UniqueId& id, int rank, Comm
   }
   *out = st->comm;
   return EG_OK;
-}
-
-bool env_on(const char* name) {
-  const char* e = eg::sw::raw(name);
-  return e && e[0] && e[0] != '0';
 }
 }  // namespace
 
@@ -164,8 +158,8 @@ int eg_dp_init(eg_ctx* ctx, const void* id128, int rank, int world, eg_dp** out)
   dp->rank = rank;
   dp->world = world;
   dp->identity = eg::dp::group_identity(id128, sizeof(UniqueId));
-  dp->split = !env_on("EG_DP_NO_SPLIT");
-  if (const char* e = eg::sw::raw("EG_DP_RESERVE_CUS")) dp->reserve_cus = atoi(e);
+  dp->split = !eg::sw::on(eg::Sw::DP_NO_SPLIT);
+  dp->reserve_cus = (int)eg::sw::integer(eg::Sw::DP_RESERVE_CUS, dp->reserve_cus);
   *out = dp;
   return EG_OK;
 }
@@ -247,7 +241,7 @@ int eg_model_step_dp(eg_model* model, const char* target, eg_dp* dp, int mean) {
   gx.split = dp->split;
   // (EG_DP_TEST_AS_MULTI=1: a one-rank group takes the multi-rank code paths — comparison collective, reserved compute
   // units — so that a one-GPU box exercises them)
-  const bool multi = dp->world > 1 || env_on("EG_DP_TEST_AS_MULTI");
+  const bool multi = dp->world > 1 || eg::sw::on(eg::Sw::DP_TEST_AS_MULTI);
   gx.reserve_cus = multi ? dp->reserve_cus : 0;
   gx.allreduce = [](void* user, float* buf, long count) {
     return eg_dp_allreduce_sum_f32(static_cast<eg_dp*>(user), buf, (int64_t)count);

@@ -24,12 +24,7 @@ int build_generic(eg_model* m, Generic& g) {
 // kernel and into maxpool2's hand-written gradient).  Same operations in the same order per element:
 // results are bit-identical.  The reference's CPU target gets a similar effect from fuseLoops
 // (passes.nim:1929-2004); its GPU target launches every kernel.
-void inline_producers(eg_model* m, TargetState& ts) {
-  static const bool off = [] {
-    const char* e = eg::sw::raw("EG_NO_INLINE");
-    return e && e[0] && e[0] != '0';
-  }();
-  if (off) return;
+void inline_producers(eg_model* m, TargetState& ts, bool batched_gemm) {
   Target& t = *ts.target;
   const Program& prog = m->prog;
   auto is_library = [&](const Kernel& k) {
@@ -37,7 +32,7 @@ void inline_producers(eg_model* m, TargetState& ts) {
     ConvMatch c;
     BatchedGemmMatch bg;
     return k.is_seed || match_gemm(k, g) || (!prog.f64 && match_conv(k, c)) ||
-           (!eg::sw::present("EG_NO_BATCHED_GEMM") && match_batched_gemm(k, bg));
+           (batched_gemm && match_batched_gemm(k, bg));
   };
   for (size_t p = 0; p < t.live.size(); ++p) {
     if (ts.lowered[p].absorbed || (int)p == t.first_update) continue;
@@ -128,11 +123,6 @@ void inline_producers(eg_model* m, TargetState& ts) {
 // combined kernel is generated here; a plan uses it only when P covers T completely and T, U and
 // the V have one shape (make_plan), otherwise both kernels run as they are.
 void inline_consumers(eg_model* m, TargetState& ts) {
-  static const bool off = [] {
-    const char* e = eg::sw::raw("EG_NO_INLINE");
-    return e && e[0] && e[0] != '0';
-  }();
-  if (off) return;
   Target& t = *ts.target;
   const Program& prog = m->prog;
   const int n = (int)t.live.size();
@@ -227,7 +217,9 @@ int lower_target(eg_model* m, TargetState& ts) {
   Target& t = *ts.target;
   ts.lowered.clear();
   ts.lowered.resize(t.live.size());
-  inline_producers(m, ts);
+  // read once: both inlining passes, and both questions about batched products, agree within one lowering
+  const bool inlining = !eg::sw::on(eg::Sw::NO_INLINE), batched_gemm = !eg::sw::on(eg::Sw::NO_BATCHED_GEMM);
+  if (inlining) inline_producers(m, ts, batched_gemm);
   for (size_t p = 0; p < t.live.size(); ++p) {
     Lowered& lo = ts.lowered[p];
     lo.all_index = t.live[p];
@@ -255,7 +247,7 @@ int lower_target(eg_model* m, TargetState& ts) {
     // a product with a leading batch index: one batched launch, or a plain product over the collapsed extents
     // (EG_NO_BATCHED_GEMM=1: the generated kernel, as before)
     // (either scalar type: eg_sgemm_batched / eg_dgemm_batched, the collapsed forms eg_sgemm / eg_dgemm)
-    if (!eg::sw::present("EG_NO_BATCHED_GEMM") && match_batched_gemm(k, lo.bgemm)) {
+    if (batched_gemm && match_batched_gemm(k, lo.bgemm)) {
       lo.kind = lo.bgemm.collapsed ? StepKind::Gemm : StepKind::GemmBatched;
       lo.standalone = true;
       lo.gemm.a_read = lo.bgemm.a_read;
@@ -279,7 +271,7 @@ int lower_target(eg_model* m, TargetState& ts) {
     if (rc) return rc;
     m->pending.push_back(&lo.mode_a);  // built together with the model's other generated kernels
   }
-  inline_consumers(m, ts);
+  if (inlining) inline_consumers(m, ts);
   return EG_OK;
 }
 

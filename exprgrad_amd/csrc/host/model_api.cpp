@@ -55,10 +55,7 @@ int model_backward_with_exchange(eg_model* m, const char* target, const GradExch
   mine.split = ex.big >= 0 && !plan->pipe.active;
   mine.early = ex.early;
   mine.late = ex.late;
-  static const long reagree_every = [] {
-    const char* e = eg::sw::raw("EG_DP_REAGREE_STEPS");
-    return e ? atol(e) : 256L;
-  }();
+  const long reagree_every = eg::sw::integer(eg::Sw::DP_REAGREE_STEPS, 256);
   // keyed by what every rank derives identically from the communicator, not by this rank's group address (a one-rank
   // caller without an identity — gx.group 0 — has no peer to disagree with: its address serves)
   eg::dp::Schedule& sched = ts->dp_schedules.of(gx.group ? gx.group : (uint64_t)reinterpret_cast<uintptr_t>(gx.user));

@@ -169,6 +169,7 @@ struct DevTensor {
 struct Plan {
   std::string key;
   int esz = 1;  // 4-byte units per element (eg_model::esz)
+  bool narrow_index = true;  // EG_NO_NARROW_INDEX off when the plan was made: its generated and its sample kernels agree
   Shapes shapes;
   std::vector<Launch> launches;
   int n_backward = 0;  // launches before the first parameter update
@@ -348,7 +349,7 @@ struct LaneSwap {
 
 // lower.cpp
 int build_generic(eg_model* m, Generic& g);
-void inline_producers(eg_model* m, TargetState& ts);
+void inline_producers(eg_model* m, TargetState& ts, bool batched_gemm);
 void inline_consumers(eg_model* m, TargetState& ts);
 int lower_target(eg_model* m, TargetState& ts);
 int build_pending(eg_model* m);
@@ -373,7 +374,7 @@ int build_plan_kernels(eg_model* m, Plan& plan);
 float* tensor_ptr(eg_model* m, TargetState& ts, Plan& plan, int tid);
 bool full_cover(const Kernel& k, const KernelInfo& info, const std::vector<long>& shape);
 void note_vec4(Launch& L, long total);
-int fill_params(eg_model* m, const Kernel& k, const KernelInfo& info, const Shapes& shapes, const GenericSource& src, bool accumulate, long total, long rtotal, long chunk, std::vector<long>& out);
+int fill_params(eg_model* m, const Kernel& k, const KernelInfo& info, const Shapes& shapes, const GenericSource& src, bool accumulate, long total, long rtotal, long chunk, bool narrow_index, std::vector<long>& out);
 std::string shape_key(eg_model* m);
 void release_plan(Plan& plan);
 bool copy_can_alias(eg_model* m, TargetState& ts, const Kernel& k, const KernelInfo& info, const Shapes& shapes, int p);

@@ -92,7 +92,7 @@ void note_vec4(Launch& L, long total) {
 }
 
 int fill_params(eg_model* m, const Kernel& k, const KernelInfo& info, const Shapes& shapes, const GenericSource& src,
-                bool accumulate, long total, long rtotal, long chunk, std::vector<long>& out) {
+                bool accumulate, long total, long rtotal, long chunk, bool narrow_index, std::vector<long>& out) {
   out.clear();
   for (const Slot& s : src.slots) {
     long v = 0;
@@ -125,9 +125,8 @@ int fill_params(eg_model* m, const Kernel& k, const KernelInfo& info, const Shap
         break;
       }
       case Slot::Narrow: {
-        static const bool off = eg::sw::raw("EG_NO_NARROW_INDEX") != nullptr;
         const long lim = 1L << 31;
-        v = !off && total < lim && rtotal < lim;
+        v = narrow_index && total < lim && rtotal < lim;
         auto small = [&](int tensor) {
           auto sh = shapes.find(tensor);
           return sh != shapes.end() && prod(sh->second) < lim;
@@ -218,11 +217,7 @@ std::string shape_key(eg_model* m) {
 // the source's storage?  (reshape and its gradient.)  Requires: dst is written by this kernel only,
 // src is complete by then (no later writer), same element count, dst not in the gradient bucket.
 bool copy_can_alias(eg_model* m, TargetState& ts, const Kernel& k, const KernelInfo& info, const Shapes& shapes, int p) {
-  static const bool off = [] {
-    const char* e = eg::sw::raw("EG_NO_ALIAS");
-    return e && e[0] && e[0] != '0';
-  }();
-  if (off || !info.ok) return false;
+  if (eg::sw::on(eg::Sw::NO_ALIAS) || !info.ok) return false;
   if (k.reads.size() != 1 || !k.instrs.empty() || !k.index_instrs.empty() || k.loops.size() != 1) return false;
   const Op& rd = k.reads[0];
   if (k.result != rd.reg || !k.write.raw || !rd.raw || k.write.dims.size() != 1 || rd.dims.size() != 1) return false;
@@ -245,6 +240,7 @@ int make_plan(eg_model* m, TargetState& ts, Plan& plan) {
   Target& t = *ts.target;
   Shapes& shapes = plan.shapes;
   plan.esz = m->esz;
+  plan.narrow_index = !eg::sw::on(eg::Sw::NO_NARROW_INDEX);
   // A float64 program (compile[float64], model.nim:253-260) runs as the plain launch list: library contractions in
   // float64 (eg_dgemm), everything else as generated kernels over `double`; the float32 fusion passes (row / sample /
   // map groups, contraction epilogues, predicate bits, side lanes) generate float32 code and stay out of it.
@@ -417,7 +413,7 @@ int make_plan(eg_model* m, TargetState& ts, Plan& plan) {
         L.generic = &lo.with_consumer_code;
         L.consumer = q;
         L.blocks_x = (count + 255) / 256;
-        int rc = fill_params(m, F, info, shapes, lo.with_consumer_code.src, !u_first, count, 1, 0, L.params);
+        int rc = fill_params(m, F, info, shapes, lo.with_consumer_code.src, !u_first, count, 1, 0, plan.narrow_index, L.params);
         if (rc) return rc;
         note_vec4(L, count);
         for (size_t si = 0; si < L.generic->src.slots.size(); ++si) {
@@ -617,13 +613,13 @@ int make_plan(eg_model* m, TargetState& ts, Plan& plan) {
         L.blocks_y = col_tiles;
         L.partial_rows = nchunks;
         L.partial_cols = total;
-        int rc = fill_params(m, k, info, shapes, g.src, !overwrite, total, rtotal, chunk, L.params);
+        int rc = fill_params(m, k, info, shapes, g.src, !overwrite, total, rtotal, chunk, plan.narrow_index, L.params);
         if (rc) return rc;
       } else {
         L.kind = StepKind::GenericA;
         L.generic = &lo.mode_a;
         L.blocks_x = (total + 255) / 256;
-        int rc = fill_params(m, k, info, shapes, lo.mode_a.src, !overwrite, total, rtotal, 0, L.params);
+        int rc = fill_params(m, k, info, shapes, lo.mode_a.src, !overwrite, total, rtotal, 0, plan.narrow_index, L.params);
         if (rc) return rc;
         note_vec4(L, total);
       }

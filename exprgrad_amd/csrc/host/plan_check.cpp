@@ -162,11 +162,7 @@ void launch_io(eg_model* m, TargetState& ts, const Plan& plan, const Launch& L, 
 }  // namespace
 
 int check_plan(eg_model* m, TargetState& ts, Plan& plan) {
-  static const bool off = [] {
-    const char* e = eg::sw::raw("EG_NO_PLAN_CHECK");
-    return e && e[0] && e[0] != '0';
-  }();
-  if (off) return EG_OK;
+  if (eg::sw::on(eg::Sw::NO_PLAN_CHECK)) return EG_OK;
   const Target& t = *ts.target;
   const Program& prog = m->prog;
   const int n = (int)plan.launches.size();

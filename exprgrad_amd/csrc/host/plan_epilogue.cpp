@@ -20,14 +20,9 @@ static int predicate_tensors(eg_model* m, TargetState& ts, Plan& plan, const std
   plan.predicated.clear();
   plan.pred_unzeroed.clear();
   if (m->keep_values) return EG_OK;  // eg_model_keep_values
-  {
-    const char* e = eg::sw::raw("EG_NO_PREDICATE");
-    if (e && e[0] && e[0] != '0') return EG_OK;
-    // the batch pipeline (an experiment, off unless EG_PIPELINE=1) addresses half batches of [batch, N] tensors by rows;
-    // bit-packed tensors are not addressed that way: the experiment keeps the values
-    const char* p = eg::sw::raw("EG_PIPELINE");
-    if (p && p[0] && p[0] != '0') return EG_OK;
-  }
+  // the batch pipeline (an experiment, off unless EG_PIPELINE=1) addresses half batches of [batch, N] tensors by rows;
+  // bit-packed tensors are not addressed that way: the experiment keeps the values
+  if (eg::sw::on(eg::Sw::NO_PREDICATE) || eg::sw::on(eg::Sw::PIPELINE)) return EG_OK;
   Target& t = *ts.target;
   auto fused_launch_of_consumer = [&](int live_pos) -> Launch* {
     for (auto& L : plan.launches)
@@ -110,13 +105,8 @@ static int predicate_tensors(eg_model* m, TargetState& ts, Plan& plan, const std
 // the saved round trip through HBM is megabytes; small chains are launch bound and handled by
 // row fusion / graphs.  EG_EPILOGUE_MIN_ELEMS overrides the threshold, EG_NO_EPILOGUE=1 disables.
 int fuse_epilogues(eg_model* m, TargetState& ts, Plan& plan, const std::vector<KernelInfo>& infos) {
-  static const bool off = [] {
-    const char* e = eg::sw::raw("EG_NO_EPILOGUE");
-    return e && e[0] && e[0] != '0';
-  }();
-  if (off) return EG_OK;
-  long min_elems = 1L << 20;
-  if (const char* e = eg::sw::raw("EG_EPILOGUE_MIN_ELEMS")) min_elems = atol(e);
+  if (eg::sw::on(eg::Sw::NO_EPILOGUE)) return EG_OK;
+  const long min_elems = eg::sw::integer(eg::Sw::EPILOGUE_MIN_ELEMS, 1L << 20);
   Target& t = *ts.target;
   plan.epilogues.clear();
   for (size_t i = 0; i + 1 < plan.launches.size(); ++i) {
@@ -201,10 +191,7 @@ int fuse_epilogues(eg_model* m, TargetState& ts, Plan& plan, const std::vector<K
 // The narrow contraction disappears from the launch list (36 us at cfg 5).  EG_NO_ROW_PRODUCT=1 switches it off.
 int fold_row_products(eg_model* m, TargetState& ts, Plan& plan) {
   plan.zero_extra.clear();
-  for (const char* name : {"EG_NO_ROW_PRODUCT", "EG_PIPELINE"}) {  // read per plan: a test compares folded and unfolded plans
-    const char* e = eg::sw::raw(name);
-    if (e && e[0] && e[0] != '0') return EG_OK;
-  }
+  if (eg::sw::on(eg::Sw::NO_ROW_PRODUCT) || eg::sw::on(eg::Sw::PIPELINE)) return EG_OK;
   const Target& t = *ts.target;
   auto shares_storage = [&](int x) {
     bool s = plan.alias.count(x) != 0;
@@ -282,10 +269,7 @@ int fold_row_products(eg_model* m, TargetState& ts, Plan& plan) {
 // bucket the contraction's M + 1 rows of output land exactly in [gW; gb].  The separate column sum
 // (a second pass over g: 134 MB at cfg 5) disappears.
 int fold_bias_gradients(eg_model* m, TargetState& ts, Plan& plan, const std::vector<KernelInfo>& infos) {
-  {  // read per plan (not once per process): a test switches it to compare folded and unfolded plans
-    const char* e = eg::sw::raw("EG_NO_ONES_ROW");
-    if (e && e[0] && e[0] != '0') return EG_OK;
-  }
+  if (eg::sw::on(eg::Sw::NO_ONES_ROW)) return EG_OK;
   const Target& t = *ts.target;
   for (size_t gi = 0; gi < plan.launches.size(); ++gi) {
     Launch& G = plan.launches[gi];

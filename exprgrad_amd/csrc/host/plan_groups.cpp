@@ -5,18 +5,8 @@
 namespace eg {
 namespace model {
 
-bool row_fusion_enabled() {
-  static const bool on = [] {
-    const char* e = eg::sw::raw("EG_NO_ROWFUSE");
-    return !(e && e[0] && e[0] != '0');
-  }();
-  return on;
-}
-
-bool row_tails_enabled() {  // (read when a plan is made: a test builds one model each way)
-  const char* e = eg::sw::raw("EG_NO_ROW_TAIL");
-  return !(e && e[0] && e[0] != '0');
-}
+bool row_fusion_enabled() { return !eg::sw::on(eg::Sw::NO_ROWFUSE); }
+bool row_tails_enabled() { return !eg::sw::on(eg::Sw::NO_ROW_TAIL); }
 
 // Is the tail of this RowFused launch part of the range being issued?  (run.cpp: MODE 2 and the tail launch skipped.)
 bool row_tail_active(const Plan& plan, const Launch& L) {
@@ -60,7 +50,7 @@ int fuse_row_tails(eg_model* m, TargetState& ts, Plan& plan, const std::vector<K
         if (tt.second.role == RowGroupTensor::RowExternal || (tt.second.role == RowGroupTensor::RowLocal && (tt.second.store || tt.second.load_first)))
           row_floats += tt.second.inner;
       long cap = std::max(64L, (pg.g.B * std::max(1L, row_floats) * 4 + 12287) / 12288);
-      cap = eg::sw::integer("EG_ROW_TAIL_BLOCKS", cap);   // tuning aid
+      cap = eg::sw::integer(eg::Sw::ROW_TAIL_BLOCKS, cap);   // tuning aid
       pg.g.grid_blocks = std::min<long>(pg.nblocks, std::max(1L, cap));
     }
     int rc = generate_row_group(t.all, infos, plan.shapes, pg.g);
@@ -91,7 +81,7 @@ int fuse_row_tails(eg_model* m, TargetState& ts, Plan& plan, const std::vector<K
         row_floats += tt.second.inner;
     const long bytes_touched = pg.g.B * std::max(1L, row_floats) * 4;
     long cap = std::max(64L, (bytes_touched + 12287) / 12288);
-    cap = std::max(1L, eg::sw::integer("EG_ROW_TAIL_BLOCKS", cap));   // tuning aid
+    cap = std::max(1L, eg::sw::integer(eg::Sw::ROW_TAIL_BLOCKS, cap));   // tuning aid
     if (pg.nblocks > cap) pg.nblocks = (int)cap;
   }
   return EG_OK;
@@ -107,10 +97,7 @@ bool slab_fold_active(const Plan& plan, const Launch& L) {
 // ends its backward range between them and keeps the launch, because the exchange needs the totals in the bucket).
 // Every summed tensor must be read by the group as a raw map of its own size; EG_NO_SLAB_FOLD=1 off.
 int fuse_slab_fold(eg_model* m, TargetState& ts, Plan& plan, const std::vector<KernelInfo>& infos) {
-  {
-    const char* e = eg::sw::raw("EG_NO_SLAB_FOLD");
-    if (e && e[0] && e[0] != '0') return EG_OK;
-  }
+  if (eg::sw::on(eg::Sw::NO_SLAB_FOLD)) return EG_OK;
   if (!plan.sample_group || plan.sample_group->g.slab_floats <= 0 || plan.pipe.active) return EG_OK;
   // (a thread adds its element's B rows one after the other: beyond a few dozen samples the slab_sum launch, which
   //  spreads the rows over lanes, is the faster fold — batch 256: 69 us per step with the fold, 58 without)
@@ -168,10 +155,7 @@ int fuse_slab_fold(eg_model* m, TargetState& ts, Plan& plan, const std::vector<K
 // Switches: EG_NO_SAMPLE_FUSE=1, EG_SAMPLE_FUSE_MAX_BATCH (default 1280).
 int form_sample_group(eg_model* m, TargetState& ts, Plan& plan, const std::vector<KernelInfo>& infos, const std::map<int, int>& first_writer,
                       std::vector<int>& group_of, std::set<int>& needs_zero) {
-  {
-    const char* e = eg::sw::raw("EG_NO_SAMPLE_FUSE");
-    if ((e && e[0] && e[0] != '0') || !row_fusion_enabled()) return EG_OK;
-  }
+  if (eg::sw::on(eg::Sw::NO_SAMPLE_FUSE) || !row_fusion_enabled()) return EG_OK;
   Target& t = *ts.target;
   const Shapes& shapes = plan.shapes;
   long B = 0;
@@ -183,8 +167,7 @@ int form_sample_group(eg_model* m, TargetState& ts, Plan& plan, const std::vecto
   // (fashion_mnist step, one box, sample group vs launch chain: 43.7 vs 76.5 us at batch 32, 57 vs 119 at 256, 94 vs 136 at 512, 170 vs 183 at
   //  1024, 299 vs 245 at 2048 — until the small-channel convolutions of round 5 made the chain's five convolution launches twice as fast, the
   //  chain took 381 there and the limit was 2048)
-  long max_batch = 1280;
-  if (const char* e = eg::sw::raw("EG_SAMPLE_FUSE_MAX_BATCH")) max_batch = atol(e);
+  const long max_batch = eg::sw::integer(eg::Sw::SAMPLE_FUSE_MAX_BATCH, 1280);
   if (B < 2 || B > max_batch) return EG_OK;
   const int n = (int)t.live.size();
   const int limit = t.first_update >= 0 ? t.first_update : n;
@@ -207,7 +190,7 @@ int form_sample_group(eg_model* m, TargetState& ts, Plan& plan, const std::vecto
     } else if (ski[p].ok && scatter && ski[p].reduced) {
       ski[p].ok = false;  // (the slab row would have to start from zero)
     }
-    if (ski[p].ok && !eg::sw::present("EG_SAMPLE_NO_MFMA") && match_conv(k, cm) && cm.batched) {
+    if (ski[p].ok && !eg::sw::on(eg::Sw::SAMPLE_NO_MFMA) && match_conv(k, cm) && cm.batched) {
       // a convolution member on the matrix cores (rowfuse.hpp conv_role): small operand fragments must fit registers
       auto tensor_of = [&](int op) { return op < 0 ? k.write.tensor : k.reads[op].tensor; };
       const int ti = tensor_of(cm.img_op), to = tensor_of(cm.out_op), tf = tensor_of(cm.flt_op);
@@ -249,7 +232,7 @@ int form_sample_group(eg_model* m, TargetState& ts, Plan& plan, const std::vecto
       }
     }
   }
-  static const bool debug = eg::sw::raw("EG_DEBUG_SAMPLE") != nullptr;
+  const bool debug = eg::sw::on(eg::Sw::DEBUG_SAMPLE);
   if (debug)
     for (int p = 0; p < limit; ++p)
       fprintf(stderr, "[eg] sample: live %d ok %d loop %d raw %d reduced %d seed %d gather %d work %ld absorbed %d inlined %d | %s\n", p, (int)ski[p].ok,
@@ -398,7 +381,7 @@ int form_sample_group(eg_model* m, TargetState& ts, Plan& plan, const std::vecto
         if (!first_plain[tid]) g.lds_zero.insert(tid);
       }
     // parameters the members only read, into what is left of the block's LDS (at most 48 KB of them): rowfuse.hpp `staged`
-    if (!eg::sw::present("EG_SAMPLE_NO_STAGE")) {
+    if (!eg::sw::on(eg::Sw::SAMPLE_NO_STAGE)) {
       std::set<int> read_only, written_by;
       for (size_t i = 0; i < g.kernel_index.size(); ++i) {
         const Kernel& k = t.all[g.kernel_index[i]];
@@ -422,6 +405,7 @@ int form_sample_group(eg_model* m, TargetState& ts, Plan& plan, const std::vecto
   char name[64];
   snprintf(name, sizeof(name), "eg_samples%d", m->kernel_serial++);
   g.name = name;
+  g.narrow_index = plan.narrow_index;
   int rc = generate_sample_group(t.all, infos, shapes, g);
   if (rc) return rc;
   if (g.slab_floats > 0) {

@@ -69,12 +69,8 @@ bool launch_tensors(const Plan& plan, const Launch& L, std::set<int>& reads, std
 // it on the side lane instead of in front of it (tools/overlap_probe.py: 582 -> 511 us).
 void plan_overlap(eg_model* m, TargetState& ts, Plan& plan) {
   (void)ts;
-  static const bool off = [] {
-    const char* e = eg::sw::raw("EG_NO_OVERLAP");
-    return e && e[0] && e[0] != '0';
-  }();
   plan.overlaps.clear();
-  if (off) return;
+  if (eg::sw::on(eg::Sw::NO_OVERLAP)) return;
   const int n = (int)plan.launches.size();
   for (int j = 1; j < n; ++j) {
     const Launch& B = plan.launches[j];
@@ -99,14 +95,13 @@ void plan_overlap(eg_model* m, TargetState& ts, Plan& plan) {
       if (clash) break;
       first = i;
     }
-    static const bool debug = eg::sw::raw("EG_DEBUG_OVERLAP") != nullptr;
-    if (debug) fprintf(stderr, "[eg] overlap: contraction %d (%.1f GFLOP) takes launches [%d, %d)\n", j, flops / 1e9, first, j);
+    if (eg::sw::on(eg::Sw::DEBUG_OVERLAP)) fprintf(stderr, "[eg] overlap: contraction %d (%.1f GFLOP) takes launches [%d, %d)\n", j, flops / 1e9, first, j);
     if (first < j && ensure_side_lane(m->ctx) == EG_OK) {
       plan.overlaps.push_back({first, j});
       // Round 6: a row group shortly in front of the group whose totals (a bias gradient's column sums) nobody reads before
       // the contraction is over hands its fold to the side lane: in the dense step the row kernel's in-kernel fold was
       // 5 of its 12.8 us, on the critical path between the forward product and the backward chain.
-      const bool keep_tail = eg::sw::raw("EG_NO_DEFERRED_FOLD") != nullptr;   // (read per plan: a test builds one model each way)
+      const bool keep_tail = eg::sw::on(eg::Sw::NO_DEFERRED_FOLD);
       for (int r = first - 1; !keep_tail && r >= 0 && r >= first - 3; --r) {
         const Launch& R = plan.launches[r];
         if (r + 1 == plan.n_backward) break;

@@ -232,6 +232,7 @@ struct SampleGroup {
   std::map<int, long> lds;
   std::set<int> lds_zero;           // of those: accumulated into before being written whole (start from zero)
   int threads = 256;                // block size (a multiple of 64)
+  bool narrow_index = true;         // the plan's: 32-bit index arithmetic is allowed (EG_NO_NARROW_INDEX off when the plan was made)
   // Round 6: small PARAMETER tensors the members read (filter banks, a dense layer's weights) are copied into LDS once, at the
   // kernel's start: a member that walked them with dependent loads paid an L2 round trip per iteration (the 400-term dense
   // layer of the fashion_mnist network: eight of them in a row).  tensor id -> floats.

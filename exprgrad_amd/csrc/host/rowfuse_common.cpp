@@ -113,7 +113,7 @@ static const char* const kXorLane =
     "  } else return __shfl_xor(v, OFF, 64);\n"
     "}\n#endif\n";
 std::string xor_lane_prelude() {
-  return eg::sw::raw("EG_NO_DPP_BUTTERFLY") ? std::string("#ifndef EG_XOR_LANE\n#define EG_XOR_LANE\ntemplate <int OFF> __device__ __forceinline__ float "
+  return eg::sw::on(eg::Sw::NO_DPP_BUTTERFLY) ? std::string("#ifndef EG_XOR_LANE\n#define EG_XOR_LANE\ntemplate <int OFF> __device__ __forceinline__ float "
                                                           "eg_xor_lane(float v) { return __shfl_xor(v, OFF, 64); }\n#endif\n")
                                             : std::string(kXorLane);
 }

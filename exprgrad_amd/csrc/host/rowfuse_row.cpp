@@ -200,7 +200,7 @@ int generate_row_group(const std::vector<Kernel>& all, const std::vector<KernelI
   // One block (a batch of at most 256 rows): the totals go straight to their destinations.  In a captured graph a
   // dependent launch costs ~4.5 us whatever it does, and row_finalize of one partial row does nothing but copy
   // (p + 0 + 0 + 0 in its tree: the same value).
-  g.single_block = g.B <= 256 && g.red_total > 0 && eg::sw::raw("EG_NO_ROW_DIRECT") == nullptr;
+  g.single_block = g.B <= 256 && g.red_total > 0 && !eg::sw::on(eg::Sw::NO_ROW_DIRECT);
   if (g.single_block) g.in_kernel_finalize = false;
   if (g.red_total <= 0) g.in_kernel_finalize = false;
   if (!g.in_kernel_finalize) g.tail_kernels.clear();
@@ -389,7 +389,7 @@ int generate_row_group(const std::vector<Kernel>& all, const std::vector<KernelI
         c += "    }\n  }\n";
         // EG_ROW_TRACE=1 (detector): the last block to arrive prints where ITS time went — cycles since its own start at:
         // samples done, partial row stored and drained, ticket taken, partial rows of all blocks read, totals and tail done
-        if (eg::sw::raw("EG_ROW_TRACE") != nullptr) {
+        if (eg::sw::on(eg::Sw::ROW_TRACE)) {
           auto insert_before = [&](const std::string& anchor, const std::string& text, size_t from) {
             const size_t at = c.find(anchor, from);
             if (at == std::string::npos) return std::string::npos;

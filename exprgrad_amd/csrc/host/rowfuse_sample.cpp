@@ -446,7 +446,7 @@ void elide_barriers(const SampleCtx& cx, bool& prologue_barrier, std::vector<Sam
 // computes with Index VALUES (`toScalar(i * 100000)`: only addressing is known to fit — the rule of Slot::Narrow,
 // codegen.hpp).  64-bit divisions and multiply-adds per element were most of a convolution member's time.
 bool index_fits_32_bits(const SampleCtx& cx, const std::set<int>& touched) {
-  bool narrow = eg::sw::raw("EG_NO_NARROW_INDEX") == nullptr && cx.g.B * std::max(1L, cx.g.slab_floats) < (1L << 31);
+  bool narrow = cx.g.narrow_index && cx.g.B * std::max(1L, cx.g.slab_floats) < (1L << 31);
   for (int t : touched) narrow = narrow && prodv(cx.shapes.at(t)) < (1L << 31);
   for (int ki : cx.g.kernel_index) {
     const Kernel& k = cx.all[ki];
@@ -468,8 +468,8 @@ bool index_fits_32_bits(const SampleCtx& cx, const std::set<int>& touched) {
 // what its second, instruction-cache-warm execution costs)
 std::string assemble(const SampleCtx& cx, const std::string& head, bool head_barrier, const std::string& row,
                      const std::vector<SampleMember>& members, bool narrow) {
-  const bool trace = eg::sw::raw("EG_SAMPLE_TRACE") != nullptr;
-  const long repeat = trace ? eg::sw::integer("EG_SAMPLE_TRACE", 1) - 100 : -1;
+  const bool trace = eg::sw::is_set(eg::Sw::SAMPLE_TRACE);
+  const long repeat = eg::sw::integer(eg::Sw::SAMPLE_TRACE, 0) - 100;   // (unset: negative, no member repeats)
   const std::string barrier = "  __syncthreads();\n";
   const std::string stamp = trace ? "  if (threadIdx.x == 0 && blockIdx.x == 0 && trn_ < 48) tr_[trn_++] = __builtin_readcyclecounter();\n" : "";
   const std::regex long_type("\\blong\\b"), long_literal("\\b([0-9]+)L\\b");
@@ -508,7 +508,7 @@ int generate_sample_group(const std::vector<Kernel>& all, const std::vector<Kern
   std::string sig;
   std::string head = emit_prologue(g, cx.NT, touched, written, sig);
   // EG_SAMPLE_STOP=<k> (tuning aid): the kernel ends behind member k — wrong numbers, the time of the first k + 1 members
-  const long stop = eg::sw::integer("EG_SAMPLE_STOP", -1);
+  const long stop = eg::sw::integer(eg::Sw::SAMPLE_STOP, -1);
   std::vector<SampleMember> members;
   long scratch_floats = 0;
   bool need_dummy = false, need_zeros4 = false;
@@ -546,7 +546,7 @@ int generate_sample_group(const std::vector<Kernel>& all, const std::vector<Kern
   if (need_zeros4) head += "  __shared__ __attribute__((aligned(16))) float zeros4_[4];\n  if (threadIdx.x < 4) zeros4_[threadIdx.x] = 0.0f;\n";
   if (need_dummy) head = "  __shared__ float dummy_[" + cx.NT + "];\n" + head;   // (not `scratch`: a member behind an elided barrier may be using that)
   if (scratch_floats > 0) head = "  __shared__ float scratch[" + std::to_string(scratch_floats) + "];\n" + head;
-  if (eg::sw::raw("EG_SAMPLE_KEEP_BARRIERS") == nullptr) elide_barriers(cx, prologue_barrier, members);
+  if (!eg::sw::on(eg::Sw::SAMPLE_KEEP_BARRIERS)) elide_barriers(cx, prologue_barrier, members);
   const std::string row = g.slab_floats > 0 ? "  float* const row = slab + n * " + std::to_string(g.slab_floats) + "L;\n" : "";
   g.narrow = index_fits_32_bits(cx, touched);
   g.routes.clear();

@@ -96,7 +96,7 @@ int run_launch(eg_model* m, TargetState& ts, Plan& plan, Launch& L) {
       if (!handle) {
         const std::string name = "eg_gemm_epi" + std::to_string(m->kernel_serial++);
         const std::string src = eg::gemm::fused_source(f, struct_code, pe.spec.struct_name, name);
-        if (const char* dump = eg::sw::raw("EG_DUMP_FUSED")) {  // debugging aid: the generated translation unit
+        if (const char* dump = eg::sw::text(eg::Sw::DUMP_FUSED)) {  // debugging aid: the generated translation unit
           if (FILE* fp = fopen((std::string(dump) + "/" + name + "_" + variant + ".hip").c_str(), "w")) {
             fputs(src.c_str(), fp);
             fclose(fp);
@@ -111,9 +111,8 @@ int run_launch(eg_model* m, TargetState& ts, Plan& plan, Launch& L) {
         }
         m->kernels.push_back(handle);
       }
-      static const bool gemm_trace = eg::sw::raw("EG_GEMM_TRACE") != nullptr;
       long long* trace = nullptr;
-      if (gemm_trace && !f.narrow) {
+      if (eg::sw::on(eg::Sw::GEMM_TRACE) && !f.narrow) {
         trace = eg::gemm::trace_begin(ctx, f.grid, (unsigned)f.nt / 64);
         eg::gemm::fused_set_trace(f, trace);
       }
@@ -407,7 +406,7 @@ int run_range_eager(eg_model* m, TargetState& ts, Plan& plan, int begin, int end
       // shrink by 11 us, the contraction shares its CUs from the start and takes 14 us longer.  A data-parallel step keeps
       // the side lane first: its early gradient exchange rides that lane and must not queue behind 256 resident blocks.
       // EG_OVERLAP_SIDE_FIRST=1: the order of rounds 2 - 5 everywhere.
-      const bool side_first = eg::sw::raw("EG_OVERLAP_SIDE_FIRST") != nullptr || (hook && hook->big == big);
+      const bool side_first = eg::sw::on(eg::Sw::OVERLAP_SIDE_FIRST) || (hook && hook->big == big);
       if (!side_first) {
         int rc = run_launch(m, ts, plan, plan.launches[big]);
         if (rc) return rc;
@@ -440,8 +439,7 @@ int run_range_eager(eg_model* m, TargetState& ts, Plan& plan, int begin, int end
     // Two independent tiny contractions next to each other (a dense layer's two gradients at a small batch): one launch
     // (EG_NO_SMALL_PAIR=1: two).  Independence is checked on the storage: neither writes what the other touches.
     // (A collapsed batched product, Launch::standalone, keeps its own launch here as everywhere else.)
-    const bool pair_off = eg::sw::raw("EG_NO_SMALL_PAIR") != nullptr;   // (read per launch sequence: a test builds one model each way)
-    if (!pair_off && !m->f64 && i + 1 < end && i + 1 != plan.n_backward &&
+    if (!eg::sw::on(eg::Sw::NO_SMALL_PAIR) && !m->f64 && i + 1 < end && i + 1 != plan.n_backward &&
         !(next_overlap < plan.overlaps.size() && plan.overlaps[next_overlap].first == i + 1)) {
       const Launch &A = plan.launches[i], &B = plan.launches[i + 1];
       if (A.kind == StepKind::Gemm && B.kind == StepKind::Gemm && !A.ones_tensor && !B.ones_tensor && !A.standalone && !B.standalone &&
@@ -472,13 +470,7 @@ int run_range_eager(eg_model* m, TargetState& ts, Plan& plan, int begin, int end
   return EG_OK;
 }
 
-bool graphs_enabled() {
-  static const bool on = [] {
-    const char* e = eg::sw::raw("EG_NO_GRAPH");
-    return !(e && e[0] && e[0] != '0');
-  }();
-  return on;
-}
+bool graphs_enabled() { return !eg::sw::on(eg::Sw::NO_GRAPH); }
 
 std::string capture_key(eg_model* m, TargetState& ts) {
   std::ostringstream key;
@@ -535,7 +527,7 @@ int run_range(eg_model* m, TargetState& ts, Plan& plan, int begin, int end, bool
   }
   hipGraph_t graph = nullptr;
   hipError_t e = hipStreamBeginCapture(m->ctx->stream, hipStreamCaptureModeThreadLocal);
-  static const bool debug = eg::sw::raw("EG_DEBUG_GRAPH") != nullptr;
+  const bool debug = eg::sw::on(eg::Sw::DEBUG_GRAPH);
   if (e != hipSuccess) {  // capture unavailable on this stream: stay eager
     if (debug) fprintf(stderr, "[eg] begin capture failed: %s\n", hipGetErrorString(e));
     (void)hipGetLastError();

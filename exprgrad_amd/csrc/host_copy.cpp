@@ -148,13 +148,7 @@ static void parallel_copy(Pool& pool, void* dst, const void* src, size_t bytes) 
   });
 }
 
-static bool staging_enabled() {
-  static const bool on = [] {
-    const char* e = eg::sw::raw("EG_NO_STAGED_COPY");
-    return !(e && e[0] && e[0] != '0');
-  }();
-  return on;
-}
+static bool staging_enabled() { return !eg::sw::on(eg::Sw::NO_STAGED_COPY); }
 
 static bool is_pageable(const void* host) {
   hipPointerAttribute_t attr;

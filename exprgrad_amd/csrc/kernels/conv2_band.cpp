@@ -32,7 +32,7 @@ namespace {
 eg_kernel* get_or_build(eg_ctx* ctx, const std::string& name, const std::string& source) {
   auto it = ctx->jit.find(name);
   if (it != ctx->jit.end()) return it->second;
-  if (const char* dump = eg::sw::raw("EG_DUMP_BAND")) {  // debugging aid: the generated translation unit
+  if (const char* dump = eg::sw::text(eg::Sw::DUMP_BAND)) {  // debugging aid: the generated translation unit
     if (FILE* fp = fopen((std::string(dump) + "/" + name + ".hip").c_str(), "w")) {
       fputs(source.c_str(), fp);
       fclose(fp);
@@ -44,10 +44,7 @@ eg_kernel* get_or_build(eg_ctx* ctx, const std::string& name, const std::string&
   return k;
 }
 
-bool disabled() {
-  const char* e = eg::sw::raw("EG_CONV_NO_BAND");  // read per call: a test compares the routes
-  return e && e[0] && e[0] != '0';
-}
+bool disabled() { return eg::sw::on(eg::Sw::CONV_NO_BAND); }
 
 std::string S(long v) { return std::to_string(v); }
 
@@ -68,8 +65,8 @@ Band plan_band(long HI, long WI, long CI, long FH, long FW, long PY, long PX, lo
   b.WP = WI + 2 * PX;
   b.STR = CI | 1;
   const long budget = 40 * 1024 / elem_bytes;
-  long target = 1024;
-  if (const char* e = eg::sw::raw("EG_CONV_BAND_PIXELS")) target = atol(e) > 0 ? atol(e) : target;  // tuning aid
+  long target = eg::sw::integer(eg::Sw::CONV_BAND_PIXELS, 1024);  // tuning aid
+  if (target <= 0) target = 1024;
   b.R = std::min(Ho, std::max(1L, target / Wo));
   b.NB = b.R == Ho ? std::max(1L, std::min(16L, target / (Ho * Wo))) : 1;
   auto elems = [&](long nb, long r) { return nb * (r + FH - 1) * b.WP * b.STR; };

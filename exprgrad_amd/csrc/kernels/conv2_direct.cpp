@@ -32,13 +32,7 @@ eg_kernel* get_or_build(eg_ctx* ctx, const std::string& name, const std::string&
   return k;
 }
 
-bool disabled() {
-  static const bool off = [] {
-    const char* e = eg::sw::raw("EG_CONV_NO_DIRECT");
-    return e && e[0] && e[0] != '0';
-  }();
-  return off;
-}
+bool disabled() { return eg::sw::on(eg::Sw::CONV_NO_DIRECT); }
 
 std::string L(long v) { return std::to_string(v) + "L"; }
 
@@ -242,8 +236,7 @@ int conv2_direct_grad_filter_try(eg_ctx* ctx, long N, long H, long W, long C, lo
   eg_kernel* k = get_or_build(ctx, name, s);
   if (!k) return EG_ERR_COMPILE;
   long blocks = (P + 256 * 8 - 1) / (256 * 8);  // at least 8 pixels per thread where the problem allows
-  long cap = ctx->compute_units;  // few blocks: the shuffle reduction of E values per block is the fixed cost
-  if (const char* e = eg::sw::raw("EG_CONV_DIRECT_BLOCKS")) cap = atol(e);
+  const long cap = eg::sw::integer(eg::Sw::CONV_DIRECT_BLOCKS, ctx->compute_units);  // few blocks: the shuffle reduction of E values per block is the fixed cost
   if (blocks > cap) blocks = cap;
   if (blocks < 1) blocks = 1;
   const size_t pfloats = ((size_t)blocks * E + 3) & ~(size_t)3;

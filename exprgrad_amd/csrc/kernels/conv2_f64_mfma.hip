@@ -305,7 +305,7 @@ const char* const kKernelNames[4] = {"", "eg_conv64_mfma_fwd", "eg_conv64_mfma_g
 
 namespace eg {
 
-bool conv2_f64_mfma_enabled() { return eg::sw::raw("EG_CONV_NO_MFMA64") == nullptr; }
+bool conv2_f64_mfma_enabled() { return !eg::sw::on(eg::Sw::CONV_NO_MFMA64); }
 
 // The one internal entry of the three roles: the C entry points below and the model layer (host/run.cpp) both come here
 // with checked, non-empty extents.  a / b as the library's entry points take them: image + filters (forward), filters +

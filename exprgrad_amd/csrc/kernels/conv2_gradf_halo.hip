@@ -284,8 +284,7 @@ namespace eg {
 int conv2_gradf_halo_try(eg_ctx* ctx, long N, long H, long W, long C, long F, long FH, long FW, const float* img, const float* gout,
                          float* gflt, int accumulate, bool* launched) {
   *launched = false;
-  const char* e = eg::sw::raw("EG_CONV_NO_GRADF_HALO");   // (read per call: a test compares the two routes)
-  const bool off = e && e[0] && e[0] != '0';
+  const bool off = eg::sw::on(eg::Sw::CONV_NO_GRADF_HALO);
   if (off || FH != 3 || FW != 3 || C % QB != 0 || F % QB != 0 || C < QB || F < QB) return EG_OK;
   const long Ho = H - 2, Wo = W - 2;
   if (Ho <= 0 || Wo <= 0) return EG_OK;
@@ -322,7 +321,7 @@ int conv2_gradf_halo_try(eg_ctx* ctx, long N, long H, long W, long C, long F, lo
   a.segs = segs;
   a.qc = (int)(C / QB);
   a.ranges = (int)ranges;
-  static const bool trace_on = eg::sw::raw("EG_GRADF_TRACE") != nullptr;
+  const bool trace_on = eg::sw::on(eg::Sw::GRADF_TRACE);
   const long nwaves = quadrants * ranges * WAVES;
   if (trace_on) EG_HIP_CHECK(hipMalloc((void**)&a.trace, (size_t)nwaves * 64 * sizeof(long long)));
   void* params[] = {&a};

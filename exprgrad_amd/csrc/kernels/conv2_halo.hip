@@ -404,11 +404,7 @@ int conv2_halo_try(eg_ctx* ctx, long N, long H, long W, long C, long F, long FH,
 // flt_aligned: the filter bank the caller will pass is 16-byte aligned.
 bool conv2_halo_suits(eg_ctx* ctx, long N, long H, long W, long C, long F, long FH, long FW, long py, long px, const float* img,
                       bool flt_aligned) {
-  static const bool off = [] {
-    const char* e = eg::sw::raw("EG_CONV_NO_HALO");
-    return e && e[0] && e[0] != '0';
-  }();
-  if (off) return false;
+  if (eg::sw::on(eg::Sw::CONV_NO_HALO)) return false;
   const long Ho = H + 2 * py - FH + 1, Wo = W + 2 * px - FW + 1;
   if (FH > 3 || FW > 3 || C % CK != 0 || C < CK || Ho <= 0 || Wo <= 0) return false;
   if ((reinterpret_cast<uintptr_t>(img) & 15) || !flt_aligned) return false;
@@ -465,11 +461,10 @@ int conv2_halo_try_padded(eg_ctx* ctx, long N, long H, long W, long C, long F, l
     return EG_OK;
   }
   a.items = blocks;
-  static const bool wide_off = eg::sw::raw("EG_CONV_NO_WIDE_STORE") != nullptr;
-  a.wide_store = !wide_off && F % 4 == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0;
+  a.wide_store = !eg::sw::on(eg::Sw::CONV_NO_WIDE_STORE) && F % 4 == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0;
   // one block per CU (LDS); several rounds of work run as persistent blocks
   const long grid = blocks < (long)ctx->compute_units ? blocks : (long)ctx->compute_units;
-  static const bool trace_on = eg::sw::raw("EG_HALO_TRACE") != nullptr;
+  const bool trace_on = eg::sw::on(eg::Sw::HALO_TRACE);
   const long nwaves = grid * (NT / 64);
   if (trace_on) {
     EG_HIP_CHECK(hipMalloc((void**)&a.trace, (size_t)nwaves * 32 * sizeof(long long)));

@@ -28,34 +28,34 @@ using namespace eg::gemm;
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-// The GEMM switches, read again after every reload of the switch table (eg_switches_reload): kept per thread and
-// generation so that a product costs no switch lookups (the planner's seventeen would outnumber those of a small product).
+// The GEMM switches as the planner wants them (a parsed tile, counts), derived again after every reload of the environment
+// (eg_switches_reload): kept per thread and generation so that a product parses nothing.
 const GemmSwitches& gemm_switches() {
   thread_local GemmSwitches s;
   thread_local unsigned seen = 0;
   const unsigned gen = eg::sw::generation();
   if (gen == seen) return s;
   s = GemmSwitches();
-  s.no_small = eg::sw::on("EG_NO_SMALL_GEMM");
-  s.no_skinny = eg::sw::on("EG_NO_SKINNY_GEMM");
-  s.no_pair = eg::sw::present("EG_GEMM_NO_PAIR");
-  s.no_t96 = eg::sw::present("EG_GEMM_NO_T96");
-  s.no_streamk = eg::sw::present("EG_GEMM_NO_STREAMK");
-  s.no_xrow = eg::sw::present("EG_GEMM_NO_XROW");
-  s.no_bk32 = eg::sw::present("EG_GEMM_NO_BK32");
-  s.no_wide_store = eg::sw::present("EG_GEMM_NO_WIDE_STORE");
-  s.no_skew = eg::sw::present("EG_GEMM_NO_SKEW");
-  s.old_tile_model = eg::sw::present("EG_GEMM_OLD_TILE_MODEL");
-  s.small_bk32 = eg::sw::present("EG_GEMM_SMALL_BK32");
-  s.debug_tile = eg::sw::present("EG_DEBUG_TILE");
-  s.trace = eg::sw::present("EG_GEMM_TRACE");
-  const char* tile = eg::sw::raw("EG_GEMM_FORCE_TILE");
-  const char* splits = eg::sw::raw("EG_GEMM_FORCE_SPLITS");
-  const char* blocks = eg::sw::raw("EG_STREAMK_BLOCKS_PER_CU");
+  s.no_small = eg::sw::on(eg::Sw::NO_SMALL_GEMM);
+  s.no_skinny = eg::sw::on(eg::Sw::NO_SKINNY_GEMM);
+  s.no_pair = eg::sw::on(eg::Sw::GEMM_NO_PAIR);
+  s.no_t96 = eg::sw::on(eg::Sw::GEMM_NO_T96);
+  s.no_streamk = eg::sw::on(eg::Sw::GEMM_NO_STREAMK);
+  s.no_xrow = eg::sw::on(eg::Sw::GEMM_NO_XROW);
+  s.no_bk32 = eg::sw::on(eg::Sw::GEMM_NO_BK32);
+  s.no_wide_store = eg::sw::on(eg::Sw::GEMM_NO_WIDE_STORE);
+  s.no_skew = eg::sw::on(eg::Sw::GEMM_NO_SKEW);
+  s.old_tile_model = eg::sw::on(eg::Sw::GEMM_OLD_TILE_MODEL);
+  s.small_bk32 = eg::sw::on(eg::Sw::GEMM_SMALL_BK32);
+  s.debug_tile = eg::sw::on(eg::Sw::DEBUG_TILE);
+  s.trace = eg::sw::on(eg::Sw::GEMM_TRACE);
+  const char* tile = eg::sw::text(eg::Sw::GEMM_FORCE_TILE);
+  const char* splits = eg::sw::text(eg::Sw::GEMM_FORCE_SPLITS);
+  const char* blocks = eg::sw::text(eg::Sw::STREAMK_BLOCKS_PER_CU);
   if ((s.force_tile = tile != nullptr)) sscanf(tile, "%d,%d", &s.force_bm, &s.force_bn);
   if ((s.force_splits = splits != nullptr)) s.force_splits_n = atoi(splits);
   if ((s.streamk_blocks = blocks != nullptr)) s.streamk_blocks_per_cu = atol(blocks);
-  s.streamk_min_ratio = eg::sw::real("EG_STREAMK_MIN_RATIO", 24.0);
+  s.streamk_min_ratio = eg::sw::real(eg::Sw::STREAMK_MIN_RATIO, 24.0);
   seen = gen;
   return s;
 }
@@ -368,8 +368,7 @@ namespace gemm {
 bool ones_row_supported(int trans_a, int trans_b, long M, long N, long K, const float* A, long lda, const float* B, long ldb) {
   const bool vec_a = operand_vec(lda, trans_a ? M : K, aligned16(A)), vec_b = operand_vec(ldb, trans_b ? K : N, aligned16(B));
   // large enough for the matrix-core path (not the one-wave-per-output kernel) and at least one k-tile
-  const char* off = eg::sw::raw("EG_NO_ONES_ROW");
-  return vec_a && vec_b && K >= 16 && !((M + 1) * N <= 16384 && K <= 2048) && !(off && off[0] && off[0] != '0');
+  return vec_a && vec_b && K >= 16 && !((M + 1) * N <= 16384 && K <= 2048) && !eg::sw::on(eg::Sw::NO_ONES_ROW);
 }
 
 int sgemm_ones_row(eg_ctx* ctx, int trans_a, int trans_b, long M, long N, long K, const float* A, long lda, const float* B,
@@ -593,7 +592,7 @@ extern "C" int eg_conv2_nhwc_grad_image(eg_ctx* ctx, int64_t N, int64_t H, int64
   // The halo kernel pads by itself (pixels outside the gradient come from a block of zeros): only the flipped bank is
   // prepared — no padded copy of the gradient is written and read back (cfg 4: 2 x 17 MB, 8 -> 3 us of preparation).
   // EG_CONV_NO_VIRTUAL_PAD=1: the padded copy of rounds 1 and 2.
-  const bool virtual_pad = eg::sw::raw("EG_CONV_NO_VIRTUAL_PAD") == nullptr;  // (read per call: a test compares the two routes)
+  const bool virtual_pad = !eg::sw::on(eg::Sw::CONV_NO_VIRTUAL_PAD);
   if (virtual_pad && FH <= 3 && FW <= 3 && F % 16 == 0 && aligned16(gout) &&
       eg::conv2_halo_suits(ctx, N, Ho, Wo, F, C, FH, FW, FH - 1, FW - 1, gout, true)) {   // (the bank goes to ctx->aux: aligned)
     rc = eg::ensure_aux(ctx, flt_floats * sizeof(float));
@@ -723,7 +722,7 @@ int plan_fused(eg_ctx* ctx, int trans_a, int trans_b, long M, long N, long K, co
   memcpy(out.args, &args, sizeof(args));
   out.args_size = sizeof(args);
   {  // tiny K: a store stream, not matrix work (gemm_narrow_k_block)
-    const bool off = eg::sw::raw("EG_NO_NARROW_K") != nullptr;   // (read per call: a test compares the two routes)
+    const bool off = eg::sw::on(eg::Sw::NO_NARROW_K);
     const long tpr = N / 4;
     if (!off && K >= 1 && K <= 16 && N % 4 == 0 && tpr >= 1 && tpr <= 256 && 256 % tpr == 0 && ldc % 4 == 0 && aligned16(C) &&
         (!bias || aligned16(bias)) && M * N >= (1L << 16)) {

@@ -239,7 +239,7 @@ int dgemm(eg_ctx* ctx, int trans_a, int trans_b, long M, long N, long K, const d
   rc = eg::set_device(ctx);
   if (rc) return rc;
   DgemmProblem prob = {M, N, K, lda, ldb, aligned16(A), aligned16(B), ctx->compute_units};
-  if (const char* e = eg::sw::raw("EG_DGEMM_TILE")) {  // measurement aid: "<config>[,<splits>]"; without the count the model's slices stay
+  if (const char* e = eg::sw::text(eg::Sw::DGEMM_TILE)) {  // measurement aid: "<config>[,<splits>]"; without the count the model's slices stay
     prob.force_config = atoi(e);
     if (const char* comma = strchr(e, ',')) prob.force_splits = atol(comma + 1) > 0 ? atol(comma + 1) : 1;
   }
@@ -279,7 +279,7 @@ int dgemm_batched(eg_ctx* ctx, int trans_a, int trans_b, long batch, long M, lon
   if (rc) return rc;
 
   DgemmBatchedProblem prob = {batch, M, N, K, lda, ldb, stride_a, stride_b, aligned16(A), aligned16(B), ctx->compute_units};
-  if (const char* e = eg::sw::raw("EG_DGEMM_BATCHED_ROUTE")) prob.force = strcmp(e, "launch") == 0 ? 1 : strcmp(e, "loop") == 0 ? 2 : 0;
+  if (const char* e = eg::sw::text(eg::Sw::DGEMM_BATCHED_ROUTE)) prob.force = strcmp(e, "launch") == 0 ? 1 : strcmp(e, "loop") == 0 ? 2 : 0;
   const DgemmBatchedPlan plan = plan_dgemm_batched(prob);
   if (plan.loop) {   // every item fills the chip by itself: plain products on their own routes
     for (long b = 0; b < batch; ++b) {

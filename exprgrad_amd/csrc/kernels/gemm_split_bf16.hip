@@ -541,7 +541,7 @@ int sgemm_split(eg_ctx* ctx, int trans_a, int trans_b, long M, long N, long K, c
   // anything the exact entry would refuse or that does not qualify goes there untouched
   if (!ctx || !A || !B || !C || M <= 0 || N <= 0 || K <= 0) return EG_ERR_UNSUPPORTED;
   if (lda < (trans_a ? M : K) || ldb < (trans_b ? K : N) || ldc < N) return EG_ERR_UNSUPPORTED;
-  if (eg::sw::on("EG_NO_SPLIT_GEMM")) return EG_ERR_UNSUPPORTED;
+  if (eg::sw::on(eg::Sw::NO_SPLIT_GEMM)) return EG_ERR_UNSUPPORTED;
   // Shape gate: whole 256 x 256 tiles that fill the chip at least once and K >= 2048 (smaller products keep the exact path:
   // none of them is bound by matrix cycles the way a full round is), and an exact product that is one launch (the fallback).
   if (M % BM != 0 || N % BN != 0 || K % 32 != 0 || K < 2048) return EG_ERR_UNSUPPORTED;
@@ -569,7 +569,7 @@ int sgemm_split(eg_ctx* ctx, int trans_a, int trans_b, long M, long N, long K, c
   const SplitOperand oa = {A, lda, M, trans_a ? 0 : 1, pa};
   const SplitOperand ob = {B, ldb, N, trans_b ? 1 : 0, pb};
   // tiles for an operand whose k runs along ld, when its rows can be read 16 bytes at a time
-  const bool scalar = eg::sw::on("EG_SPLIT_PASS_SCALAR");
+  const bool scalar = eg::sw::on(eg::Sw::SPLIT_PASS_SCALAR);
   const int tiled = (!scalar && !oa.kc && lda % 4 == 0 ? 1 : 0) | (!scalar && !ob.kc && ldb % 4 == 0 ? 2 : 0);
   if (tiled) {
     const long blocks = (long)TILE_BLOCKS_PER_CU * ctx->compute_units;
@@ -596,7 +596,7 @@ int sgemm_split(eg_ctx* ctx, int trans_a, int trans_b, long M, long N, long K, c
   g.tiles_m = (int)(M / BM);
   g.tiles_n = (int)(N / BN);
   g.accumulate = accumulate;
-  g.skew = eg::sw::present("EG_GEMM_NO_SKEW") ? 0 : 1;
+  g.skew = eg::sw::on(eg::Sw::GEMM_NO_SKEW) ? 0 : 1;
   g.flag = ctx->split_flag;
   g.epoch = epoch;
   hipLaunchKernelGGL(split_gemm_kernel, dim3((unsigned)(g.tiles_m * g.tiles_n)), dim3(NT), 0, ctx->stream, g);

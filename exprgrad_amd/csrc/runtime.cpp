@@ -19,13 +19,7 @@ namespace eg {
 // library call uses it, and models do the same with the parts of their result arena that the
 // kernels are supposed to overwrite completely.  A read of memory nobody wrote then shows up as NaN
 // in the result instead of as whatever an earlier launch left there.
-bool poison_enabled() {
-  static const bool on = [] {
-    const char* e = eg::sw::raw("EG_POISON");
-    return e && e[0] && e[0] != '0';
-  }();
-  return on;
-}
+bool poison_enabled() { return eg::sw::on(eg::Sw::POISON); }
 
 static int poison_block(eg_ctx* ctx, void* p, size_t bytes) {
   if (!poison_enabled() || !p || !bytes) return EG_OK;
@@ -111,7 +105,7 @@ int kernels_compile_batch(eg_ctx* ctx, const char* label, const char* source, co
   std::vector<char> code;
   int rc = rtc::compile(label, source, ctx->arch, code);
   if (rc) return rc;
-  if (const char* dump = eg::sw::raw("EG_DUMP_CODE")) {  // debugging aid: the code object, for llvm-objdump -d
+  if (const char* dump = eg::sw::text(eg::Sw::DUMP_CODE)) {  // debugging aid: the code object, for llvm-objdump -d
     if (FILE* fp = fopen((std::string(dump) + "/" + label + ".co").c_str(), "wb")) {
       fwrite(code.data(), 1, code.size(), fp);
       fclose(fp);

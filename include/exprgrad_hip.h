@@ -75,11 +75,15 @@ int eg_device_props(int device, int* compute_units, int* clock_khz, int64_t* hbm
 int eg_compiler_info(char* text, size_t cap);
 /* Run-time compilations of this process: served from the on-disk cache / compiled, and the seconds spent compiling. */
 int eg_kernel_cache_stats(int64_t* hits, int64_t* misses, double* compile_seconds);
-/* Environment switches (csrc/switches.cpp): the library honours exactly the names of ONE table — every optimisation can
+/* Environment switches (csrc/switches.hpp): the library honours exactly the names of ONE list - every optimisation can
  * be turned off (class "execution"), detectors and dumps ("detector"), the data-parallel and run-time-compiler settings,
- * and measurement aids ("tuning") that are read only under EG_TUNING=1.  The environment is read once, at first use;
- * eg_switches_reload re-reads it (a host that changes a variable between two calls).  eg_switch_table writes
- * "<name>\t<class>\t<purpose>\n" per switch into text (at most cap - 1 bytes) and returns the length of the whole table.
+ * and measurement aids ("tuning") that are read only under EG_TUNING=1.  An on / off switch is ON when it is set, not
+ * empty and does not begin with '0': NAME=0 and NAME= are off, for every such switch.  The environment is read at first
+ * use and again by eg_switches_reload (a host that changes a variable between two calls, not during one); after it every
+ * read sees the new value - a model's plan keeps the switches it was made under, a launch reads its own on every call.
+ * Only EG_HIPRTC_LIB, EG_KERNEL_CACHE and EG_NO_KERNEL_CACHE are fixed at first use (the compiler library and the cache
+ * directory are opened once).  eg_switch_table writes "<name>\t<class>\t<purpose>\n" per switch into text (at most
+ * cap - 1 bytes) and returns the length of the whole table.
  * No reference counterpart (its only switches are compile-time defines: -d:opencl, -d:exprgrad_fast_math). */
 int eg_switches_reload(void);
 int64_t eg_switch_table(char* text, size_t cap);

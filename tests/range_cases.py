@@ -493,7 +493,7 @@ def colsum_cases(patterns=COLSUM_PATTERNS, env=None):
 
 
 def colsum_no_slab_cases():
-    """The aligned patterns again with the slab sum switched off (read once per process: a child process runs them)."""
+    """The aligned patterns again with the slab sum switched off (a child process that starts with the switch set runs them)."""
     return colsum_cases(("aligned",), {"EG_NO_SLAB_SUM": "1"})
 
 

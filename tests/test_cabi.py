@@ -93,9 +93,12 @@ def test_null_handles_are_errors_with_a_message():
 
 
 def test_switches_are_one_closed_table():
-    """Every environment variable the library reads is a row of csrc/switches.cpp: no getenv() anywhere else (rtc.cpp's
-    HOME / XDG_CACHE_HOME for the cache directory excepted), every name passed to eg::sw::raw / on / present / integer /
-    real is in the table, every row of the table is read somewhere, and DESIGN.md documents every row."""
+    """Every environment variable the library reads is a row of csrc/switches.hpp: no getenv() anywhere else (rtc.cpp's
+    HOME / XDG_CACHE_HOME for the cache directory excepted), every row of the table is read somewhere (as eg::Sw::NAME), and
+    DESIGN.md documents every row.  That every name read is in the table is now the compiler's claim: the accessors take an
+    eg::Sw id, and a name outside the list does not compile.  And nobody keeps a copy: no static in csrc/ is initialised from
+    eg::sw, except the rows that are fixed at first use (rtc.cpp: the kernel cache's two; EG_HIPRTC_LIB is read under its
+    call_once)."""
     import glob
     import re
     from exprgrad_amd import _lib
@@ -103,6 +106,7 @@ def test_switches_are_one_closed_table():
     names = [t[0] for t in table]
     assert len(names) == len(set(names)) and all(len(t) == 3 and t[1] in ("execution", "data-parallel", "compiler", "detector", "tuning") for t in table)
     used = set()
+    latched = []
     src = os.path.join(ROOT, "exprgrad_amd", "csrc")
     for path in glob.glob(os.path.join(src, "**", "*"), recursive=True):
         if not path.endswith((".cpp", ".hip", ".hpp")) or os.sep + "build" + os.sep in path:
@@ -113,12 +117,21 @@ def test_switches_are_one_closed_table():
         if base == "rtc.cpp":
             assert sorted(raw_env) == ["HOME", "XDG_CACHE_HOME"], raw_env
         elif base not in ("switches.cpp", "switches.hpp"):
-            assert not raw_env and "getenv(" not in text.replace("eg::sw::", ""), (base, raw_env)
-        used.update(re.findall(r'sw::(?:raw|on|present|integer|real)\("([A-Z_0-9]+)"', text))
-        used.update(re.findall(r'env_on\("([A-Z_0-9]+)"', text))
-        used.update(re.findall(r'\{"(EG_[A-Z_0-9]+)", "EG_', text))          # a loop over several names
-        used.update(re.findall(r', "(EG_[A-Z_0-9]+)"\}\)', text))
+            assert not raw_env and "getenv(" not in text, (base, raw_env)
+        if base not in ("switches.cpp", "switches.hpp"):
+            used.update("EG_" + n for n in re.findall(r'\bSw::([A-Z_0-9]+)', text))
+        for m in re.finditer(r'\b(?:static|thread_local)\b', text):
+            # the declaration up to its semicolon (one inside the braces of a lambda initialiser does not end it)
+            depth, end = 0, m.end()
+            while end < len(text) and not (text[end] == ";" and depth == 0):
+                depth += {"{": 1, "}": -1}.get(text[end], 0)
+                if depth < 0 or (text[end] == "{" and "=" not in text[m.end():end]):
+                    break                     # a function's body, or the end of the scope: no initialiser
+                end += 1
+            if "sw::" in text[m.end():end]:
+                latched.append((base, re.findall(r'Sw::([A-Z_0-9]+)', text[m.end():end])))
     assert used <= set(names), sorted(used - set(names))
     assert set(names) - used <= {"EG_TUNING"}, sorted(set(names) - used)
+    assert sorted(latched) == [("rtc.cpp", ["KERNEL_CACHE"]), ("rtc.cpp", ["NO_KERNEL_CACHE"])], latched
     design = open(os.path.join(ROOT, "DESIGN.md")).read()
     assert [n for n in names if n not in design] == []

@@ -100,7 +100,7 @@ print("CHILD-OK")
 
 
 def test_the_same_step_on_the_generated_kernels():
-    """EG_CONV_NO_MFMA64=1 is the parent route; switches are read once per process, so the step runs in a fresh one."""
+    """EG_CONV_NO_MFMA64=1 is the parent route; the step runs in a fresh process that starts with the switch set."""
     env = dict(os.environ, EG_CONV_NO_MFMA64="1")
     out = subprocess.run([sys.executable, "-c", CHILD.format(tests=os.path.join(ROOT, "tests"))], cwd=ROOT, env=env, capture_output=True, text=True,
                          timeout=600)

@@ -12,7 +12,7 @@ restatement; tests/test_generated_cases_cpu.py holds those three to each other):
     default   in this process, through whatever groups the planner forms (the small and map groups of rowfuse_small.cpp emit
               many of these kernels with code of their own); the plan is printed, not asserted.
 
-The three switches are read once per process, so the first two runs are one fresh child process each (subprocess of
+The first two runs are one fresh child process each, started with its switches set (subprocess of
 sys.executable, one at a time, under a time limit); a child that fails in any way fails its tests and no other child is
 started.  Gates: tests/parity.py (Trio.check: 1e-5 of the exact value, the direct gate against the oracle), the bound of
 tests/test_gpu_f64.py for compile[float64], and generated_cases.check_against_numpy on the WHOLE result tensor — exact cases

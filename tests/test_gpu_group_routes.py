@@ -8,7 +8,7 @@ table (TOL on the whole tensor); a second run gives the same bits; and a tensor 
 either refused by read_tensor or equal to the reference — and equal to it after keep_values(True), with the output's bits
 unchanged.
 
-One child process with EG_NO_ROWFUSE=1 (read once per process) runs the whole table without groups: the unfused side of
+One child process that starts with EG_NO_ROWFUSE=1 runs the whole table without groups: the unfused side of
 every comparison, through the same gates.  Same bits are asserted only where the code's own comments claim the same
 operations in the same order: EG_NO_ROW_DIRECT against `direct` and the in-kernel fold against row_finalize on the same grid
 (rowfuse_row.cpp), EG_SAMPLE_KEEP_BARRIERS / EG_SAMPLE_NO_STAGE / EG_NO_NARROW_INDEX against the default sample kernel

@@ -15,8 +15,8 @@ Which kernel or branch a case reaches
                       chunk_range's second trip of a block needs the grid cap of 32 blocks per CU: the "large" test.
     reduce.hip        eg_sum: vector partials for n >= 4 and an aligned input.  eg_rowsum: range_cases.ROWSUM_SHAPES.
                       eg_colsum: range_cases.COLSUM_ROUTES lists first and second pass of every case (all six pairs of
-                      vec / scalar with slab / tree / thread occur); EG_NO_SLAB_SUM is read once per process, so the
-                      aligned patterns run again in a child process with the slab sum off (tree and thread finals
+                      vec / scalar with slab / tree / thread occur); the aligned patterns run
+                      again in a child process that starts with EG_NO_SLAB_SUM=1, the slab sum off (tree and thread finals
                       behind a vector first pass).  eg_colsum_f64 has a single form.
     convolutions      the comments of range_cases.CONV_SHAPES, row by row, read from the dispatch code for 256 compute
                       units (the library reports no route, so the routes are a reading of the code, not an assertion).  Not reached by any row: conv2_direct.cpp's switch of its loads on the image's alignment
@@ -167,7 +167,7 @@ def test_column_sum_routes_on_this_device(gpu_ctx):
 
 
 def test_column_sums_without_the_slab_sum():
-    """reduce.hip reads EG_NO_SLAB_SUM once per process (a function-local static), so the pass runs in a child."""
+    """The pass again with EG_NO_SLAB_SUM=1, in a child process that starts with the switch set."""
     env = dict(os.environ, EG_NO_SLAB_SUM="1")
     done = subprocess.run([sys.executable, os.path.abspath(__file__), "no-slab-pass"], env=env, capture_output=True, text=True, timeout=300)
     assert done.returncode == 0 and "no-slab pass ok" in done.stdout, done.stdout[-3000:] + done.stderr[-3000:]

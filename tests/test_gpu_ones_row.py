@@ -52,8 +52,8 @@ def test_bias_gradient_as_the_last_row_of_the_weight_gradient(gpu_ctx, monkeypat
 
 
 def test_fold_can_be_switched_off_and_agrees(gpu_ctx):
-    """EG_NO_ONES_ROW is read once per process, so the unfused path is exercised by its own fallback: a
-    caller-owned input that is not 16-byte aligned disqualifies the LDS-DMA loop at run time, and the
+    """EG_NO_ONES_ROW is read when a plan is made (test_plan_switch_unfolds_and_agrees flips it); here the unfused
+    path is exercised by its own fallback: a caller-owned input that is not 16-byte aligned disqualifies the LDS-DMA loop at run time, and the
     launch falls back to contraction + column sum."""
     torch = pytest.importorskip("torch")
     from exprgrad_amd import model as egm

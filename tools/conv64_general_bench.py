@@ -1,6 +1,6 @@
 """float64 convolutions that only the implicit-GEMM kernel takes (csrc/kernels/conv2_f64_mfma.hip): each role through the C
 entry points, and a one-layer model (conv2 -> mse -> gradientDescent) with the kernel on and with EG_CONV_NO_MFMA64=1 (the
-generated kernels: the route of the commit before the kernel).  Switches are read once per process, so the two model runs
+generated kernels: the route of the commit before the kernel).  Each of the two model runs starts with its switches set: they
 are child processes of this one call, alternating, three rounds each.
 
 Method: warm-up launches, then events around `reps` launches on the context's stream; operands rotate through enough

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Prints the markdown table of DESIGN.md section 4 "Switches" from the library's own table (eg_switch_table,
-csrc/switches.cpp): python tools/switch_table.py"""
+csrc/switches.hpp): python tools/switch_table.py"""
 import os
 import sys
 
