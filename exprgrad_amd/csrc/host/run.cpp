@@ -476,8 +476,12 @@ std::string capture_key(eg_model* m, TargetState& ts) {
   std::ostringstream key;
   for (auto& in : m->inputs)
     if (in.second.bound) key << in.first << "=" << (const void*)in.second.device << ";";
+  // the scale as its bit pattern: six significant digits print 0.5f and 0.5000004f (1/3000000 and 1/3000001) alike, and a
+  // key that says "same" replays the graph that holds the other scale
+  uint32_t scale_bits;
+  memcpy(&scale_bits, &m->grad_scale, sizeof(scale_bits));
   key << "w" << m->ctx->workspace << "x" << m->ctx->aux << "s" << m->ctx->side_workspace << "y" << m->ctx->side_aux << "b"
-      << (void*)ts.bucket << "g" << m->grad_scale << "e" << m->epoch;
+      << (void*)ts.bucket << "g" << std::hex << scale_bits << std::dec << "e" << m->epoch;
   return key.str();
 }
 

@@ -369,7 +369,8 @@ int eg_model_run_update(eg_model* model, const char* target);
 int eg_model_fit(eg_model* model, const char* target, int n_inputs, const char* const* names, const float* const* data,
                  const int* on_device, const int* ranks, const int64_t* shapes8, int64_t batch_size);
 /* Scale applied to the seed gradient gradLoss (passes.nim:594-596) — B_local/B_global for
- * batch-mean losses under data parallelism.  Default 1. */
+ * batch-mean losses under data parallelism.  Default 1.
+ * A scale that differs from the last one in any bit sends the next run of every range back to an eager run and a new capture. */
 int eg_model_set_grad_scale(eg_model* model, float scale);
 
 /* readOutput (model.nim:370-376): shape of / blocking copy of the target's output tensor. */
