@@ -31,8 +31,9 @@ void inline_producers(eg_model* m, TargetState& ts, bool batched_gemm) {
     GemmMatch g;
     ConvMatch c;
     BatchedGemmMatch bg;
+    Batched2GemmMatch bg2;
     return k.is_seed || match_gemm(k, g) || (!prog.f64 && match_conv(k, c)) ||
-           (batched_gemm && match_batched_gemm(k, bg));
+           (batched_gemm && (match_batched_gemm(k, bg) || (!prog.f64 && match_batched2_gemm(k, bg2))));
   };
   for (size_t p = 0; p < t.live.size(); ++p) {
     if (ts.lowered[p].absorbed || (int)p == t.first_update) continue;
@@ -256,6 +257,18 @@ int lower_target(eg_model* m, TargetState& ts) {
       lo.gemm.trans_b = lo.bgemm.trans_b;
       continue;
     }
+    // a product with two batch indices, the head index inside the rows included: one eg_sgemm_batched2 launch, stand-alone
+    // like the above.  (float64: no such entry yet — the generated kernel over `double` stays.)
+    if (batched_gemm && !m->prog.f64 && match_batched2_gemm(k, lo.bgemm2)) {
+      lo.kind = StepKind::GemmBatched;
+      lo.standalone = true;
+      lo.two_batch = true;
+      lo.gemm.a_read = lo.bgemm2.a_read;
+      lo.gemm.b_read = lo.bgemm2.b_read;
+      lo.gemm.trans_a = lo.bgemm2.trans_a;
+      lo.gemm.trans_b = lo.bgemm2.trans_b;
+      continue;
+    }
     // (float64: no library convolution yet — conv2 and its gradients run as generated kernels over `double`)
     if (!m->prog.f64 && match_conv(k, lo.conv)) {
       lo.kind = lo.conv.role == ConvMatch::Forward     ? StepKind::Conv
@@ -312,7 +325,7 @@ void describe(eg_model* m) {
       const Lowered& lo = ts.lowered[p];
       const Kernel& k = ts.target->all[lo.all_index];
       const char* kind = lo.absorbed ? "fused-into-previous"
-                         : lo.kind == StepKind::GemmBatched ? "eg_bgemm"
+                         : lo.kind == StepKind::GemmBatched ? (lo.two_batch ? "eg_bgemm2" : "eg_bgemm")
                          : lo.kind == StepKind::Gemm && lo.standalone ? (lo.bgemm.row_k ? "gemm(batch rows collapsed into k)" : "gemm(batch rows collapsed into m)")
                          : lo.kind == StepKind::Gemm ? (lo.bias_tensor ? "gemm+bias" : "gemm")
                          : lo.kind == StepKind::Conv ? "conv2"

@@ -155,6 +155,69 @@ bool match_batched_gemm(const Kernel& k, BatchedGemmMatch& m) {
   return false;
 }
 
+// s[b,h,i,j] += q[b,i,h,k] * kk[b,j,h,k], o[b,i,h,d] += p[b,h,i,j] * v[b,j,h,d] and their derived forms (match.hpp): two
+// batch registers in any position but the last.  An operand that ends in a batch register has no unit-stride matrix axis
+// and is not a match.
+bool match_batched2_gemm(const Kernel& k, Batched2GemmMatch& m) {
+  if (!k.index_instrs.empty()) return false;
+  if (k.instrs.size() != 1 || k.instrs[0].kind != IK::Mul || k.result != k.instrs[0].res) return false;
+  if (k.reads.size() != 2 || k.loops.size() != 5 || !k.setup.empty()) return false;
+  for (auto& lp : k.loops)
+    if (lp.has_bounds) return false;
+  const std::vector<int>& args = k.instrs[0].args;
+  if (!((args[0] == k.reads[0].reg && args[1] == k.reads[1].reg) || (args[0] == k.reads[1].reg && args[1] == k.reads[0].reg)))
+    return false;
+  std::vector<int> w, r[2];
+  if (!bare_dims(k.write, w) || !bare_dims(k.reads[0], r[0]) || !bare_dims(k.reads[1], r[1])) return false;
+  for (const std::vector<int>* regs : {&w, &r[0], &r[1]}) {
+    if (regs->size() != 4) return false;
+    for (int reg : *regs)
+      if (loop_index(k, reg) < 0) return false;
+  }
+  auto pos = [](const std::vector<int>& regs, int reg) {
+    for (int d = 0; d < 4; ++d)
+      if (regs[d] == reg) return d;
+    return -1;
+  };
+  // the write's registers: in both reads (batch), or in exactly one (m, n); n is the last one
+  std::vector<int> batch;
+  int mm = 0;
+  const int n = w[3];
+  for (int reg : w) {
+    const bool in0 = pos(r[0], reg) >= 0, in1 = pos(r[1], reg) >= 0;
+    if (in0 && in1) batch.push_back(reg);
+    else if (in0 != in1 && reg != n) mm = reg;
+    else if (in0 == in1) return false;
+  }
+  if (batch.size() != 2 || !mm || n == batch[0] || n == batch[1]) return false;
+  const int b = pos(r[0], n) >= 0 ? 0 : 1, a = 1 - b;   // the read that names n is B: the product commutes
+  if (pos(r[a], mm) < 0) return false;
+  int kk = 0;
+  for (auto& lp : k.loops)
+    if (pos(w, lp.reg) < 0) kk = lp.reg;
+  if (!kk || pos(r[a], kk) < 0 || pos(r[b], kk) < 0) return false;
+  if ((r[a][3] != mm && r[a][3] != kk) || (r[b][3] != n && r[b][3] != kk)) return false;
+  Batched2GemmMatch out;
+  out.a_read = a;
+  out.b_read = b;
+  out.trans_a = r[a][3] == mm;
+  out.trans_b = r[b][3] == kk;
+  out.li = loop_index(k, mm);
+  out.lj = loop_index(k, n);
+  out.lk = loop_index(k, kk);
+  const std::vector<int>* ops[3] = {&r[a], &r[b], &w};
+  const int rows[3] = {out.trans_a ? kk : mm, out.trans_b ? n : kk, mm};
+  for (int o = 0; o < 3; ++o) {
+    for (int q = 0; q < 2; ++q) {
+      out.lb[q] = loop_index(k, batch[q]);
+      out.batch_dim[o][q] = pos(*ops[o], batch[q]);
+    }
+    out.row_dim[o] = pos(*ops[o], rows[o]);
+  }
+  m = out;
+  return true;
+}
+
 // out[y,x] += bias[x] on the tensor the preceding contraction wrote   dnn.nim:22-24
 bool match_bias(const Kernel& k, int tensor) {
   if (!k.index_instrs.empty()) return false;

@@ -34,10 +34,25 @@ struct BatchedGemmMatch {
   int lg = 0, li = 0, lj = 0, lk = 0;  // loop indices of g, m, n, k (collapsed: lg, and li (row_k: lk), are the two collapsed loops)
 };
 
+// A `++=` product with two batch indices anywhere but last (match_batched2_gemm): five loops, the write and both reads of
+// rank 4 over bare registers.  Two registers are in all three operands (the batch registers), m is in the write and A, n in
+// the write and B, k in both reads; every operand ends in one of its two matrix registers, the write in n:
+//   s[b,h,i,j] ++= q[b,i,h,k] * kk[b,j,h,k]   NT        o[b,i,h,d] ++= p[b,h,i,j] * v[b,j,h,d]   NN
+// trans_a / trans_b as for GemmMatch.  Operands are indexed 0 = A, 1 = B, 2 = the write.
+struct Batched2GemmMatch {
+  int a_read = 0, b_read = 0;  // indices into k.reads
+  bool trans_a = false, trans_b = false;
+  int lb[2] = {0, 0};          // loop indices of the batch registers, in the order the write names them
+  int li = 0, lj = 0, lk = 0;  // loop indices of m, n, k
+  int batch_dim[3][2] = {};    // per operand: the dimensions that lb[0] and lb[1] index
+  int row_dim[3] = {};         // per operand: the dimension of its matrix register that is not the last one
+};
+
 bool bare2(const Op& op, int& r0, int& r1);
 int loop_index(const Kernel& k, int reg);
 bool match_gemm(const Kernel& k, GemmMatch& m);
 bool match_batched_gemm(const Kernel& k, BatchedGemmMatch& m);
+bool match_batched2_gemm(const Kernel& k, Batched2GemmMatch& m);
 bool match_bias(const Kernel& k, int tensor);
 bool match_conv(const Kernel& k, ConvMatch& m);
 

@@ -274,7 +274,9 @@ const char* eg_model_launch_text(eg_model* m, const char* target) {
         }
         break;
       case StepKind::GemmBatched:
-        os << "eg_bgemm " << (L.trans_a ? "T" : "N") << (L.trans_b ? "T" : "N") << " " << L.batch << " x " << L.M << "x" << L.N << "x" << L.K
+        os << (L.batch1 > 0 ? "eg_bgemm2 " : "eg_bgemm ") << (L.trans_a ? "T" : "N") << (L.trans_b ? "T" : "N") << " " << L.batch;
+        if (L.batch1 > 0) os << "x" << L.batch1;
+        os << " x " << L.M << "x" << L.N << "x" << L.K
            << " -> t" << L.c_tensor << (L.accumulate ? " accumulate" : "");
         break;
       case StepKind::Conv: os << "conv2 -> t" << L.c_tensor << (L.accumulate ? " accumulate" : ""); break;

@@ -35,7 +35,8 @@ namespace model {
 using namespace eg::kd;
 using eg::set_error;
 
-// GemmBatched: one product per leading batch index in one launch (kernels/gemm_batched.hip)
+// GemmBatched: one product per leading batch index in one launch (kernels/gemm_batched.hip); with Launch::batch1 > 0 one
+// product per pair of batch indices (kernels/gemm_batched2.hip), treated alike everywhere but in the call itself
 // WideRows: a row group with one wave per sample (rowfuse.hpp); Launch::row_group indexes Plan::row_groups as for RowFused
 enum class StepKind { Gemm, Conv, ConvGradImage, ConvGradFilter, Seed, GenericA, GenericB, RowFused, SmallFused, GemmFused, SampleFused, WideRows, GemmBatched };
 
@@ -53,6 +54,10 @@ struct Lowered {
   // collapsed extents.  Both are stand-alone launches: no epilogue, no row / sample group, no side lane.
   BatchedGemmMatch bgemm;
   bool standalone = false;
+  // A product with two batch indices (match_batched2_gemm): kind GemmBatched, stand-alone like the above.  A plan whose
+  // shapes do not pass its checks runs the generated kernel instead (mode_a, generated when first needed).
+  bool two_batch = false;
+  Batched2GemmMatch bgemm2;
   int bias_tensor = 0;  // fused bias (0 = none)
   bool absorbed = false;  // this kernel was folded into the previous step
   bool inlined = false;   // an elementwise producer recomputed inside its consumers: never launched, never stored
@@ -76,7 +81,8 @@ struct Launch {
   long M = 0, N = 0, K = 0, lda = 0, ldb = 0, ldc = 0;
   int a_tensor = 0, b_tensor = 0, c_tensor = 0, bias_tensor = 0;
   bool trans_a = false, trans_b = false;
-  long batch = 0, stride_a = 0, stride_b = 0, stride_c = 0;   // GemmBatched
+  long batch = 0, stride_a = 0, stride_b = 0, stride_c = 0;   // GemmBatched (two batch indices: the outer index and its strides)
+  long batch1 = 0, stride_a1 = 0, stride_b1 = 0, stride_c1 = 0;   //   the inner index of a product with two (batch1 > 0)
   bool standalone = false;   // Gemm: a collapsed batched product (Lowered::standalone): never fused, grouped or overlapped
   long cN = 0, cH = 0, cW = 0, cC = 0, cF = 0, cFH = 0, cFW = 0;
   // Seed

@@ -236,6 +236,55 @@ bool copy_can_alias(eg_model* m, TargetState& ts, const Kernel& k, const KernelI
   return true;
 }
 
+// A product with two batch indices (match_batched2_gemm) as a launch: the checks of the rank-3 form — loops from 0, rank-4
+// shapes, every extent at least the loop extent that indexes it — and the leading dimensions and batch strides of the
+// dense row-major tensors: the stride of a dimension is the product of the later extents, whatever the loops cover.  The
+// batch register with the larger stride in C is the outer index.  false: the shapes do not suit, the generated kernel runs.
+bool plan_batched2(const Batched2GemmMatch& g, const Kernel& k, const KernelInfo& info, const Shapes& shapes, Launch& L) {
+  if (!info.ok) return false;
+  auto ext = [&](int loop) { return info.bounds[loop].second; };
+  for (int l : {g.lb[0], g.lb[1], g.li, g.lj, g.lk})
+    if (info.bounds[l].first != 0 || ext(l) < 1) return false;   // (batch1 > 0 marks the form: an empty product stays generated)
+  const Op* ops[3] = {&k.reads[g.a_read], &k.reads[g.b_read], &k.write};
+  long ld[3], bstride[3][2];
+  for (int o = 0; o < 3; ++o) {
+    auto sh = shapes.find(ops[o]->tensor);
+    if (sh == shapes.end() || sh->second.size() != 4) return false;
+    const std::vector<long>& dims = sh->second;
+    for (int d = 0; d < 4; ++d)
+      if (dims[d] < ext(loop_index(k, ops[o]->dims[d].only_register()))) return false;
+    auto stride = [&](int d) {
+      long st = 1;
+      for (int e = d + 1; e < 4; ++e) st *= dims[e];
+      return st;
+    };
+    ld[o] = stride(g.row_dim[o]);
+    for (int q = 0; q < 2; ++q) bstride[o][q] = stride(g.batch_dim[o][q]);
+  }
+  const int outer = bstride[2][0] >= bstride[2][1] ? 0 : 1, inner = 1 - outer;
+  L.kind = StepKind::GemmBatched;
+  L.standalone = true;
+  L.a_tensor = ops[0]->tensor;
+  L.b_tensor = ops[1]->tensor;
+  L.trans_a = g.trans_a;
+  L.trans_b = g.trans_b;
+  L.batch = ext(g.lb[outer]);
+  L.batch1 = ext(g.lb[inner]);
+  L.M = ext(g.li);
+  L.N = ext(g.lj);
+  L.K = ext(g.lk);
+  L.lda = ld[0];
+  L.ldb = ld[1];
+  L.ldc = ld[2];
+  L.stride_a = bstride[0][outer];
+  L.stride_a1 = bstride[0][inner];
+  L.stride_b = bstride[1][outer];
+  L.stride_b1 = bstride[1][inner];
+  L.stride_c = bstride[2][outer];
+  L.stride_c1 = bstride[2][inner];
+  return true;
+}
+
 int make_plan(eg_model* m, TargetState& ts, Plan& plan) {
   Target& t = *ts.target;
   Shapes& shapes = plan.shapes;
@@ -438,7 +487,9 @@ int make_plan(eg_model* m, TargetState& ts, Plan& plan) {
       continue;
     }
     bool overwrite = first && full_cover(k, info, wshape);
-    if (lo.standalone) {
+    if (lo.two_batch && plan_batched2(lo.bgemm2, k, info, shapes, L)) {
+      L.c_tensor = wt;
+    } else if (lo.standalone && !lo.two_batch) {
       // A product with a leading batch index (match_batched_gemm).  The tensors are dense row-major, so an item of a rank-3
       // operand [G, R, C] is a [R, C] matrix at g * R * C; collapsed forms read (g, i) as one row index, which needs the
       // collapsed loops to cover that extent of every rank-3 operand.
@@ -616,6 +667,13 @@ int make_plan(eg_model* m, TargetState& ts, Plan& plan) {
         int rc = fill_params(m, k, info, shapes, g.src, !overwrite, total, rtotal, chunk, plan.narrow_index, L.params);
         if (rc) return rc;
       } else {
+        if (lo.two_batch && lo.mode_a.src.name.empty()) {   // a product with two batch indices whose shapes did not suit (plan_batched2)
+          char name[64];
+          snprintf(name, sizeof(name), "eg_k%d_a", m->kernel_serial++);
+          int rc = generate_mode_a(k, name, lo.mode_a.src);
+          if (rc) return rc;
+        }
+        if (lo.two_batch && !lo.mode_a.handle) plan.pending.push_back({lo.mode_a.src.name, lo.mode_a.src.source, &lo.mode_a.handle});
         L.kind = StepKind::GenericA;
         L.generic = &lo.mode_a;
         L.blocks_x = (total + 255) / 256;

@@ -53,6 +53,11 @@ int sgemm_split(eg_ctx* ctx, int trans_a, int trans_b, long M, long N, long K, c
 // and the model layer's batched launches run.
 int sgemm_batched(eg_ctx* ctx, int trans_a, int trans_b, long batch, long M, long N, long K, const float* A, long lda, long stride_a,
                   const float* B, long ldb, long stride_b, float* C, long ldc, long stride_c, int accumulate, const float* bias);
+// batch0 x batch1 exact f32 products of one shape, X_{o,i} = X + o * stride_x0 + i * stride_x1 (gemm_batched2.hip): what
+// eg_sgemm_batched2 and the model layer's launches with two batch indices run.
+int sgemm_batched2(eg_ctx* ctx, int trans_a, int trans_b, long batch0, long batch1, long M, long N, long K, const float* A, long lda,
+                   long stride_a0, long stride_a1, const float* B, long ldb, long stride_b0, long stride_b1, float* C, long ldc, long stride_c0,
+                   long stride_c1, int accumulate, const float* bias);
 // The float64 twins (gemm_f64_mfma.hip): the plain product behind eg_dgemm, and `batch` of them in one launch — what
 // eg_dgemm_batched and a float64 model's batched launches run.  Strides and leading dimensions in doubles.
 int dgemm(eg_ctx* ctx, int trans_a, int trans_b, long M, long N, long K, const double* A, long lda, const double* B, long ldb, double* C,

@@ -624,6 +624,27 @@ bool batched_runs_as_loop(const GemmProblem& item, const GemmSwitches& sw) {
   return p.grid >= item.cus && p.route != Route::Small;
 }
 
+bool batched2_c_distinct(long batch0, long stride_c0, long batch1, long stride_c1, long M, long ldc, long N) {
+  struct Axis {
+    long extent, stride;
+  };
+  Axis axes[4] = {{batch0, stride_c0}, {batch1, stride_c1}, {M, ldc}, {N, 1}};
+  int n = 0;
+  for (const Axis& a : axes) {
+    if (a.extent < 1) return false;
+    if (a.extent > 1) axes[n++] = a;
+  }
+  std::sort(axes, axes + n, [](const Axis& x, const Axis& y) { return x.stride > y.stride; });
+  // from the fastest axis up: `span` is the largest offset the axes behind this one reach (128-bit: extents and strides are
+  // the caller's 64-bit numbers)
+  __int128 span = 0;
+  for (int q = n - 1; q >= 0; --q) {
+    if ((__int128)axes[q].stride < span + 1) return false;
+    span += (__int128)(axes[q].extent - 1) * axes[q].stride;
+  }
+  return true;
+}
+
 // ---- float64 -----------------------------------------------------------------------------------------------------------
 namespace {
 

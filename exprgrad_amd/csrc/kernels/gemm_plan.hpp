@@ -110,6 +110,14 @@ GemmPlan plan_gemm_batched(const GemmProblem& item, long batch, const GemmSwitch
 // products on their own routes.  Decided from the item alone, so that an item has the same bits whatever batch it is part of.
 bool batched_runs_as_loop(const GemmProblem& item, const GemmSwitches& sw);
 
+// The one rule for the C of a product with two batch indices (eg_sgemm_batched2): no two of its elements
+// C + o * stride_c0 + i * stride_c1 + m * ldc + n (o < batch0, i < batch1, m < M, n < N) share an address.  The axes
+// (batch0, stride_c0), (batch1, stride_c1), (M, ldc), (N, 1) without those of extent 1, ordered by stride, largest first:
+// every stride must be at least 1 + the sum of (extent - 1) * stride over the axes after it, i.e. one past the span of everything
+// that varies faster.  Sufficient, not necessary; it holds for nested layouts in any nesting order (o[b,i,h,d]: ldc = H * D,
+// stride_c1 = D) and fails for every tie, every stride below 1 and every extent below 1.
+bool batched2_c_distinct(long batch0, long stride_c0, long batch1, long stride_c1, long M, long ldc, long N);
+
 // ---- float64: the plain product (gemm_f64_mfma.hip, dgemm_kernel) -------------------------------------------------------
 // One eg_dgemm call as the planner sees it.  Leading dimensions in doubles.
 struct DgemmProblem {

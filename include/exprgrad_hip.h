@@ -179,6 +179,38 @@ int eg_sgemm_batched(eg_ctx* ctx, int trans_a, int trans_b, int64_t batch, int64
                      const float* A, int64_t lda, int64_t stride_a, const float* B, int64_t ldb, int64_t stride_b,
                      float* C, int64_t ldc, int64_t stride_c, int accumulate, const float* bias);
 
+/* eg_sgemm_batched with two batch indices:
+ *   C_{o,i}[m,n] (+)= sum_k opA_{o,i}(m,k) * opB_{o,i}(k,n) (+ bias[n])   for o in [0, batch0), i in [0, batch1),
+ *   X_{o,i} = X + o * stride_x0 + i * stride_x1.
+ * The multi-head products: s[b,h,i,j] ++= q[b,i,h,k] * kk[b,j,h,k] is trans_b = 1 with lda = ldb = H * K and
+ * stride_a1 = stride_b1 = K; o[b,i,h,d] ++= p[b,h,i,j] * v[b,j,h,d] writes a C whose items interleave (ldc = H * D,
+ * stride_c1 = D).  trans_a / trans_b, lda / ldb, accumulate and bias (shared by all items) as for eg_sgemm_batched: no alignment
+ * is required, elements of A and B outside an item's view are never read, elements of C outside the items are never
+ * written, C is not read when accumulate == 0, K == 0 writes bias or zeros, batch0 == 0, batch1 == 0 and empty products
+ * succeed and launch nothing.
+ * Strides of A and B: each of the four may be 0 (the operand is shared along that index); items of A or B may overlap
+ * or interleave freely, they are only read.  A negative one is EG_ERR_INVALID.
+ * C must not alias itself, and that is the only rule for ldc, stride_c0 and stride_c1: of the axes (batch0, stride_c0),
+ * (batch1, stride_c1), (M, ldc), (N, 1) without those of extent 1, ordered by stride, largest first, every stride is at
+ * least 1 + the sum of (extent - 1) * stride over the axes after it.  For nested strides that is what eg_sgemm_batched
+ * accepts; it also accepts C items that interleave, and rejects every tie and every 0.  Otherwise EG_ERR_INVALID.
+ * batch0 and batch1 must each be below 2^31 (EG_ERR_INVALID).
+ * 16-byte loads of an operand, and the store of whole tiles through LDS, are taken when what they need of item 0 holds
+ * for every item: the pointer 16-byte aligned and both of that operand's strides multiples of 4.
+ * One launch of batch0 x batch1 x tiles blocks on 64 x 64 tiles (kernels/gemm_batched2.hip), split along the flattened
+ * (o, i) range when it would exceed 2^22 blocks; items that fill the chip by themselves run as a loop of exact products.
+ * No k-slices, workspace or atomics, never the split-bf16 route: every output element is one k-ascending sum on the f32
+ * matrix instruction.  Bits:
+ *   - item (o, i) has the bits of an eg_sgemm_batched call with batch 1 on its three pointers;
+ *   - with stride_x0 == batch1 * stride_x1 for all three operands, the call has the bits of eg_sgemm_batched with
+ *     batch = batch0 * batch1. */
+int eg_sgemm_batched2(eg_ctx* ctx, int trans_a, int trans_b, int64_t batch0, int64_t batch1,
+                      int64_t M, int64_t N, int64_t K,
+                      const float* A, int64_t lda, int64_t stride_a0, int64_t stride_a1,
+                      const float* B, int64_t ldb, int64_t stride_b0, int64_t stride_b1,
+                      float* C, int64_t ldc, int64_t stride_c0, int64_t stride_c1,
+                      int accumulate, const float* bias);
+
 /* out[y,x] (+)= bias[x]   — dense's second kernel, dnn.nim:22-24. out is [rows, cols]. */
 int eg_bias_add(eg_ctx* ctx, int64_t rows, int64_t cols, const float* bias, float* out,
                 int accumulate);
