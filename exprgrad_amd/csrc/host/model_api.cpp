@@ -310,7 +310,13 @@ const char* eg_model_launch_text(eg_model* m, const char* target) {
       }
       case StepKind::WideRows: {
         const PlanRowGroup& pg = *plan.row_groups[L.row_group];
-        os << "wide-row-fused " << pg.g.name << " W=" << pg.g.W << " " << pg.g.kernel_index.size() << " kernels (";
+        os << "wide-row-fused " << pg.g.name << " W=" << pg.g.W << " ";
+        if (!pg.g.rows.empty()) {  // collapsed leading axes: the rows as their extents (a group over [B, W] prints none)
+          os << "rows=";
+          for (size_t d = 0; d < pg.g.rows.size(); ++d) os << (d ? "x" : "") << pg.g.rows[d];
+          os << " ";
+        }
+        os << pg.g.kernel_index.size() << " kernels (";
         for (size_t ki = 0; ki < pg.g.kernel_index.size(); ++ki) {
           const int wt = ts.target->all[pg.g.kernel_index[ki]].write.tensor;
           const std::string& nm = m->prog.tensors[wt].name;

@@ -362,6 +362,9 @@ int build_pending(eg_model* m);
 void describe(eg_model* m);
 // plan_groups.cpp
 int form_row_groups(eg_model* m, TargetState& ts, Plan& plan, const std::vector<KernelInfo>& infos, const std::map<int, int>& first_writer, std::vector<int>& group_of);
+// wide row groups over collapsed leading axes (rowfuse.hpp): formed first, entries of plan.row_groups like the others
+int form_collapsed_groups(eg_model* m, TargetState& ts, Plan& plan, const std::vector<KernelInfo>& infos, const std::map<int, int>& first_writer,
+                          std::vector<int>& group_of);
 constexpr int SAMPLE_GROUP_CODE = -1000000;  // group_of[] entry of a sample group's kernels
 int form_sample_group(eg_model* m, TargetState& ts, Plan& plan, const std::vector<KernelInfo>& infos, const std::map<int, int>& first_writer,
                       std::vector<int>& group_of, std::set<int>& needs_zero);

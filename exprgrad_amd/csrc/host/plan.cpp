@@ -380,7 +380,10 @@ int make_plan(eg_model* m, TargetState& ts, Plan& plan) {
   std::set<int> needs_zero;
   plan.sample_group.reset();
   if (fuse) {
-    int rc = form_sample_group(m, ts, plan, infos, first_writer, group_of, needs_zero);
+    // a softmax chain over collapsed leading axes is claimed first: a sample group would give it one block per sample
+    int rc = form_collapsed_groups(m, ts, plan, infos, first_writer, group_of);
+    if (rc) return rc;
+    rc = form_sample_group(m, ts, plan, infos, first_writer, group_of, needs_zero);
     if (rc) return rc;
   }
   int rc_groups = fuse ? form_row_groups(m, ts, plan, infos, first_writer, group_of) : EG_OK;

@@ -210,6 +210,7 @@ int form_sample_group(eg_model* m, TargetState& ts, Plan& plan, const std::vecto
       }
     }
     if (lo.standalone) ski[p].ok = false;   // a batched product keeps its own launch
+    if (group_of[p] != -1) ski[p].ok = false;   // a collapsed wide row group (form_collapsed_groups) took it: a run may form on either side
     if (ski[p].ok && ski[p].reduced && !ts.bucket_offset.count(k.write.tensor)) ski[p].ok = false;
     if (ski[p].ok && plan.alias.count(k.write.tensor)) ski[p].ok = false;
     // What belongs on the matrix cores stays there: a contraction whose two other extents are both >= 32 (a hidden layer of
@@ -241,7 +242,7 @@ int form_sample_group(eg_model* m, TargetState& ts, Plan& plan, const std::vecto
   // longest run
   int best_p = 0, best_q = 0, best_members = 0;
   for (int p = 0; p < limit;) {
-    if (!(ski[p].ok || (ts.lowered[p].absorbed && ts.lowered[p].inlined))) {
+    if (group_of[p] != -1 || !(ski[p].ok || (ts.lowered[p].absorbed && ts.lowered[p].inlined))) {
       ++p;
       continue;
     }
@@ -250,6 +251,7 @@ int form_sample_group(eg_model* m, TargetState& ts, Plan& plan, const std::vecto
     long work = 0;
     for (; q < limit; ++q) {
       const Lowered& lo = ts.lowered[q];
+      if (group_of[q] != -1) break;
       if (lo.absorbed && lo.inlined) continue;  // recomputed inside its readers: nothing to run
       if (!ski[q].ok) break;
       // a bias folded into the contraction in front of it is part of THAT launch: a member only next to its contraction
@@ -425,8 +427,14 @@ int form_sample_group(eg_model* m, TargetState& ts, Plan& plan, const std::vecto
 // wide row kernels over one width W in 65 .. 4096.  Decided from the shapes alone.  A group's launch is StepKind::WideRows:
 // it shares PlanRowGroup, the partial rows and row_finalize with the thread-per-sample groups, and takes no part in row
 // tails, deferred folds or the batch pipeline.
+//
+// `collapsed`: the groups over collapsed leading axes (rowfuse.hpp; form_collapsed_groups below) instead of those over
+// [B, W].  The rows of such a group are the leading extents of the rank-3 / rank-4 tensor its first member touches (g.B = R,
+// their product: the grid, the partial rows and row_finalize take the value as they take B), and the run must hold a sum
+// over the row — softmax and normalisation chains; a run of maps over a rank-4 tensor keeps its map group, epilogue or
+// sample group.
 static int form_wide_groups(eg_model* m, TargetState& ts, Plan& plan, const std::vector<KernelInfo>& infos,
-                            const std::map<int, int>& first_writer, std::vector<int>& group_of, long B) {
+                            const std::map<int, int>& first_writer, std::vector<int>& group_of, long B, bool collapsed) {
   Target& t = *ts.target;
   const Shapes& shapes = plan.shapes;
   const int n = (int)t.live.size();
@@ -434,6 +442,8 @@ static int form_wide_groups(eg_model* m, TargetState& ts, Plan& plan, const std:
   std::set<int> inlined;
   for (int p = 0; p < n; ++p)
     if (ts.lowered[p].inlined) inlined.insert(t.all[t.live[p]].write.tensor);
+  // (StepKind::Gemm only: a batched product, StepKind::GemmBatched, takes no epilogue, so a scale map over its result —
+  // the scores of an attention block — may begin a group)
   auto gemm_result = [&](int tensor, int before) {
     for (int s = 0; s < before; ++s)
       if (ts.lowered[s].kind == StepKind::Gemm && !ts.lowered[s].absorbed && t.all[t.live[s]].write.tensor == tensor) return true;
@@ -442,21 +452,25 @@ static int form_wide_groups(eg_model* m, TargetState& ts, Plan& plan, const std:
   constexpr long RED_MAX = 2 * WIDE_MAX_W + 64;  // floats of a partial row; four of them in LDS (at most 130 KB)
   int p = 0;
   while (p < n) {
-    const long W = group_of[p] == -1 ? wide_width_of(t.all[t.live[p]], shapes, B) : 0;
-    if (W < WIDE_MIN_W || W > WIDE_MAX_W) {
+    std::vector<long> lead;
+    const long W = group_of[p] == -1 ? wide_width_of(t.all[t.live[p]], shapes, B, collapsed ? &lead : nullptr) : 0;
+    if (W < WIDE_MIN_W || W > WIDE_MAX_W || (collapsed && lead.size() < 2)) {
       ++p;
       continue;
     }
+    const long R = collapsed ? prod(lead) : B;   // rows per group
     std::unique_ptr<PlanRowGroup> pg(new PlanRowGroup());
     RowGroup& g = pg->g;
-    g.B = B;
+    g.B = R;
     g.W = W;
+    if (collapsed) g.rows = lead;
     const long NJ = (W + 63) / 64;
     int q = p;
     while (q < n && group_of[q] == -1 && !(q != p && q == t.first_update) && !(p < t.first_update && q >= t.first_update && t.first_update >= 0)) {
       const Kernel& k = t.all[t.live[q]];
-      const WideKernelInfo wi = analyse_wide_kernel(m->prog, k, infos[t.live[q]], shapes, B, W);
+      const WideKernelInfo wi = analyse_wide_kernel(m->prog, k, infos[t.live[q]], shapes, R, W, collapsed ? &lead : nullptr);
       if (!wi.ok) break;
+      if (collapsed && ts.lowered[q].standalone) break;   // a batched product keeps its own launch
       // a bias folded into a library contraction is not available on its own
       if (ts.lowered[q].absorbed && !ts.lowered[q].inlined) break;
       // an elementwise map over a contraction's result is that contraction's epilogue candidate (plan_epilogue.cpp): a
@@ -476,9 +490,11 @@ static int form_wide_groups(eg_model* m, TargetState& ts, Plan& plan, const std:
         gt.tensor = op.tensor;
         bool row = false;
         for (auto& d : op.dims) row = row || (yreg && d.factor_of(yreg));
+        for (int l : wi.row_loops)   // collapsed rows: any of the row registers
+          for (auto& d : op.dims) row = row || d.factor_of(k.loops[l].reg);
         if (it != roles.end() && row != (gt.role == RowGroupTensor::RowLocal || gt.role == RowGroupTensor::RowExternal)) ok = false;
         if (row) {
-          gt.inner = prod(shapes.at(op.tensor)) / B;
+          gt.inner = prod(shapes.at(op.tensor)) / R;
           if (write) gt.role = RowGroupTensor::RowLocal;
           else if (it == roles.end()) gt.role = RowGroupTensor::RowExternal;
           if (!write && it == roles.end() && inlined.count(op.tensor)) ok = false;  // (its producer is not a member)
@@ -541,6 +557,11 @@ static int form_wide_groups(eg_model* m, TargetState& ts, Plan& plan, const std:
       return false;
     };
     bool usable = q - p >= 2 && row_kernels >= 2;
+    if (collapsed) {  // only around a sum over the collapsed rows
+      bool row_sum = false;
+      for (auto& wi : g.wide) row_sum = row_sum || (!wi.seed && wi.kind == WideKernelInfo::RowRed);
+      usable = usable && row_sum;
+    }
     for (auto& kv : g.tensors)  // a lane-local seed somebody outside the group wants
       if (kv.second.role == RowGroupTensor::SmallLocal && (used_after(kv.first) || written_outside_before(kv.first))) usable = false;
     if (!usable) {
@@ -567,7 +588,7 @@ static int form_wide_groups(eg_model* m, TargetState& ts, Plan& plan, const std:
     char name[64];
     snprintf(name, sizeof(name), "eg_wrows%d", m->kernel_serial++);
     g.name = name;
-    pg->nblocks = (int)((B + 255) / 256);  // the grid of a row group; a block's four waves share its 256 samples
+    pg->nblocks = (int)((R + 255) / 256);  // the grid of a row group; a block's four waves share its 256 samples
     int rc = generate_wide_group(t.all, shapes, g);
     if (rc) return rc;
     plan.pending.push_back({g.name, g.source, &pg->handle});
@@ -581,6 +602,21 @@ static int form_wide_groups(eg_model* m, TargetState& ts, Plan& plan, const std:
     p = q;
   }
   return EG_OK;
+}
+
+// Wide row groups over collapsed leading axes: the softmax between the two products of an attention block.  Called before
+// form_sample_group, which treats the positions taken here as taken and may form on either side: with 2 <= B <= 1280 it
+// would give the chain one block per b (8 blocks for 8 x 16 x 512 rows).  EG_NO_ROWFUSE=1 turns these off like every group.
+int form_collapsed_groups(eg_model* m, TargetState& ts, Plan& plan, const std::vector<KernelInfo>& infos,
+                          const std::map<int, int>& first_writer, std::vector<int>& group_of) {
+  if (!row_fusion_enabled()) return EG_OK;
+  long B = 0;
+  for (auto& in : m->inputs)
+    if (in.second.bound && !in.second.shape.empty()) {
+      B = in.second.shape[0];
+      break;
+    }
+  return form_wide_groups(m, ts, plan, infos, first_writer, group_of, B, true);
 }
 
 // Partition the live kernel list into row groups (rowfuse.hpp) and build their kernels.
@@ -808,7 +844,7 @@ int form_row_groups(eg_model* m, TargetState& ts, Plan& plan, const std::vector<
     p = q;
   }
   {
-    int rc = form_wide_groups(m, ts, plan, infos, first_writer, group_of, B);
+    int rc = form_wide_groups(m, ts, plan, infos, first_writer, group_of, B, false);
     if (rc) return rc;
   }
   // ---- small-kernel groups among what is left (encoded as -2 - index in group_of)

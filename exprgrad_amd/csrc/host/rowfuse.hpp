@@ -66,14 +66,32 @@ struct WideKernelInfo {
   bool raw = false;
   bool seed = false;
   enum Kind { Map, RowRed, ColRed, AllRed } kind = Map;
+  std::vector<int> row_loops;  // collapsed rows (below): indices into k.loops of the row registers, in operand position order
 };
 constexpr long WIDE_MIN_W = 65, WIDE_MAX_W = 4096;
 // floats of group state one lane may hold: ceil(W / 64) per [B, W] tensor written in the group and per [W] batch sum
 // (a [B] value or the seed is one value per wave and not counted); the generated kernels must not spill
 constexpr long WIDE_STATE_MAX = 128;
 // the width a wide group starting with `k` would have: dimension 1 of the first [B, W] tensor it touches (0: none)
-long wide_width_of(const Kernel& k, const Shapes& shapes, long B);
-WideKernelInfo analyse_wide_kernel(const Program& prog, const Kernel& k, const KernelInfo& info, const Shapes& shapes, long B, long W);
+//
+// Collapsed leading axes.  A dense row-major tensor [d0 .. d(r-2), W] of rank r in {3, 4} is R = d0 * .. * d(r-2) rows of W
+// floats, and [d0 .. d(r-2)] is one value per row: the softmax over the last axis of multi-head scores [B, H, I, J] is the
+// same chain over [B * H * I, J].  With `lead` given, wide_width_of also looks, where the kernel touches no [B, W] tensor,
+// for the first operand of the highest rank among 3 and 4 and reports its leading extents in *lead (R is their product;
+// rank 2: {B}, everything as without `lead`).  analyse_wide_kernel with those `lead` (two or three extents) and B = R:
+//   * up to r - 1 row loops and at most one column loop x over 0 .. W, none with explicit bounds, none used as a value, no
+//     computed indices;
+//   * every operand is a row tensor [lead.., W] indexed by the row registers, bare and in this order, then x; a per-row
+//     tensor [lead..] indexed by the same registers in the same order; a [W] tensor indexed by x; a single element; or the
+//     raw `{it}` form over R * W elements of row tensors;
+//   * which register is which is read from its POSITION in the row and per-row operands, never from its extent (I == J in
+//     self-attention; a leading extent may equal W): a register at two positions, or at different positions in two
+//     operands of one kernel, disqualifies the kernel.
+// The kinds are those above with "row" for "sample".  The planner forms such a group only around a reduction over the row
+// (plan_groups.cpp): softmax and normalisation chains; runs of maps over a rank-4 tensor keep their routes.
+long wide_width_of(const Kernel& k, const Shapes& shapes, long B, std::vector<long>* lead = nullptr);
+WideKernelInfo analyse_wide_kernel(const Program& prog, const Kernel& k, const KernelInfo& info, const Shapes& shapes, long B, long W,
+                                   const std::vector<long>* lead = nullptr);
 
 struct RowGroupTensor {
   int tensor = 0;
@@ -117,6 +135,8 @@ struct RowGroup {
   // Wide groups ("one wave per sample", below): W > 0, and `wide` holds the members' analysis instead of `infos`.
   long W = 0;
   std::vector<WideKernelInfo> wide;
+  // A wide group over collapsed leading axes: their extents (B is their product); empty for a group over [B, W].
+  std::vector<long> rows;
 };
 
 // Emit the fused kernel.  Arguments of the generated kernel:

@@ -3,19 +3,156 @@
 
 namespace eg::kd {
 
-long wide_width_of(const Kernel& k, const Shapes& shapes, long B) {
+long wide_width_of(const Kernel& k, const Shapes& shapes, long B, std::vector<long>* lead) {
   auto width = [&](const Op& op) -> long {
     auto it = shapes.find(op.tensor);
     return it != shapes.end() && it->second.size() == 2 && it->second[0] == B ? it->second[1] : 0;
   };
+  long w = 0;
   for (auto& rd : k.reads)
-    if (const long w = width(rd)) return w;
-  return width(k.write);
+    if (!w) w = width(rd);
+  if (!w) w = width(k.write);
+  if (!lead) return w;
+  lead->clear();
+  if (w) {  // a [B, W] tensor decides, as without `lead`
+    lead->push_back(B);
+    return w;
+  }
+  // collapsed leading axes: the first operand of the highest rank among 3 and 4 (a per-row operand has one dimension less)
+  const std::vector<long>* best = nullptr;
+  for (const Op* op : ops_of(k)) {
+    auto it = shapes.find(op->tensor);
+    if (it == shapes.end() || it->second.size() < 3 || it->second.size() > 4) continue;
+    if (!best || it->second.size() > best->size()) best = &it->second;
+  }
+  if (!best) return 0;
+  lead->assign(best->begin(), best->end() - 1);
+  return best->back();
 }
 
-WideKernelInfo analyse_wide_kernel(const Program& prog, const Kernel& k, const KernelInfo& info, const Shapes& shapes, long B, long W) {
+// A wide row kernel over collapsed leading axes (rowfuse.hpp): `lead` are the extents d0 .. d(r-2), W the row's width.
+static WideKernelInfo analyse_collapsed_kernel(const Program& prog, const Kernel& k, const KernelInfo& info, const Shapes& shapes,
+                                               const std::vector<long>& lead, long W) {
+  WideKernelInfo r;
+  const long R = prodv(lead);
+  const size_t nlead = lead.size();
+  if (nlead < 2 || nlead > 3 || R <= 0) return r;
+  const std::vector<const Op*> ops = ops_of(k);
+  for (const Op* op : ops)
+    if (!shapes.count(op->tensor)) return r;
+  auto state = [&](const Op* op) {
+    const TK kind = prog.tensors[op->tensor].kind;
+    return kind == TK::Param || kind == TK::Cache;
+  };
+  auto single = [&](const Op* op) {  // one element, addressed by constants
+    for (auto& d : op->dims)
+      if (!d.factors.empty()) return false;
+    return prodv(shapes.at(op->tensor)) == 1;
+  };
+  auto used_as_value = [&](int reg) {
+    for (auto& ins : k.instrs)
+      for (int a : ins.args)
+        if (a == reg) return true;
+    return false;
+  };
+  if (!k.setup.empty() || k.loops.empty() || k.loops.size() > nlead + 1) return r;
+  for (auto& l : k.loops)
+    if (l.has_bounds) return r;
+  std::vector<long> row_shape = lead;
+  row_shape.push_back(W);
+  bool any_raw = false;
+  for (const Op* op : ops) any_raw = any_raw || (op->raw && !single(op));
+  if (any_raw) {
+    // a raw map over R * W elements: it = row * W + x
+    if (k.loops.size() != 1 || info.bounds[0].first != 0 || info.bounds[0].second != R * W) return r;
+    const int it = k.loops[0].reg;
+    if (used_as_value(it)) return r;
+    for (const Op* op : ops) {
+      if (single(op)) continue;
+      if (!op->raw || op->dims.size() != 1 || op->dims[0].only_register() != it || state(op) || shapes.at(op->tensor) != row_shape) return r;
+    }
+    r.ok = true;
+    r.raw = true;
+    r.row_loop = 0;
+    r.row_loops = {0};
+    r.kind = single(&k.write) ? WideKernelInfo::AllRed : WideKernelInfo::Map;
+    return r;
+  }
+  // The registers by POSITION: the first row or per-row operand names them, every other one must agree.  Extents decide
+  // nothing (I == J, a leading extent equal to W): a [lead.., W] tensor has rank r, a [lead..] tensor rank r - 1 >= 2, a [W]
+  // tensor rank 1.
+  std::vector<int> regs(nlead, 0);
+  int x = 0;
+  bool named = false;
+  std::vector<int> kinds(ops.size(), 0);  // per op: 0 single element, 1 row tensor, 2 per-row tensor, 3 [W]
+  for (size_t o = 0; o < ops.size(); ++o) {
+    const Op* op = ops[o];
+    if (single(op)) {
+      kinds[o] = 0;
+      continue;
+    }
+    const std::vector<long>& shp = shapes.at(op->tensor);
+    if (op->raw || op->dims.size() != shp.size()) return r;
+    std::vector<int> at(op->dims.size());
+    for (size_t d = 0; d < op->dims.size(); ++d)
+      if (!(at[d] = op->dims[d].only_register())) return r;  // bare registers only
+    if (shp == row_shape || shp == lead) {
+      if (state(op)) return r;
+      kinds[o] = shp == row_shape ? 1 : 2;
+      for (size_t d = 0; d < nlead; ++d) {
+        if (named && regs[d] != at[d]) return r;  // another register at this position
+        regs[d] = at[d];
+      }
+      named = true;
+      if (kinds[o] == 1) {
+        if (x && x != at[nlead]) return r;
+        x = at[nlead];
+      }
+    } else if (shp.size() == 1 && shp[0] == W) {
+      kinds[o] = 3;
+      if (x && x != at[0]) return r;
+      x = at[0];
+    } else {
+      return r;
+    }
+  }
+  if (!named) return r;  // nothing indexed by the row
+  for (size_t d = 0; d < nlead; ++d) {
+    if (regs[d] == x) return r;
+    for (size_t e = 0; e < d; ++e)
+      if (regs[d] == regs[e]) return r;  // one register at two positions
+  }
+  // every loop is one of those registers, over its tensor extent; a loop no operand uses can only be x
+  r.row_loops.assign(nlead, -1);
+  for (size_t l = 0; l < k.loops.size(); ++l) {
+    const int reg = k.loops[l].reg;
+    if (used_as_value(reg)) return WideKernelInfo();
+    size_t d = 0;
+    while (d < nlead && regs[d] != reg) ++d;
+    const long extent = d < nlead ? lead[d] : W;
+    if (info.bounds[l].first != 0 || info.bounds[l].second != extent) return WideKernelInfo();
+    if (d < nlead) {
+      r.row_loops[d] = (int)l;
+    } else {
+      if ((x && x != reg) || r.col_loop >= 0) return WideKernelInfo();
+      r.col_loop = (int)l;
+    }
+  }
+  for (int l : r.row_loops)
+    if (l < 0) return WideKernelInfo();
+  if (x && r.col_loop < 0) return WideKernelInfo();
+  r.ok = true;
+  r.row_loop = r.row_loops[0];
+  const int wk = kinds[ops.size() - 1];  // (ops_of: the write is last)
+  r.kind = wk == 1 ? WideKernelInfo::Map : wk == 2 ? WideKernelInfo::RowRed : wk == 3 ? WideKernelInfo::ColRed : WideKernelInfo::AllRed;
+  return r;
+}
+
+WideKernelInfo analyse_wide_kernel(const Program& prog, const Kernel& k, const KernelInfo& info, const Shapes& shapes, long B, long W,
+                                   const std::vector<long>* lead) {
   WideKernelInfo r;
   if (!info.ok || B <= 0 || W < WIDE_MIN_W || W > WIDE_MAX_W || !k.index_instrs.empty() || k.f64) return r;
+  if (lead && lead->size() >= 2 && !k.is_seed) return prodv(*lead) == B ? analyse_collapsed_kernel(prog, k, info, shapes, *lead, W) : r;
   const std::vector<const Op*> ops = ops_of(k);
   for (const Op* op : ops)
     if (!shapes.count(op->tensor)) return r;
