@@ -321,6 +321,14 @@ void describe(eg_model* m) {
   for (auto& kv : m->targets) {
     TargetState& ts = kv.second;
     os << "target " << kv.first << " (" << ts.target->live.size() << " kernels)\n";
+    // forward attention chains (match_attention): one eg_attn launch when the plan fuses them (plan_attention.cpp)
+    std::vector<std::pair<int, int>> attn(ts.lowered.size(), {-1, -1});
+    for (int p = 0; !m->prog.f64 && p < (int)ts.lowered.size(); ++p) {
+      AttentionMatch am;
+      if (!match_attention(m->prog, *ts.target, p, am)) continue;
+      for (int s = p; s < p + am.n; ++s) attn[s] = {p, p + am.n - 1};
+      p += am.n - 1;
+    }
     for (size_t p = 0; p < ts.lowered.size(); ++p) {
       const Lowered& lo = ts.lowered[p];
       const Kernel& k = ts.target->all[lo.all_index];
@@ -335,6 +343,7 @@ void describe(eg_model* m) {
                          : (lo.b_capable ? "generic(map|split-reduce)" : "generic(map)");
       os << "  [" << p << "] " << kind;
       if (lo.kind == StepKind::Gemm || lo.kind == StepKind::GemmBatched) os << (lo.gemm.trans_a ? " T" : " N") << (lo.gemm.trans_b ? "T" : "N");
+      if (attn[p].first >= 0) os << " (eg_attn: one launch for kernels " << attn[p].first << ".." << attn[p].second << " when the plan fuses them)";
       os << " : " << to_text(k) << "\n";
     }
   }

@@ -48,6 +48,25 @@ struct Batched2GemmMatch {
   int row_dim[3] = {};         // per operand: the dimension of its matrix register that is not the last one
 };
 
+// The forward attention chain over consecutive live kernels of a target (match_attention.cpp):
+//   [0]       scores[b,h,i,j]  ++= q[..] * kk[..]              a product match_batched2_gemm takes as NT
+//   [1]       scaled[b,h,i,j]  ++= scores[b,h,i,j] * literal   optional, either operand order; absent: scale 1
+//   [n - 3]   sums[b,h,i]      ++= exp(e[b,h,i,j])             e: scaled, or scores without a scale map
+//   [n - 2]   softmax[b,h,i,j] ++= exp(e[b,h,i,j]) / sums[b,h,i]
+//   [n - 1]   context[..]      ++= softmax[b,h,i,j] * v[..]    a product match_batched2_gemm takes as NN, softmax its A
+// with every register of the three middle kernels bare and in the positions of the scores, no loop bounds, and every
+// intermediate tensor (scores, scaled, sums, softmax) a Result that exactly one live kernel of the target writes, no live
+// kernel outside the chain reads, and that is not the target's output.  (Gradient-bucket membership is the planner's check.)
+struct AttentionMatch {
+  int n = 0;                           // kernels of the chain: 5 with a scale map, 4 without
+  float scale = 1.f;
+  Batched2GemmMatch scores, context;   // of kernels [0] and [n - 1]
+  int t_scores = 0, t_scaled = 0, t_sums = 0, t_softmax = 0;   // t_scaled: 0 without a scale map
+  int t_q = 0, t_k = 0, t_v = 0, t_out = 0;
+};
+// The chain at live positions [p, p + m.n) of `t`?  why (optional): the reason of a refusal, a constant string.
+bool match_attention(const Program& prog, const Target& t, int p, AttentionMatch& m, const char** why = nullptr);
+
 bool bare2(const Op& op, int& r0, int& r1);
 int loop_index(const Kernel& k, int reg);
 bool match_gemm(const Kernel& k, GemmMatch& m);

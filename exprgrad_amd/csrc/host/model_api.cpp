@@ -279,6 +279,18 @@ const char* eg_model_launch_text(eg_model* m, const char* target) {
         os << " x " << L.M << "x" << L.N << "x" << L.K
            << " -> t" << L.c_tensor << (L.accumulate ? " accumulate" : "");
         break;
+      case StepKind::Attention: {
+        char scale[32];
+        snprintf(scale, sizeof(scale), "%g", (double)L.attn_scale);
+        os << "eg_attn " << L.batch << "x" << L.batch1 << " x " << L.M << "x" << L.N << "x" << L.K << "x" << L.attn_d << " scale=" << scale << " (";
+        for (size_t ki = 0; ki < L.attn_members.size(); ++ki) {
+          const int wt = ts.target->all[ts.target->live[L.attn_members[ki]]].write.tensor;
+          const std::string& nm = m->prog.tensors[wt].name;
+          os << (ki ? ", " : "") << (nm.empty() || nm == "-" ? "t" + std::to_string(wt) : nm);
+        }
+        os << ")" << (L.accumulate ? " accumulate" : "");
+        break;
+      }
       case StepKind::Conv: os << "conv2 -> t" << L.c_tensor << (L.accumulate ? " accumulate" : ""); break;
       case StepKind::ConvGradImage: os << "conv2-grad-image -> t" << L.c_tensor << (L.accumulate ? " accumulate" : ""); break;
       case StepKind::ConvGradFilter: os << "conv2-grad-filter -> t" << L.c_tensor << (L.accumulate ? " accumulate" : ""); break;
@@ -662,6 +674,9 @@ static int read_tensor(eg_model* m, TargetState& ts, int tid, void* host, int64_
   EG_REQUIRE(!(ts.last->sample_group && ts.last->sample_group->g.lds.count(tid)), EG_ERR_INVALID,
              "tensor %d lived in the LDS of a sample group's blocks in the last run's plan: its values were never stored "
              "(eg_model_keep_values(model, 1) makes the plans keep values)", tid);
+  EG_REQUIRE(!ts.last->attn_hidden.count(tid), EG_ERR_INVALID,
+             "tensor %d lived in the registers of an attention group's blocks in the last run's plan: its values were never stored "
+             "(eg_model_keep_values(model, 1) makes the plans keep values)", tid);
   float* p = tensor_ptr(m, ts, *ts.last, tid);
   // (no storage at all: the tensor of a producer that was inlined into its readers when the model was compiled)
   EG_REQUIRE(p, EG_ERR_INVALID, "tensor %d was not materialised by the last run", tid);
@@ -742,6 +757,9 @@ int eg_model_tensor_ptr(eg_model* m, const char* target, int tensor_id, float** 
              tensor_id);
   EG_REQUIRE(!(ts->last->sample_group && ts->last->sample_group->g.lds.count(tensor_id)), EG_ERR_INVALID,
              "tensor %d lived in the LDS of a sample group's blocks in the last run's plan: its values were never stored "
+             "(eg_model_keep_values(model, 1) makes the plans keep values)", tensor_id);
+  EG_REQUIRE(!ts->last->attn_hidden.count(tensor_id), EG_ERR_INVALID,
+             "tensor %d lived in the registers of an attention group's blocks in the last run's plan: its values were never stored "
              "(eg_model_keep_values(model, 1) makes the plans keep values)", tensor_id);
   float* const p = tensor_ptr(m, *ts, *ts->last, tensor_id);
   EG_REQUIRE(p || prod(s->second) == 0, EG_ERR_INVALID, "tensor %d was not materialised by the last run", tensor_id);

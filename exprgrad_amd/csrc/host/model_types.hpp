@@ -1,9 +1,11 @@
 // Types and internal interfaces of the model layer (group 3 of the C ABI), shared by its translation
 // units:
 //   match.cpp          library patterns (contraction, bias, convolution and its gradients)
+//   match_attention.cpp  the forward attention chain (scores, scale, softmax, context)
 //   lower.cpp          static lowering of a target, inlining, generated sources
 //   plan.cpp           per-shape plans: launch list, overwrite / accumulate, arena   (+ plan_check.cpp)
 //   plan_groups.cpp    row / small / map fusion groups
+//   plan_attention.cpp attention groups: a forward attention chain as one launch
 //   plan_epilogue.cpp  contraction + consumer epilogues
 //   plan_overlap.cpp   side-lane groups
 //   run.cpp            launches, HIP graphs
@@ -37,8 +39,9 @@ using eg::set_error;
 
 // GemmBatched: one product per leading batch index in one launch (kernels/gemm_batched.hip); with Launch::batch1 > 0 one
 // product per pair of batch indices (kernels/gemm_batched2.hip), treated alike everywhere but in the call itself
+// Attention: the forward attention chain (match_attention) as one eg_attention launch (kernels/attention_f32.hip), stand-alone
 // WideRows: a row group with one wave per sample (rowfuse.hpp); Launch::row_group indexes Plan::row_groups as for RowFused
-enum class StepKind { Gemm, Conv, ConvGradImage, ConvGradFilter, Seed, GenericA, GenericB, RowFused, SmallFused, GemmFused, SampleFused, WideRows, GemmBatched };
+enum class StepKind { Gemm, Conv, ConvGradImage, ConvGradFilter, Seed, GenericA, GenericB, RowFused, SmallFused, GemmFused, SampleFused, WideRows, GemmBatched, Attention };
 
 struct Generic {
   GenericSource src;
@@ -83,6 +86,11 @@ struct Launch {
   bool trans_a = false, trans_b = false;
   long batch = 0, stride_a = 0, stride_b = 0, stride_c = 0;   // GemmBatched (two batch indices: the outer index and its strides)
   long batch1 = 0, stride_a1 = 0, stride_b1 = 0, stride_c1 = 0;   //   the inner index of a product with two (batch1 > 0)
+  // Attention: a = q, b = kk, c = the context; M = I, N = J, K as it is; batch / batch1 and the strides as for GemmBatched
+  int v_tensor = 0;
+  long attn_d = 0, ldv = 0, stride_v = 0, stride_v1 = 0;
+  float attn_scale = 1.f;
+  std::vector<int> attn_members;   // live positions of the fused kernels, in order
   bool standalone = false;   // Gemm: a collapsed batched product (Lowered::standalone): never fused, grouped or overlapped
   long cN = 0, cH = 0, cW = 0, cC = 0, cF = 0, cFH = 0, cFW = 0;
   // Seed
@@ -186,6 +194,10 @@ struct Plan {
   // each element; stored as one bit per element (bit idx & 31 of 32-bit word idx >> 5, flat element index), in the
   // zeroed part of the arena.
   std::map<int, PredicateSpec> predicated;
+  // Attention groups (plan_attention.cpp): the launch of the group that starts at a live position, and the intermediates
+  // (scores, scaled, sums, softmax) that live in the registers of its blocks: no arena storage
+  std::map<int, Launch> attn_groups;
+  std::set<int> attn_hidden;
   std::vector<int> random_tensors;   // TensorRandom tensors the live kernels read: refilled on every run
   std::map<int, long> arena_offset;  // result tensor -> float offset in the arena
   long arena_floats = 0;
@@ -365,6 +377,11 @@ int form_row_groups(eg_model* m, TargetState& ts, Plan& plan, const std::vector<
 // wide row groups over collapsed leading axes (rowfuse.hpp): formed first, entries of plan.row_groups like the others
 int form_collapsed_groups(eg_model* m, TargetState& ts, Plan& plan, const std::vector<KernelInfo>& infos, const std::map<int, int>& first_writer,
                           std::vector<int>& group_of);
+// plan_attention.cpp: forward attention chains as one launch each, formed before every other group
+constexpr int ATTENTION_GROUP_CODE = -2000000;  // group_of[] entry of an attention group's kernels
+int form_attention_groups(eg_model* m, TargetState& ts, Plan& plan, const std::vector<KernelInfo>& infos, const std::map<int, int>& first_writer,
+                          std::vector<int>& group_of);
+bool row_fusion_enabled();
 constexpr int SAMPLE_GROUP_CODE = -1000000;  // group_of[] entry of a sample group's kernels
 int form_sample_group(eg_model* m, TargetState& ts, Plan& plan, const std::vector<KernelInfo>& infos, const std::map<int, int>& first_writer,
                       std::vector<int>& group_of, std::set<int>& needs_zero);
@@ -380,6 +397,7 @@ void plan_overlap(eg_model* m, TargetState& ts, Plan& plan);
 int fuse_epilogues(eg_model* m, TargetState& ts, Plan& plan, const std::vector<KernelInfo>& infos);
 // plan.cpp
 int build_plan_kernels(eg_model* m, Plan& plan);
+bool plan_batched2(const Batched2GemmMatch& g, const Kernel& k, const KernelInfo& info, const Shapes& shapes, Launch& L);
 float* tensor_ptr(eg_model* m, TargetState& ts, Plan& plan, int tid);
 bool full_cover(const Kernel& k, const KernelInfo& info, const std::vector<long>& shape);
 void note_vec4(Launch& L, long total);

@@ -380,8 +380,11 @@ int make_plan(eg_model* m, TargetState& ts, Plan& plan) {
   std::set<int> needs_zero;
   plan.sample_group.reset();
   if (fuse) {
+    // a whole forward attention chain is one launch; what it refuses goes on to the collapsed wide row groups
+    int rc = form_attention_groups(m, ts, plan, infos, first_writer, group_of);
+    if (rc) return rc;
     // a softmax chain over collapsed leading axes is claimed first: a sample group would give it one block per sample
-    int rc = form_collapsed_groups(m, ts, plan, infos, first_writer, group_of);
+    rc = form_collapsed_groups(m, ts, plan, infos, first_writer, group_of);
     if (rc) return rc;
     rc = form_sample_group(m, ts, plan, infos, first_writer, group_of, needs_zero);
     if (rc) return rc;
@@ -395,6 +398,22 @@ int make_plan(eg_model* m, TargetState& ts, Plan& plan) {
   for (size_t p = 0; p < t.live.size(); ++p) {
     if ((int)p == t.first_update) plan.n_backward = (int)plan.launches.size();
     if (folded.count((int)p)) continue;
+    if (group_of[p] == ATTENTION_GROUP_CODE) {
+      auto ag = plan.attn_groups.find((int)p);
+      if (ag != plan.attn_groups.end()) {   // first kernel of the chain: one launch for all; accumulate as for the context product
+        Launch L = ag->second;
+        const int last = L.attn_members.back();
+        const Kernel& ck = t.all[t.live[last]];
+        const int wt = ck.write.tensor;
+        const bool is_result = m->prog.tensors[wt].kind == TK::Result;
+        const bool first = is_result && first_writer[wt] == last;
+        const bool overwrite = first && full_cover(ck, infos[t.live[last]], shapes.at(wt));
+        L.accumulate = !overwrite;
+        if (is_result && first && !overwrite) needs_zero.insert(wt);
+        plan.launches.push_back(L);
+      }
+      continue;
+    }
     if (group_of[p] == SAMPLE_GROUP_CODE) {
       if (!plan.sample_group->positions.empty() && plan.sample_group->positions[0] == (int)p) {
         Launch L;
@@ -755,6 +774,7 @@ int make_plan(eg_model* m, TargetState& ts, Plan& plan) {
   for (int pass = 0; pass < 2; ++pass) {
     for (int tid : result_tensors) {
       if (plan.alias.count(tid)) continue;  // lives in its source's storage
+      if (plan.attn_hidden.count(tid)) continue;  // lives in the registers of an attention group's blocks
       if (ts.bucket_offset.count(tid)) {
         if (pass == 0 && needs_zero.count(tid)) plan.bucket_zero.push_back(tid);
         continue;

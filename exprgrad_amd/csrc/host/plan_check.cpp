@@ -71,6 +71,12 @@ void launch_io(eg_model* m, TargetState& ts, const Plan& plan, const Launch& L, 
       wr(L.c_tensor, L.accumulate);
       wr(L.ones_tensor, false);
       break;
+    case StepKind::Attention:   // reads q, kk, v, writes the context; the intermediates are touched by nobody (checked below)
+      rd(L.a_tensor);
+      rd(L.b_tensor);
+      rd(L.v_tensor);
+      wr(L.c_tensor, L.accumulate);
+      break;
     case StepKind::GemmFused: {
       const PlanEpilogue& pe = *plan.epilogues[L.epilogue];
       rd(L.a_tensor);
@@ -187,6 +193,9 @@ int check_plan(eg_model* m, TargetState& ts, Plan& plan) {
         case StepKind::SampleFused:
           for (int pos : plan.sample_group->positions) mark(pos);
           break;
+        case StepKind::Attention:
+          for (int pos : L.attn_members) mark(pos);
+          break;
         case StepKind::GemmFused:
           mark(L.lowered);
           mark(plan.epilogues[L.epilogue]->consumer.lowered);
@@ -277,7 +286,9 @@ int check_plan(eg_model* m, TargetState& ts, Plan& plan) {
         if (sh != plan.shapes.end() && prod(sh->second) > 0)
           EG_PLAN_REQUIRE(tensor_ptr(m, ts, plan, x) != nullptr, "tensor %d (read by launch %d) has no storage", x, i);
       }
+    for (int x : io.reads) EG_PLAN_REQUIRE(!plan.attn_hidden.count(x), "launch %d reads tensor %d, which an attention group never stores", i, x);
     for (int x : io.writes) {
+      EG_PLAN_REQUIRE(!plan.attn_hidden.count(x), "launch %d writes tensor %d, which an attention group keeps in registers", i, x);
       auto sh = plan.shapes.find(x);
       if (sh != plan.shapes.end() && prod(sh->second) > 0)
         EG_PLAN_REQUIRE(tensor_ptr(m, ts, plan, x) != nullptr, "tensor %d (written by launch %d) has no storage", x, i);

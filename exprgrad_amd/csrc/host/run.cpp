@@ -61,6 +61,11 @@ int run_launch(eg_model* m, TargetState& ts, Plan& plan, Launch& L) {
       return eg::gemm::sgemm_batched(ctx, L.trans_a, L.trans_b, L.batch, L.M, L.N, L.K, tensor_ptr(m, ts, plan, L.a_tensor), L.lda, L.stride_a,
                                      tensor_ptr(m, ts, plan, L.b_tensor), L.ldb, L.stride_b, tensor_ptr(m, ts, plan, L.c_tensor), L.ldc,
                                      L.stride_c, L.accumulate, nullptr);
+    case StepKind::Attention:
+      return eg::attention::attention_f32(ctx, L.batch, L.batch1, L.M, L.N, L.K, L.attn_d, L.attn_scale, tensor_ptr(m, ts, plan, L.a_tensor), L.lda,
+                                          L.stride_a, L.stride_a1, tensor_ptr(m, ts, plan, L.b_tensor), L.ldb, L.stride_b, L.stride_b1,
+                                          tensor_ptr(m, ts, plan, L.v_tensor), L.ldv, L.stride_v, L.stride_v1, tensor_ptr(m, ts, plan, L.c_tensor), L.ldc,
+                                          L.stride_c, L.stride_c1, L.accumulate);
     case StepKind::GemmFused: {
       PlanEpilogue& pe = *plan.epilogues[L.epilogue];
       const float* bias = L.bias_tensor ? tensor_ptr(m, ts, plan, L.bias_tensor) : nullptr;

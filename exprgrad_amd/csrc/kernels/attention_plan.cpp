@@ -1,0 +1,56 @@
+// plan_attention: see attention_plan.hpp.  One tile shape (64 query rows x 64 keys, four waves of 16 rows) for every
+// problem; what varies is the padded head dimensions, the load width per operand and the cut into launches.
+#include "attention_plan.hpp"
+
+#include <algorithm>
+
+namespace eg {
+namespace attention {
+
+Plan plan_attention(const Problem& p) {
+  Plan r;
+  if (p.batch0 < 1 || p.batch1 < 1 || p.I < 1 || p.J < 0 || p.K < 0 || p.D < 1) {
+    r.reason = "an empty or negative extent";
+    return r;
+  }
+  if (p.K > MAX_HEAD) {
+    r.reason = "K above 128";
+    return r;
+  }
+  if (p.D > MAX_HEAD) {
+    r.reason = "D above 128";
+    return r;
+  }
+  r.kp = padded_head(p.K);
+  r.dp = padded_head(p.D);
+  r.lds_bytes = lds_bytes_for(r.kp, r.dp);
+  if (r.lds_bytes > LDS_LIMIT) {
+    r.reason = "the tiles exceed the LDS of a CU";
+    return r;
+  }
+  r.tiles_i = (p.I + TILE_I - 1) / TILE_I;
+  if (r.tiles_i > eg::gemm::BATCHED_MAX_BLOCKS) {
+    r.reason = "an item has more row tiles than one launch has blocks";
+    return r;
+  }
+  r.vec_q = operand_vec16(p.q);
+  r.vec_k = operand_vec16(p.k);
+  r.vec_v = operand_vec16(p.v);
+  r.items = p.batch0 * p.batch1;
+  r.grid = r.items * r.tiles_i;
+  r.items_per_launch = std::max(1L, eg::gemm::BATCHED_MAX_BLOCKS / r.tiles_i);
+  r.launches = (r.items + r.items_per_launch - 1) / r.items_per_launch;
+  r.supported = true;
+  return r;
+}
+
+Launch plan_launch(const Plan& plan, long index) {
+  Launch l;
+  l.first = index * plan.items_per_launch;
+  l.items = std::min(plan.items_per_launch, plan.items - l.first);
+  l.grid = l.items * plan.tiles_i;
+  return l;
+}
+
+}  // namespace attention
+}  // namespace eg

@@ -45,6 +45,15 @@ def sgemm_batched2(ctx, batch0, batch1, M, N, K, A, lda, strides_a, B, ldb, stri
          _p(B), ldb, strides_b[0], strides_b[1], _p(C), ldc, strides_c[0], strides_c[1], int(accumulate), _p(bias))
 
 
+def attention(ctx, batch0, batch1, I, J, K, D, scale, Q, ldq, strides_q, Kk, ldk, strides_k, V, ldv, strides_v, O, ldo, strides_o,
+              accumulate=False):
+    """Fused attention forward, one launch: for every item (o, i1), O[i,:] (+)= (sum_j exp(scale * q_i . k_j) * V[j,:]) /
+    (sum_j exp(scale * q_i . k_j)), as written, without the row maximum.  Item (o, i1) of X starts at X + o * strides_x[0] +
+    i1 * strides_x[1] (floats; a 0 in the strides of Q, Kk or V shares the operand along that index).  K and D at most 128."""
+    call("eg_attention", ctx.handle, batch0, batch1, I, J, K, D, float(scale), _p(Q), ldq, strides_q[0], strides_q[1], _p(Kk), ldk,
+         strides_k[0], strides_k[1], _p(V), ldv, strides_v[0], strides_v[1], _p(O), ldo, strides_o[0], strides_o[1], int(accumulate))
+
+
 def dgemm_batched(ctx, batch, M, N, K, A, lda, stride_a, B, ldb, stride_b, C, ldc, stride_c, trans_a=False, trans_b=False,
                   accumulate=False, bias=None):
     """The float64 form of sgemm_batched: item b uses A + b * stride_a, B + b * stride_b, C + b * stride_c (strides and

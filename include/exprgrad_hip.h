@@ -211,6 +211,40 @@ int eg_sgemm_batched2(eg_ctx* ctx, int trans_a, int trans_b, int64_t batch0, int
                       float* C, int64_t ldc, int64_t stride_c0, int64_t stride_c1,
                       int accumulate, const float* bias);
 
+/* Fused attention forward: for every item (o, i1), o in [0, batch0), i1 in [0, batch1), X_{o,i1} = X + o * stride_x0 + i1 * stride_x1,
+ *   O[i,:] (+)= (sum_j exp(scale * q_i . k_j) * V[j,:]) / (sum_j exp(scale * q_i . k_j))
+ * with Q the I x K matrix of row step ldq, Kk J x K (ldk), V J x D (ldv) and O I x D (ldo).  It replaces the scale map and the
+ * softmax of layers/dnn.nim:90-94 between the two `++=` products s[b,h,i,j] ++= q[b,i,h,k] * kk[b,j,h,k] and
+ * o[b,i,h,d] ++= p[b,h,i,j] * v[b,j,h,d]: the formula as written, without the row maximum, so the scores, the scaled
+ * scores, the row sums and the softmax are never stored.  For [b,i,h,*] tensors: ld = H * K (H * D), stride_x1 = K (D).
+ * One launch of batch0 x batch1 x ceil(I / 64) blocks (kernels/attention_f32.hip), split along the flattened (o, i1) range
+ * when it would exceed 2^22 blocks; exact f32 on the f32 matrix instruction, never the split-bf16 route; no atomics and no
+ * workspace: two calls give the same bits.
+ *   - accumulate: when it is 0, O is not read.
+ *   - Strides of Q, Kk and V: each of the six may be 0 (the operand is shared along that index); a negative one is
+ *     EG_ERR_INVALID.
+ *   - O must not alias itself: batched2_c_distinct(batch0, stride_o0, batch1, stride_o1, I, ldo, D), the rule of
+ *     eg_sgemm_batched2's C (interleaved items are accepted, every tie and every 0 is refused), else EG_ERR_INVALID.
+ *   - EG_ERR_INVALID, with a message that names eg_attention: a NULL ctx, a NULL operand of a non-empty call, a negative
+ *     extent, a leading dimension shorter than a row, a batch extent of 2^31 or more.
+ *   - EG_ERR_UNSUPPORTED, with a message that names the limit: K > 128 or D > 128.  I >= 1 and J >= 1 are arbitrary.
+ *   - batch0 == 0, batch1 == 0, I == 0 or D == 0 succeed and launch nothing.
+ *   - J == 0 writes zeros when accumulate == 0 and nothing otherwise.
+ *   - K == 0: every score is 0, the result is the mean of V's rows.
+ *   - No alignment is required.  An operand is read with 16-byte loads when its pointer is 16-byte aligned and its leading
+ *     dimension and both its strides are multiples of 4, element by element otherwise.
+ *   - Elements of O outside the items are never written, and elements of Q, Kk and V outside the views are never read,
+ *     whatever they hold — NaN included.
+ * Special values are those of the three-statement program (scale, row sum of exp, exp / sum): a row whose scores hold +Inf
+ * or overflow expf is NaN; a NaN poisons its row; a row whose terms all underflow is 0 / 0 = NaN; -Inf terms add nothing.
+ * The one departure: when the sum overflows while every term is finite, the program gives 0 for that row (finite / Inf)
+ * and this entry gives NaN. */
+int eg_attention(eg_ctx* ctx, int64_t batch0, int64_t batch1, int64_t I, int64_t J, int64_t K, int64_t D, float scale,
+                 const float* Q, int64_t ldq, int64_t stride_q0, int64_t stride_q1,
+                 const float* Kk, int64_t ldk, int64_t stride_k0, int64_t stride_k1,
+                 const float* V, int64_t ldv, int64_t stride_v0, int64_t stride_v1,
+                 float* O, int64_t ldo, int64_t stride_o0, int64_t stride_o1, int accumulate);
+
 /* out[y,x] (+)= bias[x]   — dense's second kernel, dnn.nim:22-24. out is [rows, cols]. */
 int eg_bias_add(eg_ctx* ctx, int64_t rows, int64_t cols, const float* bias, float* out,
                 int accumulate);
