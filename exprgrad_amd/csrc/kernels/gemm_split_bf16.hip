@@ -18,15 +18,24 @@
 //      16 bytes (4 rows) per lane, and its pieces turn k-contiguous through LDS (split_tiles_kernel); with
 //      EG_SPLIT_PASS_SCALAR=1, or a leading dimension that is no multiple of 4, it takes the unit path with eight
 //      4-byte loads per unit instead (split_planes_kernel, both operands as units).
-//   2. split_gemm_kernel: 256 x 256 tiles, eight waves of 128 x 64 (8 x 4 blocks of 16 x 16), LDS-DMA stages of one
-//      16-deep k-tile (3 planes x 512 rows x 32 bytes = 48 KiB), three stages, one barrier per k-tile, C written through
-//      LDS as 16-byte row pieces.  Returns at entry when the flag is set.
+//   2. the product: 256 x 256 tiles, eight waves of 128 x 64 (8 x 4 blocks of 16 x 16), LDS-DMA stages of one 16-deep
+//      k-tile (3 planes x 512 rows x 32 bytes = 48 KiB), three stages, C written through LDS as 16-byte row pieces.
+//      Returns at entry when the flag is set.  Two kernels share everything but the k loop (split_product):
+//        split_pingpong_kernel (default): two barriers per k-tile, a load phase and an MFMA phase, with the two waves of
+//          a SIMD permanently one barrier apart, so that one multiplies (at raised priority) while the other issues and
+//          reads.  The schedule is kernels/split_schedule.hpp, replayed on the CPU by tests/test_split_schedule_cpu.py.
+//        split_gemm_kernel (EG_GEMM_NO_SKEW=1, skew = 0): one barrier per k-tile, every wave in phase; the independent
+//          loop the default is compared against bit for bit (same MFMAs, same accumulators, same k order).  Its
+//          staggered roles (skew = 1, the default before the ping-pong loop) are no longer selected by the library; they
+//          stay because tests/test_split_gemm_isa.py and tests/test_split_gemm_skew_isa.py pin this kernel's instruction
+//          stream, and can go when those tests may move.
 //   3. the exact f32 kernel (sgemm_exact with GemmArgs::run_if): returns at entry unless the flag is set.
 // Only shapes whose exact product is one whole-tile launch qualify (exact_single_launch), so the fallback is one launch.
 #include <algorithm>
 #include <cfloat>
 
 #include "gemm_fused.hpp"
+#include "split_schedule.hpp"
 #include "../eg_internal.hpp"
 #include "../switches.hpp"
 
@@ -305,10 +314,10 @@ __device__ __forceinline__ const void* uniform_ptr(const void* p) {
   return reinterpret_cast<const void*>(((unsigned long)hi << 32) | lo);
 }
 
-// What a wave does in one period of the k loop (between two barriers), as bits of a wave-uniform word.  In phase
-// (EG_GEMM_NO_SKEW=1) every wave is LOAD_OWN | READ_TOP: its own six LDS-DMA pieces and its fragment reads stand between
-// the barrier and its first MFMA.  Two waves that share a SIMD would then do all of that at the same moment with nobody
-// multiplying, so by default the partners of a SIMD take different roles:
+// split_gemm_kernel: what a wave does in one period of the k loop (between two barriers), as bits of a wave-uniform
+// word.  In phase (skew = 0, EG_GEMM_NO_SKEW=1) every wave is LOAD_OWN | READ_TOP: its own six LDS-DMA pieces and its
+// fragment reads stand between the barrier and its first MFMA.  Two waves that share a SIMD then do all of that at the
+// same moment with nobody multiplying, so with skew = 1 the partners of a SIMD take different roles:
 //   early wave (READ_AHEAD):  enters period kt with the B fragments and the first A fragments of k-tile kt in registers,
 //                             multiplies at once, and behind its last MFMA reads the same fragments of k-tile kt + 1.
 //   late wave  (LOAD_OWN | LOAD_PARTNER | READ_TOP):  issues all twelve pieces of k-tile kt + 2, reads its fragments of
@@ -339,9 +348,45 @@ __device__ unsigned long long g_split_stamps[STAMP_BLOCKS][8][4];
   } while (0)
 #endif
 
-__global__ __launch_bounds__(NT) void split_gemm_kernel(SplitGemmArgs a) {
+// The sub-tile leaves through LDS as 16-byte row pieces (the 16x16 C/D map, column lane & 15 and row 4 (lane >> 4) + r,
+// would store 64-byte pieces).  Each wave parks half of its 128 x 64 sub-tile at a time in a 16 KiB region of its own
+// ([row][64] floats; 2-way on the b32 writes, which costs nothing, none on the b128 reads) and writes it back as
+// 4 rows x 256 bytes per instruction.  The barrier: every wave is done reading the last k-tile's stage.
+__device__ __forceinline__ void store_c(const SplitGemmArgs& a, unsigned char (&lds)[STAGES * STAGE_BYTES], const f32x4 (&acc)[8][4], long m_blk,
+                                        long n_blk, int wave, int lane) {
+  const int wr = wave >> 2, wc = wave & 3;
+  __syncthreads();
+  float* park = reinterpret_cast<float*>(lds) + wave * 64 * WN;
+  const int prow = lane >> 4, pc4 = (lane & 15) * 4;
+  const long col = n_blk + wc * WN + pc4;
+  f32x4 b4 = {0.f, 0.f, 0.f, 0.f};
+  if (a.bias) b4 = *reinterpret_cast<const f32x4*>(a.bias + col);
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) park[(i * 16 + 4 * prow + r) * WN + j * 16 + (lane & 15)] = acc[4 * h + i][j][r];
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // (one wave: its LDS accesses complete in order)
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      const int row = 4 * q + prow;
+      f32x4 v = *reinterpret_cast<const f32x4*>(park + row * WN + pc4);
+      f32x4* c = reinterpret_cast<f32x4*>(a.C + (m_blk + wr * WM + h * 64 + row) * a.ldc + col);
+      if (a.accumulate) v = *c + v;
+      if (a.bias) v = v + b4;
+      *c = v;
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  }
+}
+
+// Both product kernels: everything but the k loop is the same text.  PINGPONG picks the loop (below).
+template <bool PINGPONG>
+__device__ __forceinline__ void split_product(const SplitGemmArgs& a, unsigned char (&lds)[STAGES * STAGE_BYTES]) {
   if (*(volatile const unsigned*)a.flag == a.epoch) return;  // an operand did not split: the exact kernel behind runs
-  __shared__ __attribute__((aligned(16))) unsigned char lds[STAGES * STAGE_BYTES];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wave >> 2, wc = wave & 3;  // 2 x 4 waves of 128 x 64
@@ -411,6 +456,95 @@ __global__ __launch_bounds__(NT) void split_gemm_kernel(SplitGemmArgs a) {
   for (int j = 0; j < 4; ++j) fb21[j] = fb10[j] = fb00[j] = bf16x8{};
   fa01 = fa02 = bf16x8{};
 
+  // The 96 MFMAs of one k-tile, from the fragments read_head left: per block the 2^-16 pair first, then the 2^-8 pair,
+  // then a0b0 with a2b0.
+  // The A fragments of block row i + 1 are read in front of block row i's twelve MFMAs and waited for behind them.  The
+  // fences keep them there: left alone the scheduler sinks each read to its first use, and a wave that has the matrix
+  // pipe to itself (its partner is in its front or at the barrier) then stands for an LDS latency per block row
+  // (stamped: 1840 cycles per 96 MFMAs of 16).
+  auto multiply = [&](const unsigned char* st) {
+    bf16x8 c01 = fa01, c02 = fa02;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      bf16x8 n01 = c01, n02 = c02;
+      __builtin_amdgcn_sched_barrier(0);
+      if (i + 1 < 8) {
+        n01 = *reinterpret_cast<const bf16x8*>(st + a01_off + (i + 1) * 512);
+        n02 = *reinterpret_cast<const bf16x8*>(st + a02_off + (i + 1) * 512);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(c01, fb21[j], acc[i][j], 0, 0, 0);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(c01, fb10[j], acc[i][j], 0, 0, 0);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(c02, fb00[j], acc[i][j], 0, 0, 0);
+      c01 = n01;
+      c02 = n02;
+    }
+  };
+
+  if constexpr (PINGPONG) {
+    // Two barriers per k-tile, the two waves of a SIMD permanently one barrier apart (kernels/split_schedule.hpp has the
+    // schedule and its hazard argument; every count and stage number below is taken from there).  Waves 4 - 7 (role Y)
+    // issue every LDS-DMA piece, their own and their partners', and are the only ones that wait for any.
+    namespace ss = eg::split_sched;
+    static_assert(ss::STAGES == STAGES && ss::PIECES == 2 * LOADS && ss::WAVES * 64 == NT, "split_schedule.hpp is this kernel's");
+    auto issue_both = [&](int kt, int s) {
+      pieces(kt, s, wave);
+      pieces(kt, s, wave ^ PARTNER);
+    };
+    const int role = ss::role_of(wave);
+    const int KT = (int)(a.K / 16);
+    if (role == ss::Y) {
+      for (int t = 0; t < ss::prologue_tiles(ss::Y, KT); ++t) issue_both(t, ss::stage_of(t));
+      // k-tile 0 has landed; the k-tiles behind it may fly
+      const int fly = ss::prologue_vmcnt(KT);
+      if (fly == 2 * ss::PIECES) asm volatile("s_waitcnt vmcnt(24)" ::: "memory");
+      else if (fly == ss::PIECES) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
+      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    static_assert(ss::barriers_before_loop(ss::X) == 1 && ss::barriers_before_loop(ss::Y) == 2, "barrier S, then Y's stagger");
+    __builtin_amdgcn_s_barrier();
+    if (role == ss::Y) __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    int s = 0, s2 = 2;  // stage_of(kt), stage_of(kt + 2)
+    for (int kt = 0; kt < KT; ++kt) {
+      // what the role does in this load phase, made opaque in every iteration: ONE loop body with scalar branches
+      // around the issue and the wait (as loop invariants the compiler would write a loop per role)
+      int go = __builtin_amdgcn_readfirstlane(ss::load_issues(role, kt, KT) ? 1 : 0);
+      int fly = __builtin_amdgcn_readfirstlane(ss::load_waits(role) ? ss::load_vmcnt(kt, KT) : -1);  // the vmcnt to wait for, -1: none
+      asm volatile("" : "+s"(go), "+s"(fly));
+      if (go) issue_both(ss::load_issue_tile(kt), s2);
+      const unsigned char* st = lds + s * STAGE_BYTES;
+      read_head(st);
+      static_assert(ss::load_vmcnt(0, 3) == 12 && ss::load_vmcnt(0, 2) == 0, "the counts written out below");
+      if (fly == 12) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
+      else if (fly == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+      asm volatile("" ::: "memory");
+      // MFMA phase.  The fence keeps all 96 in front of the closing barrier (left alone the scheduler sinks the last
+      // eleven behind it, into the partner's turn); the wait says this phase's fragment reads are done before the stage
+      // may be refilled one barrier later.  The raised priority is the hardware's part: the SIMD issues the multiplying
+      // wave's instructions ahead of its partner's load phase.  Without it the loop is no faster than one barrier per
+      // k-tile with staggered roles, with it 2.2 - 2.6 % (profiles/split_pingpong_ab.txt).
+      __builtin_amdgcn_s_setprio(1);
+      multiply(st);
+      __builtin_amdgcn_sched_barrier(0);
+      __builtin_amdgcn_s_setprio(0);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+      asm volatile("" ::: "memory");
+      s = s == STAGES - 1 ? 0 : s + 1;
+      s2 = s2 == STAGES - 1 ? 0 : s2 + 1;
+    }
+    static_assert(ss::barriers_after_loop(ss::X) == 1 && ss::barriers_after_loop(ss::Y) == 0, "X catches up");
+    if (role == ss::X) __builtin_amdgcn_s_barrier();
+    store_c(a, lds, acc, m_blk, n_blk, wave, lane);
+    return;
+  }
+
+  // split_gemm_kernel's loop from here on: one barrier per k-tile
   const int skew = a.skew;
   const int role = !skew ? ROLE_LOAD_OWN | ROLE_READ_TOP
                          : (wave & PARTNER) ? ROLE_LOAD_OWN | ROLE_LOAD_PARTNER | ROLE_READ_TOP : ROLE_READ_AHEAD;
@@ -451,30 +585,7 @@ __global__ __launch_bounds__(NT) void split_gemm_kernel(SplitGemmArgs a) {
     const unsigned char* st = lds + s * STAGE_BYTES;
     if (r & ROLE_READ_TOP) read_head(st);
     EG_STAMP(t1);
-    // per block the 2^-16 pair first, then the 2^-8 pair, then a0b0 with a2b0
-    // The A fragments of block row i + 1 are read in front of block row i's twelve MFMAs and waited for behind them.  The
-    // fences keep them there: left alone the scheduler sinks each read to its first use, and a wave that has the matrix
-    // pipe to itself (its partner is in its front or at the barrier) then stands for an LDS latency per block row
-    // (stamped: 1840 cycles per 96 MFMAs of 16).
-    bf16x8 c01 = fa01, c02 = fa02;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      bf16x8 n01 = c01, n02 = c02;
-      __builtin_amdgcn_sched_barrier(0);
-      if (i + 1 < 8) {
-        n01 = *reinterpret_cast<const bf16x8*>(st + a01_off + (i + 1) * 512);
-        n02 = *reinterpret_cast<const bf16x8*>(st + a02_off + (i + 1) * 512);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(c01, fb21[j], acc[i][j], 0, 0, 0);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(c01, fb10[j], acc[i][j], 0, 0, 0);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(c02, fb00[j], acc[i][j], 0, 0, 0);
-      c01 = n01;
-      c02 = n02;
-    }
+    multiply(st);
     EG_STAMP(t2);
 #ifdef EG_SPLIT_GEMM_STAMPS
     front += t1 - t0;
@@ -493,37 +604,18 @@ __global__ __launch_bounds__(NT) void split_gemm_kernel(SplitGemmArgs a) {
     o[3] = (unsigned long long)KT;
   }
 #endif
+  store_c(a, lds, acc, m_blk, n_blk, wave, lane);
+}
 
-  // The sub-tile leaves through LDS as 16-byte row pieces (the 16x16 C/D map, column lane & 15 and row 4 (lane >> 4) + r,
-  // would store 64-byte pieces).  Each wave parks half of its 128 x 64 sub-tile at a time in a 16 KiB region of its own
-  // ([row][64] floats; 2-way on the b32 writes, which costs nothing, none on the b128 reads) and writes it back as
-  // 4 rows x 256 bytes per instruction.  The barrier: every wave is done reading the last k-tile's stage.
-  __syncthreads();
-  float* park = reinterpret_cast<float*>(lds) + wave * 64 * WN;
-  const int prow = lane >> 4, pc4 = (lane & 15) * 4;
-  const long col = n_blk + wc * WN + pc4;
-  f32x4 b4 = {0.f, 0.f, 0.f, 0.f};
-  if (a.bias) b4 = *reinterpret_cast<const f32x4*>(a.bias + col);
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) park[(i * 16 + 4 * prow + r) * WN + j * 16 + (lane & 15)] = acc[4 * h + i][j][r];
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // (one wave: its LDS accesses complete in order)
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const int row = 4 * q + prow;
-      f32x4 v = *reinterpret_cast<const f32x4*>(park + row * WN + pc4);
-      f32x4* c = reinterpret_cast<f32x4*>(a.C + (m_blk + wr * WM + h * 64 + row) * a.ldc + col);
-      if (a.accumulate) v = *c + v;
-      if (a.bias) v = v + b4;
-      *c = v;
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  }
+// One barrier per k-tile; with skew = 1 the waves of a SIMD in the early and late roles above, with skew = 0 in phase.
+__global__ __launch_bounds__(NT) void split_gemm_kernel(SplitGemmArgs a) {
+  __shared__ __attribute__((aligned(16))) unsigned char lds[STAGES * STAGE_BYTES];
+  split_product<false>(a, lds);
+}
+// Two barriers per k-tile, SIMD partners one barrier apart (kernels/split_schedule.hpp): the library's default.
+__global__ __launch_bounds__(NT) void split_pingpong_kernel(SplitGemmArgs a) {
+  __shared__ __attribute__((aligned(16))) unsigned char lds[STAGES * STAGE_BYTES];
+  split_product<true>(a, lds);
 }
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
@@ -596,10 +688,14 @@ int sgemm_split(eg_ctx* ctx, int trans_a, int trans_b, long M, long N, long K, c
   g.tiles_m = (int)(M / BM);
   g.tiles_n = (int)(N / BN);
   g.accumulate = accumulate;
-  g.skew = eg::sw::on(eg::Sw::GEMM_NO_SKEW) ? 0 : 1;
+  g.skew = 0;
   g.flag = ctx->split_flag;
   g.epoch = epoch;
-  hipLaunchKernelGGL(split_gemm_kernel, dim3((unsigned)(g.tiles_m * g.tiles_n)), dim3(NT), 0, ctx->stream, g);
+  // EG_GEMM_NO_SKEW=1: the in-phase loop, the independent kernel the default one is compared against bit for bit
+  if (eg::sw::on(eg::Sw::GEMM_NO_SKEW))
+    hipLaunchKernelGGL(split_gemm_kernel, dim3((unsigned)(g.tiles_m * g.tiles_n)), dim3(NT), 0, ctx->stream, g);
+  else
+    hipLaunchKernelGGL(split_pingpong_kernel, dim3((unsigned)(g.tiles_m * g.tiles_n)), dim3(NT), 0, ctx->stream, g);
   EG_HIP_CHECK(hipGetLastError());
 
   // the exact product, run only when the split pass set the flag
