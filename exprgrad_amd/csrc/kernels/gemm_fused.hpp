@@ -48,6 +48,17 @@ bool exact_single_launch(eg_ctx* ctx, int trans_a, int trans_b, long M, long N, 
 // eg_sgemm's split-bf16 path (gemm_split_bf16.hip): EG_ERR_UNSUPPORTED, before any launch, when it does not apply.
 int sgemm_split(eg_ctx* ctx, int trans_a, int trans_b, long M, long N, long K, const float* A, long lda, const float* B, long ldb,
                 float* C, long ldc, int accumulate, const float* bias);
+// The split pass in front of that product (gemm_split_pass.hip), launched on ctx->stream.  op(X) is rows x K: X[r * ld + k]
+// when k_contiguous, X[k * ld + r] otherwise; rows % 32 == 0, K % 32 == 0, src 16-byte aligned.  The plane layout, which
+// is all the two files share: `planes` holds bf16 [plane][k / 16][row][16], three planes per operand (piece 0, 1, 2 of
+// every element), op(B)'s three planes behind op(A)'s, 6 (a.rows + b.rows) K bytes in all.  An element that does not
+// split exactly sets *ctx->split_flag to `epoch`.
+struct SplitPassOperand {
+  const float* src;
+  long ld, rows;
+  bool k_contiguous;
+};
+int split_pass(eg_ctx* ctx, const SplitPassOperand& a, const SplitPassOperand& b, long K, void* planes, unsigned epoch);
 
 // `batch` exact f32 products of one shape, X_b = X + b * stride_x, in one launch (gemm_batched.hip): what eg_sgemm_batched
 // and the model layer's batched launches run.

@@ -10,29 +10,21 @@
 // same cycles per FLOP.)
 //
 // Two launches, then the exact kernel behind them as a device-side fallback:
-//   1. the split pass: op(A) and op(B) of any layout and leading dimension -> three bf16 planes each, k-contiguous
-//      in 16-deep k-tiles ([plane][k / 16][row][16]: the 8 KiB a 256-row tile needs per plane and k-tile are one
-//      contiguous piece).  An element that does not split exactly (Inf, NaN, f32 subnormal, a piece that underflows,
-//      a value that rounds to Inf) sets the context's flag word to this call's epoch.  A k-contiguous operand is read
-//      in units of 8 k (2 x 16 bytes per lane).  An operand whose k runs along ld is read in tiles of 16 k x 256 rows,
-//      16 bytes (4 rows) per lane, and its pieces turn k-contiguous through LDS (split_tiles_kernel); with
-//      EG_SPLIT_PASS_SCALAR=1, or a leading dimension that is no multiple of 4, it takes the unit path with eight
-//      4-byte loads per unit instead (split_planes_kernel, both operands as units).
+//   1. the split pass (gemm_split_pass.hip): op(A) and op(B) of any layout and leading dimension -> three bf16 planes
+//      each, in the layout stated at split_pass's declaration (gemm_fused.hpp): k-contiguous in 16-deep k-tiles, so the
+//      8 KiB a 256-row tile needs per plane and k-tile are one contiguous piece.  An element that does not split
+//      exactly sets the context's flag word to this call's epoch.
 //   2. the product: 256 x 256 tiles, eight waves of 128 x 64 (8 x 4 blocks of 16 x 16), LDS-DMA stages of one 16-deep
 //      k-tile (3 planes x 512 rows x 32 bytes = 48 KiB), three stages, C written through LDS as 16-byte row pieces.
 //      Returns at entry when the flag is set.  Two kernels share everything but the k loop (split_product):
 //        split_pingpong_kernel (default): two barriers per k-tile, a load phase and an MFMA phase, with the two waves of
 //          a SIMD permanently one barrier apart, so that one multiplies (at raised priority) while the other issues and
 //          reads.  The schedule is kernels/split_schedule.hpp, replayed on the CPU by tests/test_split_schedule_cpu.py.
-//        split_gemm_kernel (EG_GEMM_NO_SKEW=1, skew = 0): one barrier per k-tile, every wave in phase; the independent
-//          loop the default is compared against bit for bit (same MFMAs, same accumulators, same k order).  Its
-//          staggered roles (skew = 1, the default before the ping-pong loop) are no longer selected by the library; they
-//          stay because tests/test_split_gemm_isa.py and tests/test_split_gemm_skew_isa.py pin this kernel's instruction
-//          stream, and can go when those tests may move.
+//        split_gemm_kernel (EG_GEMM_NO_SKEW=1): one barrier per k-tile, every wave in phase; the independent loop the
+//          default is compared against bit for bit (same MFMAs, same accumulators, same k order).
 //   3. the exact f32 kernel (sgemm_exact with GemmArgs::run_if): returns at entry unless the flag is set.
 // Only shapes whose exact product is one whole-tile launch qualify (exact_single_launch), so the fallback is one launch.
 #include <algorithm>
-#include <cfloat>
 
 #include "gemm_fused.hpp"
 #include "split_schedule.hpp"
@@ -42,234 +34,7 @@
 namespace {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// ---- 1. the split pass ------------------------------------------------------------------------------------------------
-
-// op(X) is R x K: X[r * ld + k] when k-contiguous (kc), X[k * ld + r] otherwise.  R % 32 == 0, K % 32 == 0.
-struct SplitOperand {
-  const float* src;
-  long ld;
-  long R;
-  int kc;
-  __bf16* dst;  // 3 planes of R * K
-};
-
-// A unit is 8 consecutive k of one row: 32 bytes in, 16 bytes out per plane.  The 64 units of a wave cover 16 rows x 4
-// units when k-contiguous (4 x 128-byte reads; 2 x 512-byte plane rows out) and 32 rows x 2 units otherwise (each of the
-// 8 loads reads 2 x 128 bytes of two k-rows; 1 KiB plane rows out).
-__device__ __forceinline__ void unit_coords(const SplitOperand& o, long K, long u, long& r, long& chunk) {
-  const long cpr = K / 8, t = u >> 6;
-  const int l = (int)(u & 63);
-  if (o.kc) {
-    const long per = cpr / 4;
-    r = (t / per) * 16 + (l >> 2);
-    chunk = (t % per) * 4 + (l & 3);
-  } else {
-    const long per = cpr / 2;
-    r = (t / per) * 32 + (l >> 1);
-    chunk = (t % per) * 2 + (l & 1);
-  }
-}
-
-__device__ __forceinline__ void load_unit(const SplitOperand& o, long r, long chunk, float (&x)[8]) {
-  if (o.kc) {
-    const f32x4* p = reinterpret_cast<const f32x4*>(o.src + r * o.ld + chunk * 8);
-    const f32x4 v0 = __builtin_nontemporal_load(p), v1 = __builtin_nontemporal_load(p + 1);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      x[j] = v0[j];
-      x[4 + j] = v1[j];
-    }
-  } else {
-    const float* p = o.src + chunk * 8 * o.ld + r;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) x[j] = __builtin_nontemporal_load(p + j * o.ld);
-  }
-}
-
-// x = x0 + x1 + x2 exactly, or `bad`.  The casts are v_cvt_pk_bf16_f32 (round to nearest even; NaN stays NaN).  Both
-// subtractions are exact while nothing underflows or overflows, so the split is exact iff the last remainder is x2.
-__device__ __forceinline__ void split_elem(float v, __bf16& b0, __bf16& b1, __bf16& b2, bool& bad) {
-  b0 = (__bf16)v;
-  const float r1 = v - (float)b0;
-  b1 = (__bf16)r1;
-  const float f1 = (float)b1;
-  const float r2 = r1 - f1;
-  b2 = (__bf16)r2;
-  const float f2 = (float)b2;
-  bad |= !(r2 == f2);                                         // Inf, NaN, a value that rounds to Inf
-  bad |= v != 0.f && __builtin_fabsf(v) < FLT_MIN;           // f32 subnormal
-  bad |= (f1 != 0.f && __builtin_fabsf(f1) < FLT_MIN) || (f2 != 0.f && __builtin_fabsf(f2) < FLT_MIN);  // a piece underflows
-}
-
-__device__ __forceinline__ void split_unit(const SplitOperand& o, long K, long r, long chunk, const float (&x)[8], bool& bad) {
-  bf16x8 h0, h1, h2;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    __bf16 b0, b1, b2;
-    split_elem(x[j], b0, b1, b2, bad);
-    h0[j] = b0;
-    h1[j] = b1;
-    h2[j] = b2;
-  }
-  const long plane = o.R * K;
-  bf16x8* d = reinterpret_cast<bf16x8*>(o.dst + ((chunk >> 1) * o.R + r) * 16 + (chunk & 1) * 8);
-  const long ps = plane / 8;  // plane stride in 16-byte units
-  d[0] = h0;
-  d[ps] = h1;
-  d[2 * ps] = h2;
-}
-
-constexpr int SPLIT_NT = 256;
-constexpr int SPLIT_U = 2;  // units per thread in flight
-
-// Units [lo, hi) of the list in which [0, units_a) are op(A)'s and the rest op(B)'s, U per thread in flight.  A wave's 64
-// units never straddle the two operands: units_a and lo are multiples of 64.
-template <int U>
-__device__ __forceinline__ void split_units(const SplitOperand& a, const SplitOperand& b, long K, long units_a, long lo, long hi,
-                                            bool& bad) {
-  constexpr long STEP = (long)SPLIT_NT * U;
-  for (long base = lo; base < hi; base += STEP) {
-    float x[U][8];
-    long r[U], c[U];
-#pragma unroll
-    for (int i = 0; i < U; ++i) {
-      const long u = base + i * SPLIT_NT + threadIdx.x;
-      if (u >= hi) continue;
-      const bool in_a = u < units_a;
-      unit_coords(in_a ? a : b, K, in_a ? u : u - units_a, r[i], c[i]);
-      load_unit(in_a ? a : b, r[i], c[i], x[i]);
-    }
-#pragma unroll
-    for (int i = 0; i < U; ++i) {
-      const long u = base + i * SPLIT_NT + threadIdx.x;
-      if (u >= hi) continue;
-      split_unit(u < units_a ? a : b, K, r[i], c[i], x[i], bad);
-    }
-  }
-}
-
-// Both operands as units (EG_SPLIT_PASS_SCALAR=1, or no operand that qualifies for tiles).  A block owns one contiguous
-// chunk of the list (a multiple of SPLIT_NT * SPLIT_U).
-__global__ __launch_bounds__(SPLIT_NT) void split_planes_kernel(SplitOperand a, SplitOperand b, long K, long units_a, long units,
-                                                              unsigned* flag, unsigned epoch) {
-  constexpr long STEP = (long)SPLIT_NT * SPLIT_U;
-  const long per = ((units + gridDim.x - 1) / gridDim.x + STEP - 1) / STEP * STEP;
-  const long lo = (long)blockIdx.x * per, hi = lo + per < units ? lo + per : units;
-  bool bad = false;
-  split_units<SPLIT_U>(a, b, K, units_a, lo, hi, bad);
-  if (__builtin_expect(bad, 0)) *(volatile unsigned*)flag = epoch;
-}
-
-// A tile is 16 k x 256 rows of an operand whose k runs along ld: 16 memory rows of 1 KiB, as much as SPLIT_NT * 2 units.
-// Wave w fetches k-rows 4 w .. 4 w + 3 with one 16-byte-per-lane load each, so lane l holds rows 4 l .. 4 l + 3 at four
-// consecutive k: per row and plane 8 bytes of the 32-byte plane row.  They meet in an LDS image of the tile's three
-// plane pieces and leave it as whole 16-byte half rows, 1 KiB contiguous per plane and wave instruction.
-// The image: row r at (r / 8) * REC_BYTES + (r % 8) * 32, i.e. 16 bytes of padding behind every 8 rows (two lanes).
-//   ds_write_b64 (16 consecutive lanes per LDS cycle, 32 banks): a lane's rows are 128 bytes apart, so unpadded all 16
-//     would meet in one bank pair; with the padding lanes 2 m, 2 m + 1 start at 16 m mod 128: 2-way, no worse.
-//   ds_read_b128 (lane groups {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the same + 32; 64 banks): each group reads
-//     the sixteen 16-byte pieces of ONE record (lane_unit), 256 consecutive bytes: no conflict.
-constexpr int TILE_R = 256;
-constexpr int REC_BYTES = 8 * 32 + 16;
-constexpr int IMG_PLANE = (TILE_R / 8) * REC_BYTES;  // 8704
-constexpr int IMG_BYTES = 3 * IMG_PLANE;             // 25.5 KiB
-// Two images per block: three blocks fit a CU's LDS (12 waves), and three are the launch.  Two per CU: 65.0 us against
-// 59.1 at 4096^3 NN; four units in flight next to the tiles: no difference (profiles/split_pass_ab.txt).
-constexpr int TILE_BLOCKS_PER_CU = 3;
-
-__device__ __forceinline__ void load_tile(const SplitOperand& o, long kt, long rb, f32x4 (&x)[4]) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const float* p = o.src + (kt * 16 + wave * 4) * o.ld + rb * TILE_R + lane * 4;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) x[i] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p + i * o.ld));
-}
-
-__device__ __forceinline__ void split_tile(const f32x4 (&x)[4], unsigned char* img, bool& bad) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  unsigned char* row = img + (lane >> 1) * REC_BYTES + (lane & 1) * 128 + wave * 8;
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    bf16x4 h0, h1, h2;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      __bf16 b0, b1, b2;
-      split_elem(x[i][c], b0, b1, b2, bad);
-      h0[i] = b0;
-      h1[i] = b1;
-      h2[i] = b2;
-    }
-    *reinterpret_cast<bf16x4*>(row + c * 32) = h0;
-    *reinterpret_cast<bf16x4*>(row + c * 32 + IMG_PLANE) = h1;
-    *reinterpret_cast<bf16x4*>(row + c * 32 + 2 * IMG_PLANE) = h2;
-  }
-}
-
-// The lane's 16-byte piece among the 64 (four records) of a wave instruction: record = its ds_read_b128 lane group.
-__device__ __forceinline__ int lane_unit(int lane) {
-  const int quad = (lane >> 2) & 7;  // groups take the quads {0, 3, 5, 6} (even parity) and {1, 2, 4, 7} of a wave half
-  return ((lane >> 5) * 2 + (__builtin_popcount(quad) & 1)) * 16 + (quad >> 1) * 4 + (lane & 3);
-}
-
-__device__ __forceinline__ void store_tile(const SplitOperand& o, long K, long kt, long rb, const unsigned char* img) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const long plane = o.R * K;
-  __bf16* d = o.dst + (kt * o.R + rb * TILE_R) * 16;
-#pragma unroll
-  for (int p = 0; p < 3; ++p)
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int u = (wave * 2 + i) * 64 + lane_unit(lane);  // 16-byte piece u of the plane's 8 KiB: row u / 2, half u % 2
-      const bf16x8 v = *reinterpret_cast<const bf16x8*>(img + p * IMG_PLANE + (u >> 4) * REC_BYTES + (u & 15) * 16);
-      *reinterpret_cast<bf16x8*>(d + p * plane + u * 8) = v;
-    }
-}
-
-// Every block takes a contiguous run of each operand: tiles when the operand's bit of `tiled` is set, else units (in
-// pieces of SPLIT_NT * 2, one tile's worth), so a block's share of both kinds of work is the same as every other's.  Two
-// images: the loads of tile t + 1 fly while tile t leaves, one barrier per tile (image s is written again behind the
-// barrier of the tile after, which every wave passes only when its reads of s are done).
-__global__ __launch_bounds__(SPLIT_NT) void split_tiles_kernel(SplitOperand a, SplitOperand b, long K, int tiled, unsigned* flag,
-                                                             unsigned epoch) {
-  __shared__ __attribute__((aligned(16))) unsigned char img[2][IMG_BYTES];
-  bool bad = false;
-  int s = 0;
-#pragma unroll
-  for (int which = 0; which < 2; ++which) {
-    const SplitOperand& o = which ? b : a;
-    const long n = o.R * K / (TILE_R * 16);
-    const long lo = n * blockIdx.x / gridDim.x, hi = n * (blockIdx.x + 1) / gridDim.x;
-    if (!(tiled >> which & 1)) {
-      const long units = o.R * K / 8;
-      split_units<SPLIT_U>(o, o, K, units, lo * (SPLIT_NT * 2), hi * (SPLIT_NT * 2), bad);
-      continue;
-    }
-    if (lo >= hi) continue;
-    const long tr = o.R / TILE_R;
-    long kt = lo / tr, rb = lo % tr;
-    f32x4 x[4];
-    load_tile(o, kt, rb, x);
-    for (long t = lo; t < hi; ++t) {
-      split_tile(x, img[s], bad);
-      long nkt = kt, nrb = rb + 1;
-      if (nrb == tr) {
-        nrb = 0;
-        ++nkt;
-      }
-      if (t + 1 < hi) load_tile(o, nkt, nrb, x);
-      __syncthreads();
-      store_tile(o, K, kt, rb, img[s]);
-      s ^= 1;
-      kt = nkt;
-      rb = nrb;
-    }
-  }
-  if (__builtin_expect(bad, 0)) *(volatile unsigned*)flag = epoch;
-}
-
-// ---- 2. the product ---------------------------------------------------------------------------------------------------
 
 constexpr int BM = 256, BN = 256, WM = 128, WN = 64, NT = 512;
 constexpr int STAGES = 3;
@@ -277,6 +42,7 @@ constexpr int PLANE_BYTES = BM * 16 * 2;                  // one plane of one op
 constexpr int STAGE_BYTES = 6 * PLANE_BYTES;               // A planes 0..2, then B planes 0..2: 48 KiB
 constexpr int LOADS = STAGE_BYTES / (NT * 16);             // 16-byte LDS-DMA pieces per thread and stage: 6
 
+// pa, pb: the planes the split pass wrote (layout: split_pass's declaration, gemm_fused.hpp)
 struct SplitGemmArgs {
   const __bf16* pa;  // op(A) planes, M * K each
   const __bf16* pb;  // op(B) planes, N * K each
@@ -285,7 +51,6 @@ struct SplitGemmArgs {
   long M, N, K, ldc;
   int tiles_m, tiles_n;
   int accumulate;
-  int skew;  // 0: every wave runs the k loop in phase (EG_GEMM_NO_SKEW=1); 1: the waves of a SIMD take different roles
   const unsigned* flag;
   unsigned epoch;
 };
@@ -314,39 +79,8 @@ __device__ __forceinline__ const void* uniform_ptr(const void* p) {
   return reinterpret_cast<const void*>(((unsigned long)hi << 32) | lo);
 }
 
-// split_gemm_kernel: what a wave does in one period of the k loop (between two barriers), as bits of a wave-uniform
-// word.  In phase (skew = 0, EG_GEMM_NO_SKEW=1) every wave is LOAD_OWN | READ_TOP: its own six LDS-DMA pieces and its
-// fragment reads stand between the barrier and its first MFMA.  Two waves that share a SIMD then do all of that at the
-// same moment with nobody multiplying, so with skew = 1 the partners of a SIMD take different roles:
-//   early wave (READ_AHEAD):  enters period kt with the B fragments and the first A fragments of k-tile kt in registers,
-//                             multiplies at once, and behind its last MFMA reads the same fragments of k-tile kt + 1.
-//   late wave  (LOAD_OWN | LOAD_PARTNER | READ_TOP):  issues all twelve pieces of k-tile kt + 2, reads its fragments of
-//                             k-tile kt and multiplies; all of its front runs under the early wave's MFMAs, and the early
-//                             wave's trailing reads under its own.
-// Same MFMAs on the same accumulators in the same order in every role: C does not depend on the roles.
-constexpr int ROLE_LOAD_OWN = 1, ROLE_LOAD_PARTNER = 2, ROLE_READ_TOP = 4, ROLE_READ_AHEAD = 8;
-// Waves w and w ^ PARTNER share a SIMD: w and w + 4 (measured both ways, profiles/split_skew_ab.txt: with the roles
-// split by parity the step was slower than in phase).  Waves 4 - 7 are the late ones: in phase they already reach their
-// first MFMA ~500 cycles behind their partners (profiles/split_skew_stamps.txt).
+// Waves w and w ^ PARTNER share a SIMD: w and w + 4 (measured both ways: DESIGN.md, the split-bf16 product's row).
 constexpr int PARTNER = 4;
-
-#ifdef EG_SPLIT_GEMM_STAMPS
-// Diagnostic build only (-DEG_SPLIT_GEMM_STAMPS): per block and wave the cycles from barrier release to the first MFMA,
-// of the MFMA section, and from the last MFMA to the next barrier release, summed over the k loop, and the period count.
-// Read the shares, never this build's run time.  eg_debug_split_stamps copies the buffer out.
-constexpr int STAMP_BLOCKS = 1024;
-__device__ unsigned long long g_split_stamps[STAMP_BLOCKS][8][4];
-#define EG_STAMP(t)                                                                  \
-  do {                                                                               \
-    __builtin_amdgcn_sched_barrier(0);                                               \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory"); \
-    __builtin_amdgcn_sched_barrier(0);                                               \
-  } while (0)
-#else
-#define EG_STAMP(t) \
-  do {              \
-  } while (0)
-#endif
 
 // The sub-tile leaves through LDS as 16-byte row pieces (the 16x16 C/D map, column lane & 15 and row 4 (lane >> 4) + r,
 // would store 64-byte pieces).  Each wave parks half of its 128 x 64 sub-tile at a time in a 16 KiB region of its own
@@ -415,10 +149,6 @@ __device__ __forceinline__ void split_product(const SplitGemmArgs& a, unsigned c
       else
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, dst, 16, voff, (unsigned)(i - 3) * b_plane + bt, 0, 0);
     }
-  };
-  auto issue = [&](int kt, int s, int r) {
-    if (r & ROLE_LOAD_OWN) pieces(kt, s, wave);
-    if (r & ROLE_LOAD_PARTNER) pieces(kt, s, wave ^ PARTNER);
   };
 
   f32x4 acc[8][4];
@@ -544,70 +274,29 @@ __device__ __forceinline__ void split_product(const SplitGemmArgs& a, unsigned c
     return;
   }
 
-  // split_gemm_kernel's loop from here on: one barrier per k-tile
-  const int skew = a.skew;
-  const int role = !skew ? ROLE_LOAD_OWN | ROLE_READ_TOP
-                         : (wave & PARTNER) ? ROLE_LOAD_OWN | ROLE_LOAD_PARTNER | ROLE_READ_TOP : ROLE_READ_AHEAD;
+  // split_gemm_kernel's loop from here on: one barrier per k-tile, every wave in phase.  The wait in front of barrier kt
+  // retires this wave's six pieces of k-tile kt (the six of kt + 1 may still fly); the barrier makes every wave's visible,
+  // so a read of k-tile kt is one barrier behind the wait that retired its pieces.  The stage refilled behind barrier kt
+  // is k-tile kt - 1's, which every wave finished reading before it arrived at this barrier.
   const int KT = (int)(a.K / 16);
-  issue(0, 0, role);
-  if (KT > 1) issue(1, 1, role);
-  if (skew) {
-    // the early waves start from k-tile 0's fragments: the loaders' pieces of it have landed (twelve of k-tile 1 may fly)
-    if (KT > 1) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    if (role & ROLE_READ_AHEAD) read_head(lds);
-  }
-#ifdef EG_SPLIT_GEMM_STAMPS
-  unsigned long long t0 = 0, t1 = 0, t2 = 0, front = 0, body = 0, back = 0;
-#endif
+  pieces(0, 0, wave);
+  if (KT > 1) pieces(1, 1, wave);
   int s = 0;
   for (int kt = 0; kt < KT; ++kt) {
-    // In phase: this wave's pieces of k-tile kt have landed (those of kt + 1 may still fly).  Staggered: a loader's pieces
-    // of k-tile kt + 1, issued a period ago, have landed (k-tile kt landed a period earlier still; the other waves have
-    // nothing outstanding).  The barrier makes every wave's visible and says that every wave is done reading k-tile
-    // kt - 1, whose stage the next issue refills.  So behind barrier kt k-tile kt may be read in phase, and k-tiles kt
-    // and kt + 1 when staggered: a read is always at least one barrier behind the wait that retired its pieces.
-    if (!skew && kt + 1 < KT) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+    if (kt + 1 < KT) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-#ifdef EG_SPLIT_GEMM_STAMPS
-    EG_STAMP(t0);
-    if (kt) back += t0 - t2;
-#endif
-    // the role, made opaque in every period: ONE loop body with scalar branches around the issue and the two read sites
-    // (as a loop invariant the compiler would write a loop per role)
-    int r = role;
-    asm volatile("" : "+s"(r));
-    if (kt + 2 < KT) issue(kt + 2, s == 0 ? 2 : s - 1, r);
+    if (kt + 2 < KT) pieces(kt + 2, s == 0 ? 2 : s - 1, wave);
     const unsigned char* st = lds + s * STAGE_BYTES;
-    if (r & ROLE_READ_TOP) read_head(st);
-    EG_STAMP(t1);
+    read_head(st);
     multiply(st);
-    EG_STAMP(t2);
-#ifdef EG_SPLIT_GEMM_STAMPS
-    front += t1 - t0;
-    body += t2 - t1;
-#endif
     s = s == STAGES - 1 ? 0 : s + 1;
-    // k-tile kt + 1 landed before barrier kt (above); its stage is refilled behind barrier kt + 2 at the earliest
-    if ((r & ROLE_READ_AHEAD) && kt + 1 < KT) read_head(lds + s * STAGE_BYTES);
   }
-#ifdef EG_SPLIT_GEMM_STAMPS
-  if (lane == 0 && blockIdx.x < STAMP_BLOCKS) {
-    unsigned long long* o = g_split_stamps[blockIdx.x][wave];
-    o[0] = front;
-    o[1] = body;
-    o[2] = back;
-    o[3] = (unsigned long long)KT;
-  }
-#endif
   store_c(a, lds, acc, m_blk, n_blk, wave, lane);
 }
 
-// One barrier per k-tile; with skew = 1 the waves of a SIMD in the early and late roles above, with skew = 0 in phase.
+// One barrier per k-tile, every wave in phase (EG_GEMM_NO_SKEW=1): the loop the default is compared against.
 __global__ __launch_bounds__(NT) void split_gemm_kernel(SplitGemmArgs a) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[STAGES * STAGE_BYTES];
   split_product<false>(a, lds);
@@ -658,23 +347,8 @@ int sgemm_split(eg_ctx* ctx, int trans_a, int trans_b, long M, long N, long K, c
 
   __bf16* pa = static_cast<__bf16*>(ctx->workspace);
   __bf16* pb = pa + 3 * (size_t)M * K;
-  const SplitOperand oa = {A, lda, M, trans_a ? 0 : 1, pa};
-  const SplitOperand ob = {B, ldb, N, trans_b ? 1 : 0, pb};
-  // tiles for an operand whose k runs along ld, when its rows can be read 16 bytes at a time
-  const bool scalar = eg::sw::on(eg::Sw::SPLIT_PASS_SCALAR);
-  const int tiled = (!scalar && !oa.kc && lda % 4 == 0 ? 1 : 0) | (!scalar && !ob.kc && ldb % 4 == 0 ? 2 : 0);
-  if (tiled) {
-    const long blocks = (long)TILE_BLOCKS_PER_CU * ctx->compute_units;
-    hipLaunchKernelGGL(split_tiles_kernel, dim3((unsigned)blocks), dim3(SPLIT_NT), 0, ctx->stream, oa, ob, K, tiled, ctx->split_flag,
-                       epoch);
-  } else {
-    const long units_a = M * K / 8, units = (M + N) * K / 8;
-    long blocks = (units + SPLIT_NT * SPLIT_U - 1) / (SPLIT_NT * SPLIT_U);
-    if (blocks > 8L * ctx->compute_units) blocks = 8L * ctx->compute_units;
-    hipLaunchKernelGGL(split_planes_kernel, dim3((unsigned)blocks), dim3(SPLIT_NT), 0, ctx->stream, oa, ob, K, units_a, units,
-                       ctx->split_flag, epoch);
-  }
-  EG_HIP_CHECK(hipGetLastError());
+  rc = split_pass(ctx, {A, lda, M, !trans_a}, {B, ldb, N, trans_b != 0}, K, pa, epoch);
+  if (rc) return rc;
 
   SplitGemmArgs g = {};
   g.pa = pa;
@@ -688,7 +362,6 @@ int sgemm_split(eg_ctx* ctx, int trans_a, int trans_b, long M, long N, long K, c
   g.tiles_m = (int)(M / BM);
   g.tiles_n = (int)(N / BN);
   g.accumulate = accumulate;
-  g.skew = 0;
   g.flag = ctx->split_flag;
   g.epoch = epoch;
   // EG_GEMM_NO_SKEW=1: the in-phase loop, the independent kernel the default one is compared against bit for bit
@@ -704,13 +377,3 @@ int sgemm_split(eg_ctx* ctx, int trans_a, int trans_b, long M, long N, long K, c
 
 }  // namespace gemm
 }  // namespace eg
-
-#ifdef EG_SPLIT_GEMM_STAMPS
-// Diagnostic build only: the stamp sums of the last product launch, [block][wave][front, MFMA section, back, periods].
-extern "C" int eg_debug_split_stamps(unsigned long long* dst, size_t count) {
-  if (count > sizeof(g_split_stamps) / sizeof(unsigned long long)) return EG_ERR_UNSUPPORTED;
-  EG_HIP_CHECK(hipDeviceSynchronize());
-  EG_HIP_CHECK(hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_split_stamps), count * sizeof(unsigned long long)));
-  return 0;
-}
-#endif

@@ -1,8 +1,9 @@
-"""The split-bf16 product kernel with its SIMD partners in different roles (kernels/gemm_split_bf16.hip): every wave
-still issues the same MFMAs on the same accumulators in the same k order, so C has the bits the kernel had before the
-waves were staggered.  tests/golden/split_product_bits.json holds SHA-256 digests of C recorded from that earlier build
-(its commit id is in the file) for three products inside the gate; they must come out again by default, with
-EG_GEMM_NO_SKEW=1 (every wave in phase), and at the end of ten launches queued back to back."""
+"""The split-bf16 product's two k loops (kernels/gemm_split_bf16.hip): the default, split_pingpong_kernel (two barriers
+per k-tile, the two waves of a SIMD one barrier apart), and split_gemm_kernel with EG_GEMM_NO_SKEW=1 (one barrier per
+k-tile, every wave in phase).  In both every wave issues the same MFMAs on the same accumulators in the same k order, so
+C has the bits the kernel had before its waves ever left phase.  tests/golden/split_product_bits.json holds SHA-256
+digests of C recorded from that earlier build (its commit id is in the file) for three products inside the gate; they
+must come out again in both modes, and at the end of ten launches queued back to back."""
 import hashlib
 import json
 import os
@@ -102,7 +103,7 @@ def test_every_case_is_inside_the_gates_planner_predicate(tmp_path):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("no_skew", [False, True], ids=["staggered", "EG_GEMM_NO_SKEW"])
+@pytest.mark.parametrize("no_skew", [False, True], ids=["default", "EG_GEMM_NO_SKEW"])
 @pytest.mark.parametrize("name", sorted(CASES))
 def test_product_has_the_recorded_bits(gpu_ctx, monkeypatch, golden, name, no_skew):
     _set(monkeypatch, "EG_NO_SPLIT_GEMM", False)

@@ -1,4 +1,4 @@
-"""The split pass of the split-bf16 product (kernels/gemm_split_bf16.hip): an operand whose k runs along its leading
+"""The split pass of the split-bf16 product (kernels/gemm_split_pass.hip): an operand whose k runs along its leading
 dimension is read in 16 k x 256 row tiles, 16 bytes per lane, and turned k-contiguous through LDS.  The planes it writes
 and the elements it refuses are those of the unit path with 4-byte loads (EG_SPLIT_PASS_SCALAR=1), so C has the same
 bits: in the four layouts, with tight and with padded leading dimensions (the padding full of NaN), with twice the rows

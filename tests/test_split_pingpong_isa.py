@@ -3,95 +3,28 @@
 Two barriers per k-tile, with the two waves of a SIMD one barrier apart: a load phase (the loaders' LDS-DMA issue behind
 a scalar branch, the fragment reads of the phase's start, the loaders' counted vmcnt), a barrier, the 96 MFMAs, a
 barrier.  One wave's MFMAs run beside its partner's load phase only if ALL of them stay between the two barriers, so
-this test compiles the file for gfx950 as tests/test_split_gemm_isa.py does, finds the loop in the disassembly (the
+this test compiles the file for gfx950 (tests/isa_tools.py), finds the loop in the disassembly (the
 compiler peels the first iteration, so counts are per loop body, not per kernel) and checks exactly that."""
-import os
-import re
-import shutil
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "exprgrad_amd", "csrc")
-HIPCC = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-LLVM_BIN = os.path.join(os.path.dirname(os.path.realpath(HIPCC)), "..", "lib", "llvm", "bin")
+from isa_tools import is_branch as _is_branch, is_dma as _is_dma, is_mfma as _is_mfma
+from isa_tools import kernel_file, kernel_insts, kernel_meta, loop_to_last_back_branch
+
+SOURCE = kernel_file("gemm_split_bf16.hip")
 KERNEL = "split_pingpong_kernel"
 
 
-def _tool(name):
-    path = os.path.join(LLVM_BIN, name)
-    return path if os.path.exists(path) else "/opt/rocm/lib/llvm/bin/" + name
-
-
 @pytest.fixture(scope="module")
-def code_object(tmp_path_factory):
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc not found")
-    co = str(tmp_path_factory.mktemp("isa") / "split.co")
-    subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off",
-                    "-I" + os.path.join(ROOT, "include"), "--cuda-device-only", "--no-gpu-bundle-output", "-c",
-                    os.path.join(CSRC, "kernels", "gemm_split_bf16.hip"), "-o", co], check=True, capture_output=True)
-    return co
-
-
-@pytest.fixture(scope="module")
-def kernel(code_object):
+def kernel():
     """[(address, mnemonic, operands)] of the kernel, in address order."""
-    dis = subprocess.run([_tool("llvm-objdump"), "-d", code_object], capture_output=True, text=True, check=True).stdout
-    insts, inside = [], False
-    for line in dis.splitlines():
-        head = re.match(r"^[0-9a-f]+ <(.+)>:$", line)
-        if head:
-            if not re.match(r"^L\d+$", head.group(1)):     # (labels inside the kernel do not end it)
-                inside = KERNEL in head.group(1) and not head.group(1).endswith(".kd")
-            continue
-        m = re.match(r"^\s*(\S+)\s*(.*?)\s*//\s*([0-9A-Fa-f]+):", line)
-        if inside and m:
-            insts.append((int(m.group(3), 16), m.group(1), m.group(2)))
-    assert insts, "kernel not found in the disassembly"
-    return insts
-
-
-def _is_dma(ins):
-    return ins[1].startswith("buffer_load") and re.search(r"\blds\b", ins[2]) is not None
-
-
-def _is_branch(ins):
-    return ins[1] == "s_branch" or ins[1].startswith("s_cbranch")
-
-
-def _is_mfma(ins):
-    return ins[1].startswith("v_mfma")
-
-
-def _target(insts, ins):
-    """Address a branch jumps to (objdump prints it as a symbol plus offset, or as a signed dword count)."""
-    addr, _, ops = ins
-    m = re.search(r"<[^>]*\+0x([0-9a-fA-F]+)>", ops)
-    if m:
-        return insts[0][0] + int(m.group(1), 16)
-    count = int(ops.split()[0], 0)
-    return addr + 4 + 4 * (count - (1 << 16) if count >= (1 << 15) else count)
+    return kernel_insts(SOURCE, KERNEL)
 
 
 @pytest.fixture(scope="module")
 def body(kernel):
     """The k loop's body: the innermost loop head with matrix instructions behind it, up to the last branch back to it
     (the roles' paths through the load phase end in a backward branch each)."""
-    back = []          # (head index, branch index) of every backward branch around matrix instructions
-    for i, ins in enumerate(kernel):
-        if not _is_branch(ins):
-            continue
-        target = _target(kernel, ins)
-        if target > ins[0]:
-            continue
-        start = next(j for j, other in enumerate(kernel) if other[0] >= target)
-        if any(_is_mfma(x) for x in kernel[start:i + 1]):
-            back.append((start, i))
-    assert back, "no loop around the MFMAs"
-    head = min(back, key=lambda b: b[1] - b[0])[0]
-    return kernel[head:max(i for start, i in back if start == head) + 1]
+    return loop_to_last_back_branch(kernel)
 
 
 def test_every_matrix_instruction_is_the_two_term_form(kernel):
@@ -136,18 +69,8 @@ def test_the_lds_dma_sits_behind_a_scalar_branch_in_front_of_the_first_barrier(b
     assert not [ins for ins in body[first_barrier:] if ins[1] == "s_waitcnt" and "vmcnt" in ins[2]]
 
 
-def test_no_scratch_two_waves_per_simd_and_three_stages_of_lds(code_object, kernel):
-    notes = subprocess.run([_tool("llvm-readelf"), "--notes", code_object], capture_output=True, text=True, check=True).stdout
-    meta = {}
-    for blk in re.split(r"\n  - (?=\.)", notes):                 # one YAML map per kernel
-        name = re.search(r"^ {4}\.name:\s+(\S+)", blk, re.M)
-        if not name or KERNEL not in name.group(1):
-            continue
-        for key in ("private_segment_fixed_size", "group_segment_fixed_size", "vgpr_count", "agpr_count"):
-            m = re.search(r"\." + key + r":\s+(\d+)", blk)
-            if m:
-                meta[key] = int(m.group(1))
-    assert meta, "kernel metadata not found"
+def test_no_scratch_two_waves_per_simd_and_three_stages_of_lds(kernel):
+    meta = kernel_meta(SOURCE, KERNEL)
     assert meta["private_segment_fixed_size"] == 0
     assert not [ins for ins in kernel if ins[1].startswith("scratch_")]
     assert meta["vgpr_count"] + meta.get("agpr_count", 0) <= 256

@@ -38,7 +38,7 @@ def ours(name):
             any(k in name for k in ("colsum", "rowsum", "conv2_halo", "conv2_gradf", "grad_image_operands", "copy_segments", "dgemm_",
                                     "map_kernel", "map_grad_kernel", "bias_add_kernel", "axpy_kernel", "fill_kernel", "sum_partial",
                                     "sum_final", "slab_sum", "zero_ranges", "gemm_streamk", "split_planes_kernel",
-                                    "split_gemm_kernel")))
+                                    "split_tiles_kernel", "split_gemm_kernel", "split_pingpong_kernel")))
 
 
 def main():
