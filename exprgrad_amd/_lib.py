@@ -77,6 +77,10 @@ _SIGS = {
                                   c_void_p, c_i64, c_i64, c_i64, c_void_p, c_i64, c_i64, c_i64, c_int, c_void_p]),
     "eg_attention": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_f32, c_void_p, c_i64, c_i64, c_i64, c_void_p, c_i64, c_i64,
                              c_i64, c_void_p, c_i64, c_i64, c_i64, c_void_p, c_i64, c_i64, c_i64, c_int]),
+    "eg_attention_sums": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_f32] + [c_void_p, c_i64, c_i64, c_i64] * 4 +
+                          [c_int, c_void_p, c_i64, c_i64]),
+    "eg_attention_grad": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_f32] + [c_void_p, c_i64, c_i64, c_i64] * 4 +
+                          [c_void_p, c_i64, c_i64] + [c_void_p, c_i64, c_i64, c_i64] * 4 + [c_int]),
     "eg_bias_add": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_int]),
     "eg_colsum": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_int]),
     "eg_rowsum": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_int]),

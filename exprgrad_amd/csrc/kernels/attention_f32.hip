@@ -24,6 +24,7 @@
 #include "gemm_f32_mfma.hpp"   // xcd_remap, f32x4
 #include "gemm_plan.hpp"       // batched2_c_distinct
 #include "attention_plan.hpp"
+#include "attention_tile.hpp"   // TileRegs, load_rows, store_rows, wave_sync
 
 #include <cmath>
 
@@ -50,61 +51,15 @@ struct AttnArgs {
   unsigned batch1;                     // extent of the inner index
   unsigned first_outer, first_inner;   // the item the launch starts at: launches cut the flattened (o, i1) range
   int tiles_i;                         // blocks per item
+  float* S;                            // eg_attention_sums: the row sums, I floats per item (SUMS instantiations only)
+  long ss0, ss1;
 };
 
 constexpr int ES = TILE_J + 4;   // floats per E row
 
-// A [64][WP] tile in the registers of 256 threads: WP / 16 chunks of four floats each, chunk idx = tid + 256 * i at row
-// idx / (WP / 4), column 4 * (idx % (WP / 4)).
-template <int WP>
-struct TileRegs {
-  f32x4 r[WP / 16];
-};
-
-// Rows [0, rows) x columns [0, width) of `base` (row step ld); everything else of the tile is zero and nothing else is read.
-// A chunk that the view holds whole is one 16-byte load when `vec`; a row's ragged last chunk and every chunk of an operand
-// that is not 16-byte aligned are element loads.
-template <int WP>
-__device__ __forceinline__ void load_rows(TileRegs<WP>& t, const float* __restrict__ base, long ld, long rows, int width, bool vec, int tid) {
-  constexpr int CPR = WP / 4;
-#pragma unroll
-  for (int i = 0; i < WP / 16; ++i) {
-    const int idx = tid + i * THREADS;
-    const int row = idx / CPR, col = (idx % CPR) * 4;
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (row < rows && col < width) {
-      const float* p = base + (long)row * ld + col;
-      if (vec && col + 4 <= width) {
-        v = *reinterpret_cast<const f32x4*>(p);
-      } else {
-        v[0] = p[0];
-        if (col + 1 < width) v[1] = p[1];
-        if (col + 2 < width) v[2] = p[2];
-        if (col + 3 < width) v[3] = p[3];
-      }
-    }
-    t.r[i] = v;
-  }
-}
-
-template <int WP, int STRIDE>
-__device__ __forceinline__ void store_rows(const TileRegs<WP>& t, float* __restrict__ lds, int tid) {
-  constexpr int CPR = WP / 4;
-#pragma unroll
-  for (int i = 0; i < WP / 16; ++i) {
-    const int idx = tid + i * THREADS;
-    *reinterpret_cast<f32x4*>(&lds[(idx / CPR) * STRIDE + (idx % CPR) * 4]) = t.r[i];
-  }
-}
-
-// What one wave wrote to its own LDS rows becomes visible to its other lanes: no block barrier.
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-template <int KP, int DP>
+// SUMS: also store each row's denominator (eg_attention_sums); a compile-time flag, so that eg_attention's kernels are the
+// ones they were.
+template <int KP, int DP, bool SUMS>
 __global__ __launch_bounds__(THREADS) void attention_f32_kernel(AttnArgs a) {
   constexpr int KS = KP + 4, VS = DP + 16;
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -206,6 +161,16 @@ __global__ __launch_bounds__(THREADS) void attention_f32_kernel(AttnArgs a) {
     t += __shfl_xor(t, 8);
     sum[r] = t == INFINITY ? NAN : t;
   }
+  if constexpr (SUMS) {
+    // the value row i is divided by, from the lane that holds column 0 of its group's rows; 0 when there are no keys
+    float* const S = a.S + (long)outer * a.ss0 + (long)inner * a.ss1;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const long row = i0 + w * 16 + 4 * g + r;
+      if (c == 0 && row < a.I) S[row] = sum[r];
+    }
+    if (empty && a.accumulate) return;   // an empty sum adds nothing to O
+  }
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const long row = i0 + w * 16 + 4 * g + r;
@@ -223,37 +188,38 @@ __global__ __launch_bounds__(THREADS) void attention_f32_kernel(AttnArgs a) {
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-template <int KP, int DP>
+template <int KP, int DP, bool SUMS>
 int launch_one(eg_ctx* ctx, unsigned grid, const Plan& p, const AttnArgs& args) {
   // the attribute belongs to the device that is current (set_device has made it the context's): once per device
   constexpr int MAX_DEVICES = 64;
   static bool attr_set[MAX_DEVICES] = {};
   const bool known = ctx->device >= 0 && ctx->device < MAX_DEVICES;
   if (!known || !attr_set[ctx->device]) {
-    EG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_f32_kernel<KP, DP>), hipFuncAttributeMaxDynamicSharedMemorySize,
+    EG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_f32_kernel<KP, DP, SUMS>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)lds_bytes_for(KP, DP)));
     if (known) attr_set[ctx->device] = true;
   }
-  hipLaunchKernelGGL((attention_f32_kernel<KP, DP>), dim3(grid), dim3(p.block), (size_t)p.lds_bytes, ctx->stream, args);
+  hipLaunchKernelGGL((attention_f32_kernel<KP, DP, SUMS>), dim3(grid), dim3(p.block), (size_t)p.lds_bytes, ctx->stream, args);
   EG_HIP_CHECK(hipGetLastError());
   return EG_OK;
 }
 
-template <int KP>
+template <int KP, bool SUMS>
 int launch_kp(eg_ctx* ctx, unsigned grid, const Plan& p, const AttnArgs& args) {
   switch (p.dp) {
-    case 32: return launch_one<KP, 32>(ctx, grid, p, args);
-    case 64: return launch_one<KP, 64>(ctx, grid, p, args);
-    default: return launch_one<KP, 128>(ctx, grid, p, args);
+    case 32: return launch_one<KP, 32, SUMS>(ctx, grid, p, args);
+    case 64: return launch_one<KP, 64, SUMS>(ctx, grid, p, args);
+    default: return launch_one<KP, 128, SUMS>(ctx, grid, p, args);
   }
 }
 
-// 9 kernels: the padded K x the padded D
+// 9 kernels: the padded K x the padded D; 9 more that store the row sums
+template <bool SUMS>
 int launch_config(eg_ctx* ctx, unsigned grid, const Plan& p, const AttnArgs& args) {
   switch (p.kp) {
-    case 32: return launch_kp<32>(ctx, grid, p, args);
-    case 64: return launch_kp<64>(ctx, grid, p, args);
-    default: return launch_kp<128>(ctx, grid, p, args);
+    case 32: return launch_kp<32, SUMS>(ctx, grid, p, args);
+    case 64: return launch_kp<64, SUMS>(ctx, grid, p, args);
+    default: return launch_kp<128, SUMS>(ctx, grid, p, args);
   }
 }
 
@@ -262,25 +228,30 @@ int launch_config(eg_ctx* ctx, unsigned grid, const Plan& p, const AttnArgs& arg
 namespace eg {
 namespace attention {
 
-// The one internal entry: eg_attention and the model layer's attention launches (host/run.cpp) both come here.
-int attention_f32(eg_ctx* ctx, long batch0, long batch1, long I, long J, long K, long D, float scale, const float* Q, long ldq, long stride_q0,
-                  long stride_q1, const float* Kk, long ldk, long stride_k0, long stride_k1, const float* V, long ldv, long stride_v0, long stride_v1,
-                  float* O, long ldo, long stride_o0, long stride_o1, int accumulate) {
-  EG_REQUIRE(ctx, EG_ERR_INVALID, "eg_attention: ctx is NULL");
-  EG_REQUIRE(batch0 >= 0 && batch1 >= 0 && I >= 0 && J >= 0 && K >= 0 && D >= 0, EG_ERR_INVALID, "eg_attention: negative extent");
-  EG_REQUIRE(batch0 < (1L << 31) && batch1 < (1L << 31), EG_ERR_INVALID, "eg_attention: a batch extent of 2^31 or more");
+// The one launcher: eg_attention and the model layer's attention launches (host/run.cpp) come here with Sums == NULL,
+// eg_attention_sums with the row sums' view.  `name` is the entry the messages speak of.
+static int attention_launch(const char* name, eg_ctx* ctx, long batch0, long batch1, long I, long J, long K, long D, float scale, const float* Q,
+                            long ldq, long stride_q0, long stride_q1, const float* Kk, long ldk, long stride_k0, long stride_k1, const float* V,
+                            long ldv, long stride_v0, long stride_v1, float* O, long ldo, long stride_o0, long stride_o1, int accumulate, float* Sums,
+                            long stride_s0, long stride_s1) {
+  EG_REQUIRE(ctx, EG_ERR_INVALID, "%s: ctx is NULL", name);
+  EG_REQUIRE(batch0 >= 0 && batch1 >= 0 && I >= 0 && J >= 0 && K >= 0 && D >= 0, EG_ERR_INVALID, "%s: negative extent", name);
+  EG_REQUIRE(batch0 < (1L << 31) && batch1 < (1L << 31), EG_ERR_INVALID, "%s: a batch extent of 2^31 or more", name);
   EG_REQUIRE(stride_q0 >= 0 && stride_q1 >= 0 && stride_k0 >= 0 && stride_k1 >= 0 && stride_v0 >= 0 && stride_v1 >= 0, EG_ERR_INVALID,
-             "eg_attention: negative stride");
-  if (batch0 == 0 || batch1 == 0 || I == 0 || D == 0) return EG_OK;
-  EG_REQUIRE(O, EG_ERR_INVALID, "eg_attention: O is NULL");
-  EG_REQUIRE(J == 0 || V, EG_ERR_INVALID, "eg_attention: NULL operand");
-  EG_REQUIRE(J == 0 || K == 0 || (Q && Kk), EG_ERR_INVALID, "eg_attention: NULL operand");
-  EG_REQUIRE(ldq >= K && ldk >= K && ldv >= D, EG_ERR_INVALID, "eg_attention: leading dimension smaller than the row length");
-  EG_REQUIRE(eg::gemm::batched2_c_distinct(batch0, stride_o0, batch1, stride_o1, I, ldo, D), EG_ERR_INVALID,
-             "eg_attention: ldo, stride_o0 and stride_o1 make elements of O share an address");
-  EG_REQUIRE(K <= MAX_HEAD, EG_ERR_UNSUPPORTED, "eg_attention: K = %ld is above the limit of %d", K, MAX_HEAD);
-  EG_REQUIRE(D <= MAX_HEAD, EG_ERR_UNSUPPORTED, "eg_attention: D = %ld is above the limit of %d", D, MAX_HEAD);
-  if (J == 0 && accumulate) return EG_OK;   // an empty sum adds nothing
+             "%s: negative stride", name);
+  if (batch0 == 0 || batch1 == 0 || I == 0 || (D == 0 && !Sums)) return EG_OK;
+  EG_REQUIRE(D == 0 || O, EG_ERR_INVALID, "%s: O is NULL", name);
+  EG_REQUIRE(J == 0 || D == 0 || V, EG_ERR_INVALID, "%s: NULL operand", name);
+  EG_REQUIRE(J == 0 || K == 0 || (Q && Kk), EG_ERR_INVALID, "%s: NULL operand", name);
+  EG_REQUIRE(ldq >= K && ldk >= K && ldv >= D, EG_ERR_INVALID, "%s: leading dimension smaller than the row length", name);
+  EG_REQUIRE(D == 0 || eg::gemm::batched2_c_distinct(batch0, stride_o0, batch1, stride_o1, I, ldo, D), EG_ERR_INVALID,
+             "%s: ldo, stride_o0 and stride_o1 make elements of O share an address", name);
+  // the row sums: one row of I columns per item
+  EG_REQUIRE(!Sums || eg::gemm::batched2_c_distinct(batch0, stride_s0, batch1, stride_s1, 1, I, I), EG_ERR_INVALID,
+             "%s: stride_s0 and stride_s1 make elements of Sums share an address", name);
+  EG_REQUIRE(K <= MAX_HEAD, EG_ERR_UNSUPPORTED, "%s: K = %ld is above the limit of %d", name, K, MAX_HEAD);
+  EG_REQUIRE(D <= MAX_HEAD, EG_ERR_UNSUPPORTED, "%s: D = %ld is above the limit of %d", name, D, MAX_HEAD);
+  if (J == 0 && accumulate && !Sums) return EG_OK;   // an empty sum adds nothing
   int rc = eg::set_device(ctx);
   if (rc) return rc;
 
@@ -290,13 +261,14 @@ int attention_f32(eg_ctx* ctx, long batch0, long batch1, long I, long J, long K,
   pr.k = {ldk, stride_k0, stride_k1, aligned16(Kk)};
   pr.v = {ldv, stride_v0, stride_v1, aligned16(V)};
   pr.o = {ldo, stride_o0, stride_o1, aligned16(O)};
+  pr.sums = Sums != nullptr;
   pr.cus = ctx->compute_units;
   const Plan p = plan_attention(pr);
-  EG_REQUIRE(p.supported, EG_ERR_UNSUPPORTED, "eg_attention: %s", p.reason);
+  EG_REQUIRE(p.supported, EG_ERR_UNSUPPORTED, "%s: %s", name, p.reason);
 
   for (long n = 0; n < p.launches; ++n) {
     const Launch l = plan_launch(p, n);
-    EG_REQUIRE(l.items > 0 && l.grid > 0 && l.grid <= eg::gemm::BATCHED_MAX_BLOCKS, EG_ERR_INVALID, "eg_attention: launch out of range");
+    EG_REQUIRE(l.items > 0 && l.grid > 0 && l.grid <= eg::gemm::BATCHED_MAX_BLOCKS, EG_ERR_INVALID, "%s: launch out of range", name);
     AttnArgs args = {};
     args.Q = Q, args.Kk = Kk, args.V = V, args.O = O;
     args.ldq = ldq, args.ldk = ldk, args.ldv = ldv, args.ldo = ldo;
@@ -310,10 +282,18 @@ int attention_f32(eg_ctx* ctx, long batch0, long batch1, long I, long J, long K,
     args.first_outer = (unsigned)(l.first / batch1);
     args.first_inner = (unsigned)(l.first % batch1);
     args.tiles_i = (int)p.tiles_i;
-    rc = launch_config(ctx, (unsigned)l.grid, p, args);
+    args.S = Sums, args.ss0 = stride_s0, args.ss1 = stride_s1;
+    rc = Sums ? launch_config<true>(ctx, (unsigned)l.grid, p, args) : launch_config<false>(ctx, (unsigned)l.grid, p, args);
     if (rc) return rc;
   }
   return EG_OK;
+}
+
+int attention_f32(eg_ctx* ctx, long batch0, long batch1, long I, long J, long K, long D, float scale, const float* Q, long ldq, long stride_q0,
+                  long stride_q1, const float* Kk, long ldk, long stride_k0, long stride_k1, const float* V, long ldv, long stride_v0, long stride_v1,
+                  float* O, long ldo, long stride_o0, long stride_o1, int accumulate) {
+  return attention_launch("eg_attention", ctx, batch0, batch1, I, J, K, D, scale, Q, ldq, stride_q0, stride_q1, Kk, ldk, stride_k0, stride_k1, V,
+                          ldv, stride_v0, stride_v1, O, ldo, stride_o0, stride_o1, accumulate, nullptr, 0, 0);
 }
 
 }  // namespace attention
@@ -325,4 +305,13 @@ extern "C" int eg_attention(eg_ctx* ctx, int64_t batch0, int64_t batch1, int64_t
                             int64_t stride_o1, int accumulate) {
   return eg::attention::attention_f32(ctx, batch0, batch1, I, J, K, D, scale, Q, ldq, stride_q0, stride_q1, Kk, ldk, stride_k0, stride_k1, V, ldv,
                                       stride_v0, stride_v1, O, ldo, stride_o0, stride_o1, accumulate);
+}
+
+extern "C" int eg_attention_sums(eg_ctx* ctx, int64_t batch0, int64_t batch1, int64_t I, int64_t J, int64_t K, int64_t D, float scale, const float* Q,
+                                 int64_t ldq, int64_t stride_q0, int64_t stride_q1, const float* Kk, int64_t ldk, int64_t stride_k0,
+                                 int64_t stride_k1, const float* V, int64_t ldv, int64_t stride_v0, int64_t stride_v1, float* O, int64_t ldo,
+                                 int64_t stride_o0, int64_t stride_o1, int accumulate, float* Sums, int64_t stride_s0, int64_t stride_s1) {
+  return eg::attention::attention_launch(Sums ? "eg_attention_sums" : "eg_attention", ctx, batch0, batch1, I, J, K, D, scale, Q, ldq, stride_q0,
+                                         stride_q1, Kk, ldk, stride_k0, stride_k1, V, ldv, stride_v0, stride_v1, O, ldo, stride_o0, stride_o1,
+                                         accumulate, Sums, stride_s0, stride_s1);
 }

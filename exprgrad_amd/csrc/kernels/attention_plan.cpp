@@ -9,7 +9,7 @@ namespace attention {
 
 Plan plan_attention(const Problem& p) {
   Plan r;
-  if (p.batch0 < 1 || p.batch1 < 1 || p.I < 1 || p.J < 0 || p.K < 0 || p.D < 1) {
+  if (p.batch0 < 1 || p.batch1 < 1 || p.I < 1 || p.J < 0 || p.K < 0 || p.D < (p.sums ? 0 : 1)) {
     r.reason = "an empty or negative extent";
     return r;
   }
@@ -49,6 +49,60 @@ Launch plan_launch(const Plan& plan, long index) {
   l.first = index * plan.items_per_launch;
   l.items = std::min(plan.items_per_launch, plan.items - l.first);
   l.grid = l.items * plan.tiles_i;
+  return l;
+}
+
+static void cut(GradKernel& k, long items, long tiles) {
+  k.tiles = tiles;
+  k.grid = items * tiles;
+  k.items_per_launch = std::max(1L, eg::gemm::BATCHED_MAX_BLOCKS / std::max(1L, tiles));
+  k.launches = tiles > 0 ? (items + k.items_per_launch - 1) / k.items_per_launch : 0;
+}
+
+// Empty I, J, K and D are plans too (a kernel with no tiles has no launches; the entry decides what an empty extent
+// writes); empty batch extents are not.
+GradPlan plan_attention_grad(const GradProblem& p) {
+  GradPlan r;
+  if (p.batch0 < 1 || p.batch1 < 1 || p.I < 0 || p.J < 0 || p.K < 0 || p.D < 0) {
+    r.reason = "an empty batch or a negative extent";
+    return r;
+  }
+  if (p.K > MAX_HEAD) {
+    r.reason = "K above 128";
+    return r;
+  }
+  if (p.D > MAX_HEAD) {
+    r.reason = "D above 128";
+    return r;
+  }
+  r.kp = padded_head(p.K);
+  r.dp = padded_head(p.D);
+  r.dq.lds_bytes = grad_dq_lds_bytes(r.kp, r.dp);
+  r.dkv.lds_bytes = grad_dkv_lds_bytes(r.kp, r.dp);
+  if (r.dq.lds_bytes > LDS_LIMIT || r.dkv.lds_bytes > LDS_LIMIT) {
+    r.reason = "the tiles exceed the LDS of a CU";
+    return r;
+  }
+  const long tiles_i = (p.I + 63) / 64, tiles_j = (p.J + 63) / 64;
+  if (tiles_i > eg::gemm::BATCHED_MAX_BLOCKS || tiles_j > eg::gemm::BATCHED_MAX_BLOCKS) {
+    r.reason = "an item has more tiles than one launch has blocks";
+    return r;
+  }
+  r.vec_q = operand_vec16(p.q), r.vec_k = operand_vec16(p.k), r.vec_v = operand_vec16(p.v), r.vec_o = operand_vec16(p.o);
+  r.vec_s = operand_vec16(p.s), r.vec_do = operand_vec16(p.dout);
+  r.vec_dq = operand_vec16(p.dq), r.vec_dk = operand_vec16(p.dk), r.vec_dv = operand_vec16(p.dv);
+  r.items = p.batch0 * p.batch1;
+  cut(r.dq, r.items, tiles_i);
+  cut(r.dkv, r.items, tiles_j);
+  r.supported = true;
+  return r;
+}
+
+Launch plan_grad_launch(const GradPlan& plan, const GradKernel& kernel, long index) {
+  Launch l;
+  l.first = index * kernel.items_per_launch;
+  l.items = std::min(kernel.items_per_launch, plan.items - l.first);
+  l.grid = l.items * kernel.tiles;
   return l;
 }
 

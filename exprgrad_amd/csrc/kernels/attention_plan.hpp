@@ -24,6 +24,7 @@ struct Operand {
 struct Problem {
   long batch0 = 0, batch1 = 0, I = 0, J = 0, K = 0, D = 0;
   Operand q, k, v, o;
+  bool sums = false;   // eg_attention_sums: the row sums are stored too, and D == 0 still has them to store
   int cus = 256;
 };
 
@@ -63,6 +64,48 @@ Plan plan_attention(const Problem& p);
 
 // Launch `index` of a plan, index in [0, plan.launches).
 Launch plan_launch(const Plan& plan, long index);
+
+// ---- The backward pass (attention_grad_f32.hip): two kernels, one over tiles of 64 query rows (dQ), one over tiles of 64
+// keys (dK and dV).  Both keep the block's own rows in registers and walk the other axis in tiles of 64.
+struct GradProblem {
+  long batch0 = 0, batch1 = 0, I = 0, J = 0, K = 0, D = 0;
+  Operand q, k, v, o, s, dout, dq, dk, dv;   // s: the row sums, ld unused (0)
+  int cus = 256;
+};
+
+// One of the two kernels: `tiles` blocks per item, cut along the flattened item range like the forward.
+struct GradKernel {
+  int tile = 64;             // rows of the block's own axis
+  int step = 64;             // rows of one pass of its loop over the other axis
+  long tiles = 0, grid = 0, items_per_launch = 0, launches = 0;
+  long lds_bytes = 0;
+};
+
+struct GradPlan {
+  bool supported = false;
+  const char* reason = "";
+  int kp = 0, dp = 0;
+  // 16-byte accesses per operand: loads of Q, Kk, V, O, Sums and dO, stores (and, accumulating, loads) of dQ, dK and dV
+  bool vec_q = false, vec_k = false, vec_v = false, vec_o = false, vec_s = false, vec_do = false, vec_dq = false, vec_dk = false, vec_dv = false;
+  long items = 0;
+  GradKernel dq, dkv;
+  int block = THREADS;
+};
+
+// Floats per LDS row of a tile that is read both as an NT operand (16 rows x 4 columns per instruction) and as an NN
+// operand (4 rows x 16 columns): see attention_grad_f32.hip.
+constexpr int GRAD_PAD_BOTH = 20, GRAD_PAD_NT = 4;
+
+// dQ kernel: K tile [64][kp + 20] (NT for the scores, NN for dS * K), V tile [64][dp + 4] (NT only), the waves' dS rows
+// [4][16][68], and 1 / L and delta of the block's 64 rows.
+inline long grad_dq_lds_bytes(int kp, int dp) { return 4L * (64 * (kp + GRAD_PAD_BOTH) + 64 * (dp + GRAD_PAD_NT) + 4 * 16 * 68 + 2 * 64); }
+// dK/dV kernel: Q tile [64][kp + 20] and dO tile [64][dp + 20] (both read both ways), the waves' rows, 1 / L and delta.
+inline long grad_dkv_lds_bytes(int kp, int dp) { return 4L * (64 * (kp + GRAD_PAD_BOTH) + 64 * (dp + GRAD_PAD_BOTH) + 4 * 16 * 68 + 2 * 64); }
+
+GradPlan plan_attention_grad(const GradProblem& p);
+
+// Launch `index` of one of a plan's kernels, index in [0, kernel.launches).
+Launch plan_grad_launch(const GradPlan& plan, const GradKernel& kernel, long index);
 
 }  // namespace attention
 }  // namespace eg

@@ -54,6 +54,27 @@ def attention(ctx, batch0, batch1, I, J, K, D, scale, Q, ldq, strides_q, Kk, ldk
          strides_k[0], strides_k[1], _p(V), ldv, strides_v[0], strides_v[1], _p(O), ldo, strides_o[0], strides_o[1], int(accumulate))
 
 
+def attention_sums(ctx, batch0, batch1, I, J, K, D, scale, Q, ldq, strides_q, Kk, ldk, strides_k, V, ldv, strides_v, O, ldo, strides_o, Sums,
+                   strides_s, accumulate=False):
+    """`attention` that also stores each row's denominator L_i = sum_j exp(scale * q_i . k_j), which attention_grad needs: item
+    (o, i1) writes I floats at Sums + o * strides_s[0] + i1 * strides_s[1].  O has the bits `attention` gives; Sums is always
+    overwritten (accumulate concerns O only); Sums = None is `attention`."""
+    call("eg_attention_sums", ctx.handle, batch0, batch1, I, J, K, D, float(scale), _p(Q), ldq, strides_q[0], strides_q[1], _p(Kk), ldk,
+         strides_k[0], strides_k[1], _p(V), ldv, strides_v[0], strides_v[1], _p(O), ldo, strides_o[0], strides_o[1], int(accumulate), _p(Sums),
+         strides_s[0], strides_s[1])
+
+
+def attention_grad(ctx, batch0, batch1, I, J, K, D, scale, Q, ldq, strides_q, Kk, ldk, strides_k, V, ldv, strides_v, O, ldo, strides_o, Sums,
+                   strides_s, dO, lddo, strides_do, dQ, lddq, strides_dq, dK, lddk, strides_dk, dV, lddv, strides_dv, accumulate=0):
+    """Fused attention backward, two launches that store nothing of size I x J: from Q, Kk, V, the forward's O and Sums
+    (attention_sums with accumulate = False) and dO, the gradients dQ [I, K], dK [J, K] and dV [J, D] of every item.  Strides as
+    pairs of floats, as in `attention`; accumulate bit 0 adds to dQ, bit 1 to dK, bit 2 to dV.  K and D at most 128."""
+    call("eg_attention_grad", ctx.handle, batch0, batch1, I, J, K, D, float(scale), _p(Q), ldq, strides_q[0], strides_q[1], _p(Kk), ldk,
+         strides_k[0], strides_k[1], _p(V), ldv, strides_v[0], strides_v[1], _p(O), ldo, strides_o[0], strides_o[1], _p(Sums), strides_s[0],
+         strides_s[1], _p(dO), lddo, strides_do[0], strides_do[1], _p(dQ), lddq, strides_dq[0], strides_dq[1], _p(dK), lddk, strides_dk[0],
+         strides_dk[1], _p(dV), lddv, strides_dv[0], strides_dv[1], int(accumulate))
+
+
 def dgemm_batched(ctx, batch, M, N, K, A, lda, stride_a, B, ldb, stride_b, C, ldc, stride_c, trans_a=False, trans_b=False,
                   accumulate=False, bias=None):
     """The float64 form of sgemm_batched: item b uses A + b * stride_a, B + b * stride_b, C + b * stride_c (strides and

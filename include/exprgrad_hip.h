@@ -245,6 +245,64 @@ int eg_attention(eg_ctx* ctx, int64_t batch0, int64_t batch1, int64_t I, int64_t
                  const float* V, int64_t ldv, int64_t stride_v0, int64_t stride_v1,
                  float* O, int64_t ldo, int64_t stride_o0, int64_t stride_o1, int accumulate);
 
+/* eg_attention that also stores its denominators, for eg_attention_grad: the first 25 arguments are eg_attention's, and item
+ * (o, i1) writes Sums[o * stride_s0 + i1 * stride_s1 + i] = L_i = sum_j exp(scale * q_i . k_j) for i in [0, I): the value the
+ * kernel divides row i by, after its fixed-order sum (NaN where that sum overflowed, 0 when J == 0).
+ *   - O has the bits eg_attention gives on the same arguments, whether or not Sums is given; Sums == NULL is eg_attention.
+ *   - Sums is always overwritten, never read: accumulate concerns O only.  With J == 0 and accumulate != 0, O is left alone
+ *     and Sums is zeros; with D == 0, O is empty and Sums is still written.
+ *   - Rows i >= I and everything outside the items' I floats are never written.
+ *   - Sums must not alias itself: items of I contiguous floats must be disjoint, batched2_c_distinct(batch0, stride_s0,
+ *     batch1, stride_s1, 1, I, I), else EG_ERR_INVALID.
+ *   - Every other refusal is eg_attention's, with a message that names eg_attention_sums.
+ * The same kernels with one compile-time flag in the row sums' epilogue (kernels/attention_f32.hip); two calls give the
+ * same bits. */
+int eg_attention_sums(eg_ctx* ctx, int64_t batch0, int64_t batch1, int64_t I, int64_t J, int64_t K, int64_t D, float scale,
+                      const float* Q, int64_t ldq, int64_t stride_q0, int64_t stride_q1,
+                      const float* Kk, int64_t ldk, int64_t stride_k0, int64_t stride_k1,
+                      const float* V, int64_t ldv, int64_t stride_v0, int64_t stride_v1,
+                      float* O, int64_t ldo, int64_t stride_o0, int64_t stride_o1, int accumulate,
+                      float* Sums, int64_t stride_s0, int64_t stride_s1);
+
+/* Fused attention backward: for every item, with s_ij = q_i . k_j, p_ij = exp(scale * s_ij) / L_i, O the forward's result
+ * (computed with accumulate == 0), Sums its denominators L_i (eg_attention_sums) and dO the gradient of O,
+ *   delta_i = dO_i . o_i,  dP_ij = dO_i . v_j,  dS_ij = scale * p_ij * (dP_ij - delta_i),
+ *   dV_j (+)= sum_i p_ij dO_i,   dQ_i (+)= sum_j dS_ij k_j,   dK_j (+)= sum_i dS_ij q_i
+ * — the gradients `derive` emits for the five-statement program (scores, scale, row sums, softmax, context), up to rounding.
+ * Q, dQ are I x K, Kk, dK J x K, V, dV J x D, O, dO I x D, Sums I floats per item; addressing as for eg_attention.
+ * Two launches (kernels/attention_grad_f32.hip): batch0 x batch1 x ceil(I / 64) blocks for dQ, batch0 x batch1 x
+ * ceil(J / 64) blocks for dK and dV, each split along the flattened (o, i1) range when it would exceed 2^22 blocks.  Both
+ * recompute the probabilities tile by tile on the f32 matrix instruction (S and dP are computed in both): nothing of size
+ * I x J is stored, no atomics, no workspace, never the split-bf16 route; two calls give the same bits.
+ *   - accumulate: bit 0 adds to dQ, bit 1 to dK, bit 2 to dV; an output whose bit is clear is not read.  Other bits are
+ *     EG_ERR_INVALID.
+ *   - Strides of the six inputs: each may be 0 (the operand is shared along that index); a negative one is EG_ERR_INVALID.
+ *   - Each output must not alias itself: batched2_c_distinct on its own shape, as for eg_attention's O, else EG_ERR_INVALID.
+ *     Aliasing between different operands is undefined.
+ *   - EG_ERR_INVALID, with a message that names eg_attention_grad: a NULL ctx, a NULL operand of a non-empty call, a negative
+ *     extent, a leading dimension shorter than a row, a batch extent of 2^31 or more.
+ *   - EG_ERR_UNSUPPORTED, with a message that names the limit: K > 128 or D > 128.  I and J are arbitrary.
+ *   - A zero batch extent launches nothing.  I == 0 or J == 0: the outputs that have elements are zeros where their bit is
+ *     clear and untouched otherwise.  K == 0: dQ and dK are empty, dV is computed with every score 0.  D == 0: dV is empty, dQ
+ *     and dK are zeros where their bit is clear.
+ *   - No alignment is required.  Each of the nine operands, inputs and outputs alike, is accessed with 16-byte loads or stores
+ *     when its pointer is 16-byte aligned and its leading dimension and both its strides are multiples of 4, element by
+ *     element otherwise.
+ *   - Elements outside the views are never read and never written, whatever they hold; a row i >= I or a key j >= J of a
+ *     tile contributes exactly 0.
+ * Results for rows whose L_i is not finite (or 0) are unspecified: such rows may be NaN throughout their item, in dK and dV
+ * as well as in dQ. */
+int eg_attention_grad(eg_ctx* ctx, int64_t batch0, int64_t batch1, int64_t I, int64_t J, int64_t K, int64_t D, float scale,
+                      const float* Q, int64_t ldq, int64_t stride_q0, int64_t stride_q1,
+                      const float* Kk, int64_t ldk, int64_t stride_k0, int64_t stride_k1,
+                      const float* V, int64_t ldv, int64_t stride_v0, int64_t stride_v1,
+                      const float* O, int64_t ldo, int64_t stride_o0, int64_t stride_o1,
+                      const float* Sums, int64_t stride_s0, int64_t stride_s1,
+                      const float* dO, int64_t lddo, int64_t stride_do0, int64_t stride_do1,
+                      float* dQ, int64_t lddq, int64_t stride_dq0, int64_t stride_dq1,
+                      float* dK, int64_t lddk, int64_t stride_dk0, int64_t stride_dk1,
+                      float* dV, int64_t lddv, int64_t stride_dv0, int64_t stride_dv1, int accumulate);
+
 /* out[y,x] (+)= bias[x]   — dense's second kernel, dnn.nim:22-24. out is [rows, cols]. */
 int eg_bias_add(eg_ctx* ctx, int64_t rows, int64_t cols, const float* bias, float* out,
                 int accumulate);
