@@ -606,7 +606,7 @@ void dead_code_elim(Kernel& k) {
 }
 
 // derive(kernel, gradTensors)  passes.nim:519-549: one gradient kernel per read, in read order.
-int derive_kernel(const Kernel& kernel, const std::map<int, int>& grad_tensors, std::vector<Kernel>& out) {
+int derive_kernel(const Kernel& kernel, int index, const std::map<int, int>& grad_tensors, std::vector<Kernel>& out) {
   Kernel base = kernel;
   std::map<int, int> grad;
   const int write_grad = base.alloc();
@@ -621,10 +621,13 @@ int derive_kernel(const Kernel& kernel, const std::map<int, int>& grad_tensors, 
   int rc = derive_instrs(kernel.instrs, base, grad, extra);
   if (rc) return rc;
   base.instrs.insert(base.instrs.end(), extra.begin(), extra.end());
-  for (auto& read : kernel.reads) {
+  for (size_t r = 0; r < kernel.reads.size(); ++r) {
+    const Op& read = kernel.reads[r];
     auto g = grad.find(read.reg);
     if (g == grad.end()) continue;
     Kernel gk = base;
+    gk.derived_from = index;   // (kernels in front of the generator keep their index in Target::all)
+    gk.derived_read = (int)r;
     gk.result = g->second;
     gk.write.tensor = grad_tensors.at(read.tensor);
     gk.write.raw = read.raw;
@@ -714,7 +717,7 @@ int generate(Program& prog, Target& t) {
           }
           continue;
         }
-        int rc = derive_kernel(k2, grad_tensors, grads);
+        int rc = derive_kernel(k2, (int)jj, grad_tensors, grads);
         if (rc) return rc;
       }
       ks.erase(ks.begin() + i);

@@ -79,6 +79,9 @@ struct Kernel {
   int gen_tensor = 0;  // Backwards: the loss; Gradient: differentiate with respect to this tensor
   int gen_dest = 0;    // Gradient: tensor that receives the gradient
   bool is_seed = false;  // the gradLoss{i} = 1 kernel (passes.nim:575-606)
+  // derive's record of a gradient kernel's origin: the index in Target::all of the kernel it differentiates and which of
+  // that kernel's reads it is the gradient of (-1: not derived — written in the program or a custom gradient)
+  int derived_from = -1, derived_read = -1;
   bool f64 = false;      // the program computes in float64 (compile[float64], model.nim:253-260): set on every kernel by compile_program
   int alloc() { return ++nregs; }
 };

@@ -329,6 +329,15 @@ void describe(eg_model* m) {
       for (int s = p; s < p + am.n; ++s) attn[s] = {p, p + am.n - 1};
       p += am.n - 1;
     }
+    // training steps over a chain (match_attention_fit), where the model asks for them (eg_model_fuse_attention_fit): the
+    // chain is one eg_attn launch that stores the sums, its gradient kernels one eg_attn_grad launch
+    std::vector<int> fit_fwd(ts.lowered.size(), -1), fit_bwd(ts.lowered.size(), -1);
+    for (int p = 0; m->fuse_attention_fit && !m->prog.f64 && p < (int)ts.lowered.size(); ++p) {
+      AttentionFitMatch fm;
+      if (fit_fwd[p] >= 0 || fit_bwd[p] >= 0 || !match_attention_fit(m->prog, *ts.target, p, fm)) continue;
+      for (int s : fm.forward) fit_fwd[s] = p;
+      for (int s : fm.backward) fit_bwd[s] = p;
+    }
     for (size_t p = 0; p < ts.lowered.size(); ++p) {
       const Lowered& lo = ts.lowered[p];
       const Kernel& k = ts.target->all[lo.all_index];
@@ -344,6 +353,8 @@ void describe(eg_model* m) {
       os << "  [" << p << "] " << kind;
       if (lo.kind == StepKind::Gemm || lo.kind == StepKind::GemmBatched) os << (lo.gemm.trans_a ? " T" : " N") << (lo.gemm.trans_b ? "T" : "N");
       if (attn[p].first >= 0) os << " (eg_attn: one launch for kernels " << attn[p].first << ".." << attn[p].second << " when the plan fuses them)";
+      if (fit_fwd[p] >= 0) os << " (eg_attn with the sums: one launch for the chain at kernel " << fit_fwd[p] << " when the plan fuses the training step)";
+      if (fit_bwd[p] >= 0) os << " (eg_attn_grad: one launch for the gradient kernels of the chain at kernel " << fit_bwd[p] << " when the plan fuses the training step)";
       os << " : " << to_text(k) << "\n";
     }
   }

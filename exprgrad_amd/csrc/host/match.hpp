@@ -59,6 +59,7 @@ struct Batched2GemmMatch {
 // kernel outside the chain reads, and that is not the target's output.  (Gradient-bucket membership is the planner's check.)
 struct AttentionMatch {
   int n = 0;                           // kernels of the chain: 5 with a scale map, 4 without
+  std::vector<int> at;                 // their live positions: p, p + 1, ... (match_attention_chain with gaps: ascending)
   float scale = 1.f;
   Batched2GemmMatch scores, context;   // of kernels [0] and [n - 1]
   int t_scores = 0, t_scaled = 0, t_sums = 0, t_softmax = 0;   // t_scaled: 0 without a scale map
@@ -66,6 +67,43 @@ struct AttentionMatch {
 };
 // The chain at live positions [p, p + m.n) of `t`?  why (optional): the reason of a refusal, a constant string.
 bool match_attention(const Program& prog, const Target& t, int p, AttentionMatch& m, const char** why = nullptr);
+
+// The two halves of match_attention, shared with match_attention_fit (match_attention_grad.cpp):
+//   the kernels' structure at [p, p + m.n), nothing about who else touches the tensors (gaps: kernels that touch none of the
+//   chain's four intermediates may stand between its members — a projection of v between the softmax and the context);
+bool match_attention_chain(const Target& t, int p, AttentionMatch& m, const char** why = nullptr, bool gaps = false);
+//   and the privacy of tensors: every xs[i] (0: skipped) is a Result, not the target's output, none of `operands`, read by
+//   no live kernel outside `members` (live positions; `read_outside` is the refusal's reason) and written by exactly
+//   writers[i] live kernels.
+bool attention_private(const Program& prog, const Target& t, const std::vector<int>& xs, const std::vector<int>& writers, const std::vector<int>& operands,
+                       const std::vector<int>& members, const char* read_outside, const char** why);
+// every dimension of `op` a single bare loop register of `k`, all different: those registers
+bool bare_regs(const Kernel& k, const Op& op, std::vector<int>& regs);
+// `loops` loops without bounds, no setup, no computed indices
+bool plain_loops(const Kernel& k, size_t loops);
+
+// A training step over the chain (match_attention_grad.cpp): the forward chain at live position p and the gradient kernels
+// that the library's own derive (kd.cpp) makes of it, anywhere behind it in the target —
+//   dsoftmax[b,h,i,j] ++= dcontext[..] * v[..]                  NT product          dv[..] ++= softmax[b,h,i,j] * dcontext[..]
+//   de[b,h,i,j]       ++= dsoftmax / sums * exp(e)              map                 dsums[b,h,i] ++= -exp(e) * (dsoftmax / (sums * sums))
+//   de[b,h,i,j]       ++= dsums[b,h,i] * exp(e)                 map                 dscores[b,h,i,j] ++= de[b,h,i,j] * literal (with a scale map)
+//   dq[..]            ++= dscores[b,h,i,j] * kk[..]             product             dk[..] ++= dscores[b,h,i,j] * q[..]
+// — eight with a scale map, seven without: what eg_attention_sums and eg_attention_grad compute in three launches.  Found by
+// the tensors they read and write, held to the registers' positions that the forward products fix and to the instructions
+// derive emits; where derive recorded a kernel's origin (Kernel::derived_from) that has to agree too.  The scores, the scaled
+// scores, the softmax and the four gradients between the products are `hidden`: Results that the members alone read and
+// write and that are not the target's output.  The sums and the context are ordinary tensors: the backward reads them.
+struct AttentionFitMatch {
+  AttentionMatch fwd;
+  int t_do = 0, t_dq = 0, t_dk = 0, t_dv = 0;
+  int t_dsoftmax = 0, t_dsums = 0, t_de = 0, t_dscores = 0;   // without a scale map de is dscores: t_de == t_dscores
+  // live positions of the gradient kernels, in the order above (dscale: -1 without a scale map)
+  int p_dsoftmax = -1, p_dv = -1, p_de = -1, p_dsums = -1, p_de_sums = -1, p_dscale = -1, p_dq = -1, p_dk = -1;
+  Batched2GemmMatch dsoftmax, dv, dq, dk;
+  std::vector<int> forward, backward;   // live positions of the members, ascending
+  std::vector<int> hidden;
+};
+bool match_attention_fit(const Program& prog, const Target& t, int p, AttentionFitMatch& m, const char** why = nullptr);
 
 bool bare2(const Op& op, int& r0, int& r1);
 int loop_index(const Kernel& k, int reg);

@@ -11,8 +11,6 @@
 namespace eg {
 namespace model {
 
-namespace {
-
 // every dimension a single bare register, all different, each a loop register
 bool bare_regs(const Kernel& k, const Op& op, std::vector<int>& regs) {
   regs.clear();
@@ -27,13 +25,18 @@ bool bare_regs(const Kernel& k, const Op& op, std::vector<int>& regs) {
   return true;
 }
 
-// a map or a row sum over the scores: four unbounded loops, no setup, no computed indices
-bool plain_rank4(const Kernel& k) {
-  if (!k.index_instrs.empty() || !k.setup.empty() || k.loops.size() != 4) return false;
+// `loops` unbounded loops, no setup, no computed indices
+bool plain_loops(const Kernel& k, size_t loops) {
+  if (!k.index_instrs.empty() || !k.setup.empty() || k.loops.size() != loops) return false;
   for (auto& lp : k.loops)
     if (lp.has_bounds) return false;
   return true;
 }
+
+namespace {
+
+// a map or a row sum over the scores
+bool plain_rank4(const Kernel& k) { return plain_loops(k, 4); }
 
 bool fail(const char** why, const char* reason) {
   if (why) *why = reason;
@@ -42,7 +45,7 @@ bool fail(const char** why, const char* reason) {
 
 }  // namespace
 
-bool match_attention(const Program& prog, const Target& t, int p, AttentionMatch& out, const char** why) {
+bool match_attention_chain(const Target& t, int p, AttentionMatch& out, const char** why, bool gaps) {
   const int n_live = (int)t.live.size();
   if (p < 0 || p + 4 > n_live) return fail(why, "fewer than four kernels");
   AttentionMatch m;
@@ -57,9 +60,27 @@ bool match_attention(const Program& prog, const Target& t, int p, AttentionMatch
   m.t_scores = k0.write.tensor;
   m.t_q = k0.reads[m.scores.a_read].tensor;
   m.t_k = k0.reads[m.scores.b_read].tensor;
+  m.at.push_back(p);
+  const char* const ends = "the chain ends behind the target's last kernel";
+  // gaps: the next member from `from` on, over kernels that touch none of the chain's tensors
+  auto next = [&](int from) {
+    while (gaps && from < n_live) {
+      const Kernel& k = kernel(from);
+      bool touches = false;
+      for (int x : {m.t_scores, m.t_scaled, m.t_sums, m.t_softmax}) {
+        if (!x) continue;
+        touches = touches || k.write.tensor == x;
+        for (auto& rd : k.reads) touches = touches || rd.tensor == x;
+      }
+      if (touches) break;
+      ++from;
+    }
+    return from;
+  };
 
   // [1] the optional scale map: scaled = scores * literal, either order
-  int at = p + 1;
+  int at = next(p + 1);
+  if (at >= n_live) return fail(why, ends);
   int e = m.t_scores;   // what the softmax reads
   {
     const Kernel& k = kernel(at);
@@ -83,11 +104,11 @@ bool match_attention(const Program& prog, const Target& t, int p, AttentionMatch
       m.scale = (float)lit->lit;
       m.t_scaled = k.write.tensor;
       e = m.t_scaled;
-      ++at;
+      m.at.push_back(at);
+      at = next(at + 1);
     }
   }
-  m.n = at - p + 3;
-  if (p + m.n > n_live) return fail(why, "the chain ends behind the target's last kernel");
+  if (at >= n_live || (!gaps && at + 3 > n_live)) return fail(why, ends);
 
   // [n - 3] the row sum of exp over the last axis
   {
@@ -100,7 +121,9 @@ bool match_attention(const Program& prog, const Target& t, int p, AttentionMatch
       return fail(why, "the row sum is not a sum of exp alone");
     if (!bare_regs(k, k.write, w) || w.size() != 3 || w[0] != r[0] || w[1] != r[1] || w[2] != r[2]) return fail(why, "the row sum does not run over the last axis");
     m.t_sums = k.write.tensor;
-    ++at;
+    m.at.push_back(at);
+    at = next(at + 1);
+    if (at >= n_live) return fail(why, ends);
   }
 
   // [n - 2] exp(e) / sums
@@ -131,7 +154,9 @@ bool match_attention(const Program& prog, const Target& t, int p, AttentionMatch
         dv->args[1] != k.reads[rs].reg || k.result != dv->res)
       return fail(why, "the softmax is not exp / sums alone");
     m.t_softmax = k.write.tensor;
-    ++at;
+    m.at.push_back(at);
+    at = next(at + 1);
+    if (at >= n_live) return fail(why, ends);
   }
 
   // [n - 1] the context
@@ -144,24 +169,46 @@ bool match_attention(const Program& prog, const Target& t, int p, AttentionMatch
     if (m.context.row_dim[0] != 2) return fail(why, "the context product does not read the softmax in the positions of the scores");
     m.t_v = k.reads[m.context.b_read].tensor;
     m.t_out = k.write.tensor;
+    m.at.push_back(at);
   }
+  m.n = (int)m.at.size();
 
-  // the intermediates exist for the chain alone
-  for (int x : {m.t_scores, m.t_scaled, m.t_sums, m.t_softmax}) {
+  out = m;
+  return true;
+}
+
+bool attention_private(const Program& prog, const Target& t, const std::vector<int>& xs, const std::vector<int>& writers, const std::vector<int>& operands,
+                       const std::vector<int>& members, const char* read_outside, const char** why) {
+  const int n_live = (int)t.live.size();
+  std::vector<char> member((size_t)n_live, 0);
+  for (int q : members) member[(size_t)q] = 1;
+  for (size_t i = 0; i < xs.size(); ++i) {
+    const int x = xs[i];
     if (!x) continue;
     if (x < 1 || x >= (int)prog.tensors.size() || prog.tensors[x].kind != TK::Result) return fail(why, "an intermediate is not a result tensor");
     if (x == t.output) return fail(why, "an intermediate is the target's output");
-    if (x == m.t_out || x == m.t_q || x == m.t_k || x == m.t_v) return fail(why, "an intermediate is an operand of the chain");
-    int writers = 0;
+    for (int o : operands)
+      if (x == o) return fail(why, "an intermediate is an operand of the chain");
+    int n_writers = 0;
     for (int q = 0; q < n_live; ++q) {
-      const Kernel& k = kernel(q);
-      if (k.write.tensor == x) ++writers;
-      if (q >= p && q < p + m.n) continue;
+      const Kernel& k = t.all[t.live[q]];
+      if (k.write.tensor == x) ++n_writers;
+      if (member[(size_t)q]) continue;
       for (auto& rd : k.reads)
-        if (rd.tensor == x) return fail(why, "an intermediate is read outside the chain");
+        if (rd.tensor == x) return fail(why, read_outside);
     }
-    if (writers != 1) return fail(why, "an intermediate has another writer");
+    if (n_writers != writers[i]) return fail(why, "an intermediate has another writer");
   }
+  return true;
+}
+
+bool match_attention(const Program& prog, const Target& t, int p, AttentionMatch& out, const char** why) {
+  AttentionMatch m;
+  if (!match_attention_chain(t, p, m, why)) return false;
+  // the intermediates exist for the chain alone
+  if (!attention_private(prog, t, {m.t_scores, m.t_scaled, m.t_sums, m.t_softmax}, {1, 1, 1, 1}, {m.t_out, m.t_q, m.t_k, m.t_v}, m.at,
+                         "an intermediate is read outside the chain", why))
+    return false;
   out = m;
   return true;
 }

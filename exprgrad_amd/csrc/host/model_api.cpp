@@ -279,16 +279,28 @@ const char* eg_model_launch_text(eg_model* m, const char* target) {
         os << " x " << L.M << "x" << L.N << "x" << L.K
            << " -> t" << L.c_tensor << (L.accumulate ? " accumulate" : "");
         break;
-      case StepKind::Attention: {
+      case StepKind::Attention:
+      case StepKind::AttentionGrad: {
+        const bool grad = L.kind == StepKind::AttentionGrad;
+        auto tname = [&](int wt) {
+          const std::string& nm = m->prog.tensors[wt].name;
+          return nm.empty() || nm == "-" ? "t" + std::to_string(wt) : nm;
+        };
         char scale[32];
         snprintf(scale, sizeof(scale), "%g", (double)L.attn_scale);
-        os << "eg_attn " << L.batch << "x" << L.batch1 << " x " << L.M << "x" << L.N << "x" << L.K << "x" << L.attn_d << " scale=" << scale << " (";
+        os << (grad ? "eg_attn_grad " : "eg_attn ") << L.batch << "x" << L.batch1 << " x " << L.M << "x" << L.N << "x" << L.K << "x" << L.attn_d << " scale=" << scale << " (";
         for (size_t ki = 0; ki < L.attn_members.size(); ++ki) {
           const int wt = ts.target->all[ts.target->live[L.attn_members[ki]]].write.tensor;
           const std::string& nm = m->prog.tensors[wt].name;
           os << (ki ? ", " : "") << (nm.empty() || nm == "-" ? "t" + std::to_string(wt) : nm);
         }
+        if (grad) {   // reads q, kk, v, the context, the sums and the context's gradient
+          os << ") sums=" << tname(L.sums_tensor) << " -> t" << L.attn_dq.tensor << ", t" << L.attn_dk.tensor << ", t" << L.attn_dv.tensor;
+          if (L.attn_acc) os << " accumulate=" << ((L.attn_acc & 1) ? "q" : "") << ((L.attn_acc & 2) ? "k" : "") << ((L.attn_acc & 4) ? "v" : "");
+          break;
+        }
         os << ")" << (L.accumulate ? " accumulate" : "");
+        if (L.sums_tensor) os << " sums=" << tname(L.sums_tensor);
         break;
       }
       case StepKind::Conv: os << "conv2 -> t" << L.c_tensor << (L.accumulate ? " accumulate" : ""); break;
@@ -780,6 +792,17 @@ int eg_model_set_epoch(eg_model* m, int64_t epoch) try {
 EG_CATCH_ALL
 
 int64_t eg_model_epoch(eg_model* m) { return m ? m->epoch : 0; }
+
+int eg_model_fuse_attention_fit(eg_model* m, int on) try {
+  EG_REQUIRE(m, EG_ERR_INVALID, "NULL model");
+  if (m->fuse_attention_fit != (on != 0)) {
+    m->fuse_attention_fit = on != 0;
+    m->inputs_gen++;  // the plan key changes: the next run looks its plan up again
+    describe(m);      // eg_model_plan_text names the launches the setting asks for
+  }
+  return EG_OK;
+}
+EG_CATCH_ALL
 
 int eg_model_keep_values(eg_model* m, int on) try {
   EG_REQUIRE(m, EG_ERR_INVALID, "NULL model");

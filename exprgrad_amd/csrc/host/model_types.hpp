@@ -2,10 +2,11 @@
 // units:
 //   match.cpp          library patterns (contraction, bias, convolution and its gradients)
 //   match_attention.cpp  the forward attention chain (scores, scale, softmax, context)
+//   match_attention_grad.cpp  the chain with the gradient kernels derive makes of it (a training step)
 //   lower.cpp          static lowering of a target, inlining, generated sources
 //   plan.cpp           per-shape plans: launch list, overwrite / accumulate, arena   (+ plan_check.cpp)
 //   plan_groups.cpp    row / small / map fusion groups
-//   plan_attention.cpp attention groups: a forward attention chain as one launch
+//   plan_attention.cpp attention groups: a forward attention chain as one launch, a training step over it as two
 //   plan_epilogue.cpp  contraction + consumer epilogues
 //   plan_overlap.cpp   side-lane groups
 //   run.cpp            launches, HIP graphs
@@ -40,8 +41,10 @@ using eg::set_error;
 // GemmBatched: one product per leading batch index in one launch (kernels/gemm_batched.hip); with Launch::batch1 > 0 one
 // product per pair of batch indices (kernels/gemm_batched2.hip), treated alike everywhere but in the call itself
 // Attention: the forward attention chain (match_attention) as one eg_attention launch (kernels/attention_f32.hip), stand-alone
+// AttentionGrad: the chain's gradient kernels (match_attention_fit) as one eg_attention_grad call (kernels/attention_grad_f32.hip),
+// behind an Attention launch that stores the row sums too; formed only under eg_model_fuse_attention_fit
 // WideRows: a row group with one wave per sample (rowfuse.hpp); Launch::row_group indexes Plan::row_groups as for RowFused
-enum class StepKind { Gemm, Conv, ConvGradImage, ConvGradFilter, Seed, GenericA, GenericB, RowFused, SmallFused, GemmFused, SampleFused, WideRows, GemmBatched, Attention };
+enum class StepKind { Gemm, Conv, ConvGradImage, ConvGradFilter, Seed, GenericA, GenericB, RowFused, SmallFused, GemmFused, SampleFused, WideRows, GemmBatched, Attention, AttentionGrad };
 
 struct Generic {
   GenericSource src;
@@ -91,6 +94,17 @@ struct Launch {
   long attn_d = 0, ldv = 0, stride_v = 0, stride_v1 = 0;
   float attn_scale = 1.f;
   std::vector<int> attn_members;   // live positions of the fused kernels, in order
+  // Attention of a fit group: the row sums are stored too, one dense row of I floats per item (sums_tensor != 0)
+  int sums_tensor = 0;
+  long stride_s = 0, stride_s1 = 0;
+  // AttentionGrad: q, kk, v, the sums, the extents and the scale as for Attention (c_tensor is unused); the context, its
+  // gradient and the three outputs as views: leading dimension and the strides of the outer and the inner batch index
+  struct AttnView {
+    int tensor = 0;
+    long ld = 0, stride0 = 0, stride1 = 0;
+  };
+  AttnView attn_o, attn_do, attn_dq, attn_dk, attn_dv;
+  int attn_acc = 0;                // eg_attention_grad's accumulate bits: 1 dq, 2 dk, 4 dv
   bool standalone = false;   // Gemm: a collapsed batched product (Lowered::standalone): never fused, grouped or overlapped
   long cN = 0, cH = 0, cW = 0, cC = 0, cF = 0, cFH = 0, cFW = 0;
   // Seed
@@ -198,6 +212,10 @@ struct Plan {
   // (scores, scaled, sums, softmax) that live in the registers of its blocks: no arena storage
   std::map<int, Launch> attn_groups;
   std::set<int> attn_hidden;
+  // Fit groups (form_attention_fit_groups): their forward launch is an entry of attn_groups at the live position of the
+  // chain's last kernel, their backward launch stands here at the position of the first gradient kernel; the scores, the
+  // scaled scores, the softmax and the four gradients between the products are attn_hidden
+  std::map<int, Launch> attn_grad_groups;
   std::vector<int> random_tensors;   // TensorRandom tensors the live kernels read: refilled on every run
   std::map<int, long> arena_offset;  // result tensor -> float offset in the arena
   long arena_floats = 0;
@@ -293,6 +311,7 @@ struct eg_model {
   bool f64 = false;
   int esz = 1;
   bool keep_values = false;  // eg_model_keep_values: plans keep result values where they would keep predicate bits
+  bool fuse_attention_fit = false;  // eg_model_fuse_attention_fit: training steps over an attention chain run on the fused pair
   uint64_t inputs_gen = 0;  // bumped by every change of `inputs` (bind, clear, fit): caches keyed on the bindings compare it
   float grad_scale = 1.0f;
   long epoch = 0;
@@ -381,6 +400,9 @@ int form_collapsed_groups(eg_model* m, TargetState& ts, Plan& plan, const std::v
 constexpr int ATTENTION_GROUP_CODE = -2000000;  // group_of[] entry of an attention group's kernels
 int form_attention_groups(eg_model* m, TargetState& ts, Plan& plan, const std::vector<KernelInfo>& infos, const std::map<int, int>& first_writer,
                           std::vector<int>& group_of);
+// a training step over a chain as two launches (eg_model_fuse_attention_fit): called in front of form_attention_groups
+int form_attention_fit_groups(eg_model* m, TargetState& ts, Plan& plan, const std::vector<KernelInfo>& infos, const std::map<int, int>& first_writer,
+                              std::vector<int>& group_of);
 bool row_fusion_enabled();
 constexpr int SAMPLE_GROUP_CODE = -1000000;  // group_of[] entry of a sample group's kernels
 int form_sample_group(eg_model* m, TargetState& ts, Plan& plan, const std::vector<KernelInfo>& infos, const std::map<int, int>& first_writer,

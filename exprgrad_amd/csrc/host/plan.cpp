@@ -210,6 +210,7 @@ std::string shape_key(eg_model* m) {
   }
   os << "e" << (m->prog.epoch_in_setup ? m->epoch : 0);  // host values computed from epoch() are fixed per plan (kd.hpp)
   if (m->keep_values) os << "v";
+  if (m->fuse_attention_fit) os << "a";
   return os.str();
 }
 
@@ -380,8 +381,14 @@ int make_plan(eg_model* m, TargetState& ts, Plan& plan) {
   std::set<int> needs_zero;
   plan.sample_group.reset();
   if (fuse) {
+    plan.attn_groups.clear();
+    plan.attn_grad_groups.clear();
+    plan.attn_hidden.clear();
+    // a training step over an attention chain is two launches where the model asks for it (eg_model_fuse_attention_fit)
+    int rc = form_attention_fit_groups(m, ts, plan, infos, first_writer, group_of);
+    if (rc) return rc;
     // a whole forward attention chain is one launch; what it refuses goes on to the collapsed wide row groups
-    int rc = form_attention_groups(m, ts, plan, infos, first_writer, group_of);
+    rc = form_attention_groups(m, ts, plan, infos, first_writer, group_of);
     if (rc) return rc;
     // a softmax chain over collapsed leading axes is claimed first: a sample group would give it one block per sample
     rc = form_collapsed_groups(m, ts, plan, infos, first_writer, group_of);
@@ -410,6 +417,26 @@ int make_plan(eg_model* m, TargetState& ts, Plan& plan) {
         const bool overwrite = first && full_cover(ck, infos[t.live[last]], shapes.at(wt));
         L.accumulate = !overwrite;
         if (is_result && first && !overwrite) needs_zero.insert(wt);
+        plan.launches.push_back(L);
+      }
+      auto gg = plan.attn_grad_groups.find((int)p);
+      if (gg != plan.attn_grad_groups.end()) {   // first gradient kernel of a fit group: one launch for all; per output, the rule above
+        Launch L = gg->second;
+        const Launch::AttnView* outs[3] = {&L.attn_dq, &L.attn_dk, &L.attn_dv};
+        L.attn_acc = 0;
+        for (int o = 0; o < 3; ++o) {
+          const int wt = outs[o]->tensor;
+          int writer = -1;   // the member that writes this output
+          for (int pos : L.attn_members)
+            if (t.all[t.live[pos]].write.tensor == wt) writer = pos;
+          const Kernel& wk = t.all[t.live[writer]];
+          const bool is_result = m->prog.tensors[wt].kind == TK::Result;
+          const bool first = is_result && first_writer[wt] == writer;
+          const bool overwrite = first && full_cover(wk, infos[t.live[writer]], shapes.at(wt));
+          if (!overwrite) L.attn_acc |= 1 << o;
+          if (is_result && first && !overwrite) needs_zero.insert(wt);
+        }
+        L.accumulate = L.attn_acc != 0;
         plan.launches.push_back(L);
       }
       continue;

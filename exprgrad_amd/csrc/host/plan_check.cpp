@@ -76,6 +76,18 @@ void launch_io(eg_model* m, TargetState& ts, const Plan& plan, const Launch& L, 
       rd(L.b_tensor);
       rd(L.v_tensor);
       wr(L.c_tensor, L.accumulate);
+      wr(L.sums_tensor, false);   // a fit group's forward launch stores the row sums whole
+      break;
+    case StepKind::AttentionGrad:   // reads q, kk, v, the context, the sums and the context's gradient, writes dq, dk and dv
+      rd(L.a_tensor);
+      rd(L.b_tensor);
+      rd(L.v_tensor);
+      rd(L.attn_o.tensor);
+      rd(L.sums_tensor);
+      rd(L.attn_do.tensor);
+      wr(L.attn_dq.tensor, (L.attn_acc & 1) != 0);
+      wr(L.attn_dk.tensor, (L.attn_acc & 2) != 0);
+      wr(L.attn_dv.tensor, (L.attn_acc & 4) != 0);
       break;
     case StepKind::GemmFused: {
       const PlanEpilogue& pe = *plan.epilogues[L.epilogue];
@@ -194,6 +206,7 @@ int check_plan(eg_model* m, TargetState& ts, Plan& plan) {
           for (int pos : plan.sample_group->positions) mark(pos);
           break;
         case StepKind::Attention:
+        case StepKind::AttentionGrad:
           for (int pos : L.attn_members) mark(pos);
           break;
         case StepKind::GemmFused:

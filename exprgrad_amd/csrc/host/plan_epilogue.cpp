@@ -120,7 +120,7 @@ int fuse_epilogues(eg_model* m, TargetState& ts, Plan& plan, const std::vector<K
     bool found = false;
     for (; j < plan.launches.size() && j <= i + 4; ++j) {
       const Launch& X = plan.launches[j];
-      if (X.kind == StepKind::RowFused || X.kind == StepKind::WideRows || X.kind == StepKind::SmallFused || X.kind == StepKind::GemmFused || X.kind == StepKind::SampleFused || X.kind == StepKind::Attention) break;
+      if (X.kind == StepKind::RowFused || X.kind == StepKind::WideRows || X.kind == StepKind::SmallFused || X.kind == StepKind::GemmFused || X.kind == StepKind::SampleFused || X.kind == StepKind::Attention || X.kind == StepKind::AttentionGrad) break;
       const Kernel& kx = t.all[ts.lowered[X.lowered].all_index];
       bool reads_c = false;
       for (auto& rd : kx.reads)
@@ -307,7 +307,7 @@ int fold_bias_gradients(eg_model* m, TargetState& ts, Plan& plan, const std::vec
       bool legal = true;
       for (size_t j = lo + 1; j < hi && legal; ++j) {
         const Launch& X = plan.launches[j];
-        if (X.kind == StepKind::RowFused || X.kind == StepKind::WideRows || X.kind == StepKind::SmallFused || X.kind == StepKind::GemmFused || X.kind == StepKind::SampleFused || X.kind == StepKind::Attention) {
+        if (X.kind == StepKind::RowFused || X.kind == StepKind::WideRows || X.kind == StepKind::SmallFused || X.kind == StepKind::GemmFused || X.kind == StepKind::SampleFused || X.kind == StepKind::Attention || X.kind == StepKind::AttentionGrad) {
           legal = false;  // (their tensor sets are not worth analysing here: adjacent launches are the case that matters)
           break;
         }

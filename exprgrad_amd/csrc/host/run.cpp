@@ -62,10 +62,26 @@ int run_launch(eg_model* m, TargetState& ts, Plan& plan, Launch& L) {
                                      tensor_ptr(m, ts, plan, L.b_tensor), L.ldb, L.stride_b, tensor_ptr(m, ts, plan, L.c_tensor), L.ldc,
                                      L.stride_c, L.accumulate, nullptr);
     case StepKind::Attention:
+      if (L.sums_tensor)   // a fit group's forward: the row sums are stored for the backward launch
+        return eg::attention::attention_sums_f32(ctx, L.batch, L.batch1, L.M, L.N, L.K, L.attn_d, L.attn_scale, tensor_ptr(m, ts, plan, L.a_tensor),
+                                                 {L.lda, L.stride_a, L.stride_a1}, tensor_ptr(m, ts, plan, L.b_tensor), {L.ldb, L.stride_b, L.stride_b1},
+                                                 tensor_ptr(m, ts, plan, L.v_tensor), {L.ldv, L.stride_v, L.stride_v1}, tensor_ptr(m, ts, plan, L.c_tensor),
+                                                 {L.ldc, L.stride_c, L.stride_c1}, L.accumulate, tensor_ptr(m, ts, plan, L.sums_tensor),
+                                                 {0, L.stride_s, L.stride_s1});
       return eg::attention::attention_f32(ctx, L.batch, L.batch1, L.M, L.N, L.K, L.attn_d, L.attn_scale, tensor_ptr(m, ts, plan, L.a_tensor), L.lda,
                                           L.stride_a, L.stride_a1, tensor_ptr(m, ts, plan, L.b_tensor), L.ldb, L.stride_b, L.stride_b1,
                                           tensor_ptr(m, ts, plan, L.v_tensor), L.ldv, L.stride_v, L.stride_v1, tensor_ptr(m, ts, plan, L.c_tensor), L.ldc,
                                           L.stride_c, L.stride_c1, L.accumulate);
+    case StepKind::AttentionGrad: {
+      auto view = [](const Launch::AttnView& v) { return eg::attention::View{v.ld, v.stride0, v.stride1}; };
+      auto ptr = [&](const Launch::AttnView& v) { return tensor_ptr(m, ts, plan, v.tensor); };
+      return eg::attention::attention_grad_f32(ctx, L.batch, L.batch1, L.M, L.N, L.K, L.attn_d, L.attn_scale, tensor_ptr(m, ts, plan, L.a_tensor),
+                                               {L.lda, L.stride_a, L.stride_a1}, tensor_ptr(m, ts, plan, L.b_tensor), {L.ldb, L.stride_b, L.stride_b1},
+                                               tensor_ptr(m, ts, plan, L.v_tensor), {L.ldv, L.stride_v, L.stride_v1}, ptr(L.attn_o), view(L.attn_o),
+                                               tensor_ptr(m, ts, plan, L.sums_tensor), {0, L.stride_s, L.stride_s1}, ptr(L.attn_do), view(L.attn_do),
+                                               ptr(L.attn_dq), view(L.attn_dq), ptr(L.attn_dk), view(L.attn_dk), ptr(L.attn_dv), view(L.attn_dv),
+                                               L.attn_acc);
+    }
     case StepKind::GemmFused: {
       PlanEpilogue& pe = *plan.epilogues[L.epilogue];
       const float* bias = L.bias_tensor ? tensor_ptr(m, ts, plan, L.bias_tensor) : nullptr;
@@ -786,6 +802,11 @@ int plan_exchange(eg_model* m, TargetState& ts, Plan& plan, ExchangePlan& ex) {
       case StepKind::GemmFused:
         note(L.c_tensor, i);
         note(t.all[ts.lowered[plan.epilogues[L.epilogue]->consumer.lowered].all_index].write.tensor, i);
+        break;
+      case StepKind::AttentionGrad:
+        note(L.attn_dq.tensor, i);
+        note(L.attn_dk.tensor, i);
+        note(L.attn_dv.tensor, i);
         break;
       default:
         note(L.c_tensor, i);

@@ -25,6 +25,7 @@
 #include "gemm_plan.hpp"       // batched2_c_distinct
 #include "attention_plan.hpp"
 #include "attention_tile.hpp"   // TileRegs, load_rows, store_rows, wave_sync
+#include "gemm_fused.hpp"       // View, the internal entries
 
 #include <cmath>
 
@@ -294,6 +295,12 @@ int attention_f32(eg_ctx* ctx, long batch0, long batch1, long I, long J, long K,
                   float* O, long ldo, long stride_o0, long stride_o1, int accumulate) {
   return attention_launch("eg_attention", ctx, batch0, batch1, I, J, K, D, scale, Q, ldq, stride_q0, stride_q1, Kk, ldk, stride_k0, stride_k1, V,
                           ldv, stride_v0, stride_v1, O, ldo, stride_o0, stride_o1, accumulate, nullptr, 0, 0);
+}
+
+int attention_sums_f32(eg_ctx* ctx, long batch0, long batch1, long I, long J, long K, long D, float scale, const float* Q, View q, const float* Kk, View k,
+                       const float* V, View v, float* O, View o, int accumulate, float* Sums, View s) {
+  return attention_launch(Sums ? "eg_attention_sums" : "eg_attention", ctx, batch0, batch1, I, J, K, D, scale, Q, q.ld, q.stride0, q.stride1, Kk, k.ld,
+                          k.stride0, k.stride1, V, v.ld, v.stride0, v.stride1, O, o.ld, o.stride0, o.stride1, accumulate, Sums, s.stride0, s.stride1);
 }
 
 }  // namespace attention

@@ -29,6 +29,7 @@
 #include "gemm_plan.hpp"       // batched2_c_distinct
 #include "attention_plan.hpp"
 #include "attention_tile.hpp"
+#include "gemm_fused.hpp"       // View, the internal entries
 
 #include <cmath>
 
@@ -584,3 +585,17 @@ extern "C" int eg_attention_grad(eg_ctx* ctx, int64_t batch0, int64_t batch1, in
   }
   return EG_OK;
 }
+
+namespace eg {
+namespace attention {
+
+int attention_grad_f32(eg_ctx* ctx, long batch0, long batch1, long I, long J, long K, long D, float scale, const float* Q, View q, const float* Kk, View k,
+                       const float* V, View v, const float* O, View o, const float* Sums, View s, const float* dO, View dout, float* dQ, View dq,
+                       float* dK, View dk, float* dV, View dv, int accumulate) {
+  return eg_attention_grad(ctx, batch0, batch1, I, J, K, D, scale, Q, q.ld, q.stride0, q.stride1, Kk, k.ld, k.stride0, k.stride1, V, v.ld, v.stride0,
+                           v.stride1, O, o.ld, o.stride0, o.stride1, Sums, s.stride0, s.stride1, dO, dout.ld, dout.stride0, dout.stride1, dQ, dq.ld,
+                           dq.stride0, dq.stride1, dK, dk.ld, dk.stride0, dk.stride1, dV, dv.ld, dv.stride0, dv.stride1, accumulate);
+}
+
+}  // namespace attention
+}  // namespace eg

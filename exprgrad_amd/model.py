@@ -127,6 +127,12 @@ class Model:
         intermediate, as in the reference where every kernel's output is a tensor (model.nim:295-300)."""
         call("eg_model_keep_values", self.handle, 1 if on else 0)
 
+    def fuse_attention_fit(self, on=True):
+        """Training steps over an attention block run on the fused kernels: eg_attention_sums for the forward chain and
+        eg_attention_grad for the gradient kernels derived from it; scores, softmax and their gradients are never stored.
+        Off by default; part of the plan key, so turning it off returns to the plans made before."""
+        call("eg_model_fuse_attention_fit", self.handle, 1 if on else 0)
+
     def set_seed(self, seed):
         """Seed of the model's random tensors (`rand`, dropout masks); the reference uses Nim's global
         generator (`randomize(seed)`)."""

@@ -517,6 +517,21 @@ int eg_model_tensor_ptr(eg_model* model, const char* target, int tensor_id, floa
  * reference's own behaviour: every kernel's output is a tensor, model.nim:295-300); slower, for debugging and parity
  * tests.  The switch is part of the plan key: turning it back off returns to the plans made before. */
 int eg_model_keep_values(eg_model* model, int on);
+/* Training steps over an attention block on the fused kernels.  on != 0: from the next run on, a target that holds the
+ * forward chain eg_attention computes (scores, optional scale by a literal, row sums of exp, softmax, context) AND the
+ * gradient kernels the library derives from it (the softmax's gradient product, dv, three maps and a row sum between the
+ * products, dq, dk) runs them as two launches: eg_attention_sums' kernel, which stores the context and the row sums, and
+ * eg_attention_grad's pair, which writes dq, dk and dv.  The scores, the scaled scores, the softmax and the four gradients
+ * between the products are then never stored (eg_model_read_tensor refuses them as it does under the forward group).
+ * What forms: q, kk, v may be parameters or results (projections), the chain's kernels need not be neighbours.  What is
+ * refused and keeps the plan it had: everything the forward group refuses (a mask, bounded columns, a transposed operand,
+ * rank 3 or 5, a scale by a tensor or by division, K or D above 128, float64, eg_model_keep_values, EG_NO_ROWFUSE,
+ * EG_NO_BATCHED_GEMM), a missing gradient (v an input), an intermediate or one of those gradients read or written by
+ * another kernel or returned by the target, q and kk one tensor, hand-written gradients that differ from the derived ones,
+ * and a model whose gradient bucket is bound to a caller's buffer (eg_model_bind_grad_bucket) when dq, dk or dv lies in
+ * it.  A NULL model is EG_ERR_INVALID.  The setting is part of the plan key; the default is off, and with it off every
+ * plan, launch and bit is what it was. */
+int eg_model_fuse_attention_fit(eg_model* model, int on);
 
 /* Model.epoch (model.nim:39, bumped by fit at model.nim:436). */
 int eg_model_set_epoch(eg_model* model, int64_t epoch);
