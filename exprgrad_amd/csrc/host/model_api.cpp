@@ -287,20 +287,21 @@ const char* eg_model_launch_text(eg_model* m, const char* target) {
           return nm.empty() || nm == "-" ? "t" + std::to_string(wt) : nm;
         };
         char scale[32];
-        snprintf(scale, sizeof(scale), "%g", (double)L.attn_scale);
-        os << (grad ? "eg_attn_grad " : "eg_attn ") << L.batch << "x" << L.batch1 << " x " << L.M << "x" << L.N << "x" << L.K << "x" << L.attn_d << " scale=" << scale << " (";
-        for (size_t ki = 0; ki < L.attn_members.size(); ++ki) {
-          const int wt = ts.target->all[ts.target->live[L.attn_members[ki]]].write.tensor;
+        const Launch::Attn& A = L.attn;
+        snprintf(scale, sizeof(scale), "%g", (double)A.scale);
+        os << (grad ? "eg_attn_grad " : "eg_attn ") << A.e.batch0 << "x" << A.e.batch1 << " x " << A.e.I << "x" << A.e.J << "x" << A.e.K << "x" << A.e.D << " scale=" << scale << " (";
+        for (size_t ki = 0; ki < A.members.size(); ++ki) {
+          const int wt = ts.target->all[ts.target->live[A.members[ki]]].write.tensor;
           const std::string& nm = m->prog.tensors[wt].name;
           os << (ki ? ", " : "") << (nm.empty() || nm == "-" ? "t" + std::to_string(wt) : nm);
         }
         if (grad) {   // reads q, kk, v, the context, the sums and the context's gradient
-          os << ") sums=" << tname(L.sums_tensor) << " -> t" << L.attn_dq.tensor << ", t" << L.attn_dk.tensor << ", t" << L.attn_dv.tensor;
-          if (L.attn_acc) os << " accumulate=" << ((L.attn_acc & 1) ? "q" : "") << ((L.attn_acc & 2) ? "k" : "") << ((L.attn_acc & 4) ? "v" : "");
+          os << ") sums=" << tname(A.sums.tensor) << " -> t" << A.dq.tensor << ", t" << A.dk.tensor << ", t" << A.dv.tensor;
+          if (A.acc) os << " accumulate=" << ((A.acc & 1) ? "q" : "") << ((A.acc & 2) ? "k" : "") << ((A.acc & 4) ? "v" : "");
           break;
         }
         os << ")" << (L.accumulate ? " accumulate" : "");
-        if (L.sums_tensor) os << " sums=" << tname(L.sums_tensor);
+        if (A.sums.tensor) os << " sums=" << tname(A.sums.tensor);
         break;
       }
       case StepKind::Conv: os << "conv2 -> t" << L.c_tensor << (L.accumulate ? " accumulate" : ""); break;

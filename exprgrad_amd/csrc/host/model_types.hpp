@@ -7,6 +7,7 @@
 //   plan.cpp           per-shape plans: launch list, overwrite / accumulate, arena   (+ plan_check.cpp)
 //   plan_groups.cpp    row / small / map fusion groups
 //   plan_attention.cpp attention groups: a forward attention chain as one launch, a training step over it as two
+//                      (Launch::attn: extents and views as kernels/attention_plan.hpp has them; run.cpp calls kernels/attention.hpp)
 //   plan_epilogue.cpp  contraction + consumer epilogues
 //   plan_overlap.cpp   side-lane groups
 //   run.cpp            launches, HIP graphs
@@ -25,6 +26,7 @@
 
 #include "../eg_internal.hpp"
 #include "dp_schedule.hpp"
+#include "../kernels/attention_plan.hpp"
 #include "../kernels/gemm_fused.hpp"
 #include "codegen.hpp"
 #include "epilogue.hpp"
@@ -89,22 +91,24 @@ struct Launch {
   bool trans_a = false, trans_b = false;
   long batch = 0, stride_a = 0, stride_b = 0, stride_c = 0;   // GemmBatched (two batch indices: the outer index and its strides)
   long batch1 = 0, stride_a1 = 0, stride_b1 = 0, stride_c1 = 0;   //   the inner index of a product with two (batch1 > 0)
-  // Attention: a = q, b = kk, c = the context; M = I, N = J, K as it is; batch / batch1 and the strides as for GemmBatched
-  int v_tensor = 0;
-  long attn_d = 0, ldv = 0, stride_v = 0, stride_v1 = 0;
-  float attn_scale = 1.f;
-  std::vector<int> attn_members;   // live positions of the fused kernels, in order
-  // Attention of a fit group: the row sums are stored too, one dense row of I floats per item (sums_tensor != 0)
-  int sums_tensor = 0;
-  long stride_s = 0, stride_s1 = 0;
-  // AttentionGrad: q, kk, v, the sums, the extents and the scale as for Attention (c_tensor is unused); the context, its
-  // gradient and the three outputs as views: leading dimension and the strides of the outer and the inner batch index
-  struct AttnView {
-    int tensor = 0;
-    long ld = 0, stride0 = 0, stride1 = 0;
-  };
-  AttnView attn_o, attn_do, attn_dq, attn_dk, attn_dv;
-  int attn_acc = 0;                // eg_attention_grad's accumulate bits: 1 dq, 2 dk, 4 dv
+  // Attention / AttentionGrad: everything of the launch but `accumulate`.  The extents live here — M, N, K, batch and
+  // batch1 above stay 0, every reader of those asks for a gemm kind first — and each operand is a tensor and its view
+  // (kernels/attention_plan.hpp) in the launch's batch order.  None of the gemm fields is borrowed, c_tensor included: its
+  // one reader that does not ask for the kind, the default branch of the exchange plan (run.cpp, plan_exchange), has a
+  // case for each of the two kinds.
+  struct Attn {
+    struct Operand {
+      int tensor = 0;
+      eg::attention::View view;
+    };
+    eg::attention::Extents e;
+    float scale = 1.f;
+    Operand q, k, v, o;              // o: the context
+    Operand sums;                    // a fit group: the row sums, one dense row of I floats per item (tensor != 0)
+    Operand dout, dq, dk, dv;        // AttentionGrad: the context's gradient and the three outputs
+    std::vector<int> members;        // live positions of the fused kernels, in order
+    int acc = 0;                     // AttentionGrad: eg_attention_grad's accumulate bits: 1 dq, 2 dk, 4 dv
+  } attn;
   bool standalone = false;   // Gemm: a collapsed batched product (Lowered::standalone): never fused, grouped or overlapped
   long cN = 0, cH = 0, cW = 0, cC = 0, cF = 0, cFH = 0, cFW = 0;
   // Seed

@@ -409,7 +409,7 @@ int make_plan(eg_model* m, TargetState& ts, Plan& plan) {
       auto ag = plan.attn_groups.find((int)p);
       if (ag != plan.attn_groups.end()) {   // first kernel of the chain: one launch for all; accumulate as for the context product
         Launch L = ag->second;
-        const int last = L.attn_members.back();
+        const int last = L.attn.members.back();
         const Kernel& ck = t.all[t.live[last]];
         const int wt = ck.write.tensor;
         const bool is_result = m->prog.tensors[wt].kind == TK::Result;
@@ -422,21 +422,21 @@ int make_plan(eg_model* m, TargetState& ts, Plan& plan) {
       auto gg = plan.attn_grad_groups.find((int)p);
       if (gg != plan.attn_grad_groups.end()) {   // first gradient kernel of a fit group: one launch for all; per output, the rule above
         Launch L = gg->second;
-        const Launch::AttnView* outs[3] = {&L.attn_dq, &L.attn_dk, &L.attn_dv};
-        L.attn_acc = 0;
+        const int outs[3] = {L.attn.dq.tensor, L.attn.dk.tensor, L.attn.dv.tensor};
+        L.attn.acc = 0;
         for (int o = 0; o < 3; ++o) {
-          const int wt = outs[o]->tensor;
+          const int wt = outs[o];
           int writer = -1;   // the member that writes this output
-          for (int pos : L.attn_members)
+          for (int pos : L.attn.members)
             if (t.all[t.live[pos]].write.tensor == wt) writer = pos;
           const Kernel& wk = t.all[t.live[writer]];
           const bool is_result = m->prog.tensors[wt].kind == TK::Result;
           const bool first = is_result && first_writer[wt] == writer;
           const bool overwrite = first && full_cover(wk, infos[t.live[writer]], shapes.at(wt));
-          if (!overwrite) L.attn_acc |= 1 << o;
+          if (!overwrite) L.attn.acc |= 1 << o;
           if (is_result && first && !overwrite) needs_zero.insert(wt);
         }
-        L.accumulate = L.attn_acc != 0;
+        L.accumulate = L.attn.acc != 0;
         plan.launches.push_back(L);
       }
       continue;

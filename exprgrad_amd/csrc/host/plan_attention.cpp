@@ -107,41 +107,26 @@ bool plan_chain(eg_model* m, TargetState& ts, const Plan& plan, const std::vecto
   L.kind = StepKind::Attention;
   L.lowered = p;
   L.standalone = true;
-  L.a_tensor = am.t_q;
-  L.b_tensor = am.t_k;
-  L.v_tensor = am.t_v;
-  L.c_tensor = am.t_out;
-  L.batch = i4.bounds[g4.lb[outer4]].second;
-  L.batch1 = i4.bounds[g4.lb[inner4]].second;
-  if (L.batch != i0.bounds[g0.lb[outer0]].second || L.batch1 != i0.bounds[g0.lb[inner0]].second) return false;
-  L.M = L0.M;
-  L.N = L0.N;
-  L.K = L0.K;
-  L.attn_d = L4.N;
-  L.attn_scale = am.scale;
-  L.lda = L0.lda;
-  L.ldb = L0.ldb;
-  L.ldv = L4.ldb;
-  L.ldc = L4.ldc;
-  L.stride_a = stride_of(Qs, g0.batch_dim[0][outer0]);
-  L.stride_a1 = stride_of(Qs, g0.batch_dim[0][inner0]);
-  L.stride_b = stride_of(Ks, g0.batch_dim[1][outer0]);
-  L.stride_b1 = stride_of(Ks, g0.batch_dim[1][inner0]);
-  L.stride_v = stride_of(Vs, g4.batch_dim[1][outer4]);
-  L.stride_v1 = stride_of(Vs, g4.batch_dim[1][inner4]);
-  L.stride_c = stride_of(Os, g4.batch_dim[2][outer4]);
-  L.stride_c1 = stride_of(Os, g4.batch_dim[2][inner4]);
-  L.attn_members = am.at;
+  Launch::Attn& A = L.attn;
+  A.e = {i4.bounds[g4.lb[outer4]].second, i4.bounds[g4.lb[inner4]].second, L0.M, L0.N, L0.K, L4.N};
+  if (A.e.batch0 != i0.bounds[g0.lb[outer0]].second || A.e.batch1 != i0.bounds[g0.lb[inner0]].second) return false;
+  A.scale = am.scale;
+  A.q = {am.t_q, {L0.lda, stride_of(Qs, g0.batch_dim[0][outer0]), stride_of(Qs, g0.batch_dim[0][inner0])}};
+  A.k = {am.t_k, {L0.ldb, stride_of(Ks, g0.batch_dim[1][outer0]), stride_of(Ks, g0.batch_dim[1][inner0])}};
+  A.v = {am.t_v, {L4.ldb, stride_of(Vs, g4.batch_dim[1][outer4]), stride_of(Vs, g4.batch_dim[1][inner4])}};
+  A.o = {am.t_out, {L4.ldc, stride_of(Os, g4.batch_dim[2][outer4]), stride_of(Os, g4.batch_dim[2][inner4])}};
+  A.members = am.at;
   return true;
 }
 
-eg::attention::Problem problem_of(eg_model* m, const Launch& L) {
+// A view as the planner takes it: the arena's tensors start 16-byte aligned.
+eg::attention::Operand operand(const Launch::Attn::Operand& x) { return {x.view, true}; }
+
+eg::attention::Problem problem_of(eg_model* m, const Launch::Attn& A) {
   eg::attention::Problem pr;
-  pr.batch0 = L.batch, pr.batch1 = L.batch1, pr.I = L.M, pr.J = L.N, pr.K = L.K, pr.D = L.attn_d;
-  pr.q = {L.lda, L.stride_a, L.stride_a1, true};
-  pr.k = {L.ldb, L.stride_b, L.stride_b1, true};
-  pr.v = {L.ldv, L.stride_v, L.stride_v1, true};
-  pr.o = {L.ldc, L.stride_c, L.stride_c1, true};
+  static_cast<eg::attention::Extents&>(pr) = A.e;
+  pr.q = operand(A.q), pr.k = operand(A.k), pr.v = operand(A.v), pr.o = operand(A.o);
+  pr.sums = A.sums.tensor != 0;
   pr.cus = m->ctx->compute_units;
   return pr;
 }
@@ -165,7 +150,7 @@ int form_attention_groups(eg_model* m, TargetState& ts, Plan& plan, const std::v
     Launch L;
     int outer_pos = 0;
     if (!ok || !plan_chain(m, ts, plan, infos, group_of, am, L, outer_pos)) continue;
-    if (!eg::attention::plan_attention(problem_of(m, L)).supported) continue;   // K or D above 128: the unfused plan
+    if (!eg::attention::plan_attention(problem_of(m, L.attn)).supported) continue;   // K or D above 128: the unfused plan
     for (int s = p; s <= last; ++s) group_of[s] = ATTENTION_GROUP_CODE;
     for (int x : {am.t_scores, am.t_scaled, am.t_sums, am.t_softmax})
       if (x) plan.attn_hidden.insert(x);
@@ -194,6 +179,7 @@ int form_attention_fit_groups(eg_model* m, TargetState& ts, Plan& plan, const st
     Launch F;
     int outer_pos = 0;
     if (!ok || !plan_chain(m, ts, plan, infos, group_of, am, F, outer_pos)) continue;
+    const eg::attention::Extents& E = F.attn.e;
     const std::vector<long>& S = shapes.at(am.t_scores);
 
     // ---- the gradient kernels: not grouped, on one side of the boundary, behind the chain
@@ -210,11 +196,11 @@ int form_attention_fit_groups(eg_model* m, TargetState& ts, Plan& plan, const st
       int like_scores;   // the tensor of the operand that is shaped like the scores
       long M, N, K;
     };
-    const Product products[4] = {{fm.p_dsoftmax, &fm.dsoftmax, fm.t_dsoftmax, F.M, F.N, F.attn_d},
-                                 {fm.p_dv, &fm.dv, am.t_softmax, F.N, F.attn_d, F.M},
-                                 {fm.p_dq, &fm.dq, fm.t_dscores, F.M, F.K, F.N},
-                                 {fm.p_dk, &fm.dk, fm.t_dscores, F.N, F.K, F.M}};
-    std::map<int, Launch::AttnView> views;   // tensor -> its view, from the product that names it
+    const Product products[4] = {{fm.p_dsoftmax, &fm.dsoftmax, fm.t_dsoftmax, E.I, E.J, E.D},
+                                 {fm.p_dv, &fm.dv, am.t_softmax, E.J, E.D, E.I},
+                                 {fm.p_dq, &fm.dq, fm.t_dscores, E.I, E.K, E.J},
+                                 {fm.p_dk, &fm.dk, fm.t_dscores, E.J, E.K, E.I}};
+    std::map<int, eg::attention::View> views;   // tensor -> its view, from the product that names it
     for (const Product& pr : products) {
       const Kernel& k = t.all[t.live[pr.pos]];
       const KernelInfo& info = infos[t.live[pr.pos]];
@@ -229,28 +215,23 @@ int form_attention_fit_groups(eg_model* m, TargetState& ts, Plan& plan, const st
       ok = os >= 0 && g.batch_dim[os][0] <= 1 && g.batch_dim[os][1] <= 1 && g.batch_dim[os][0] != g.batch_dim[os][1];
       if (!ok) break;
       const int q_outer = g.batch_dim[os][0] == outer_pos ? 0 : 1, q_inner = 1 - q_outer;
-      ok = info.bounds[g.lb[q_outer]].second == F.batch && info.bounds[g.lb[q_inner]].second == F.batch1;
+      ok = info.bounds[g.lb[q_outer]].second == E.batch0 && info.bounds[g.lb[q_inner]].second == E.batch1;
       for (int o = 0; ok && o < 3; ++o) {
         if (o == os) continue;
         const std::vector<long>& dims = shapes.at(ops[o]->tensor);
-        Launch::AttnView v;
-        v.tensor = ops[o]->tensor;
-        v.ld = stride_of(dims, g.row_dim[o]);
-        v.stride0 = stride_of(dims, g.batch_dim[o][q_outer]);
-        v.stride1 = stride_of(dims, g.batch_dim[o][q_inner]);
-        auto seen = views.find(v.tensor);
-        if (seen != views.end()) ok = seen->second.ld == v.ld && seen->second.stride0 == v.stride0 && seen->second.stride1 == v.stride1;
-        views[v.tensor] = v;
+        const eg::attention::View v = {stride_of(dims, g.row_dim[o]), stride_of(dims, g.batch_dim[o][q_outer]), stride_of(dims, g.batch_dim[o][q_inner])};
+        auto seen = views.find(ops[o]->tensor);
+        if (seen != views.end()) ok = seen->second == v;
+        views[ops[o]->tensor] = v;
       }
     }
     if (!ok) continue;
     // q, kk and v as the gradient products see them are what the forward launch has
-    auto same = [&](int tensor, long ld, long s0, long s1) {
-      auto v = views.find(tensor);
-      return v != views.end() && v->second.ld == ld && v->second.stride0 == s0 && v->second.stride1 == s1;
+    auto same = [&](const Launch::Attn::Operand& x) {
+      auto v = views.find(x.tensor);
+      return v != views.end() && v->second == x.view;
     };
-    if (!same(am.t_q, F.lda, F.stride_a, F.stride_a1) || !same(am.t_k, F.ldb, F.stride_b, F.stride_b1) || !same(am.t_v, F.ldv, F.stride_v, F.stride_v1))
-      continue;
+    if (!same(F.attn.q) || !same(F.attn.k) || !same(F.attn.v)) continue;
     if (!views.count(fm.t_do) || !views.count(fm.t_dq) || !views.count(fm.t_dk) || !views.count(fm.t_dv)) continue;
     if (shapes.at(fm.t_do) != shapes.at(am.t_out)) continue;
 
@@ -279,28 +260,21 @@ int form_attention_fit_groups(eg_model* m, TargetState& ts, Plan& plan, const st
     if (!ok) continue;
 
     // ---- both launches
-    F.sums_tensor = am.t_sums;
-    F.stride_s = outer_pos == 0 ? S[1] * S[2] : S[2];
-    F.stride_s1 = outer_pos == 0 ? S[2] : S[1] * S[2];
-    eg::attention::Problem fp = problem_of(m, F);
-    fp.sums = true;
-    if (!eg::attention::plan_attention(fp).supported) continue;
+    F.attn.sums = {am.t_sums, outer_pos == 0 ? eg::attention::View{0, S[1] * S[2], S[2]} : eg::attention::View{0, S[2], S[1] * S[2]}};
+    if (!eg::attention::plan_attention(problem_of(m, F.attn)).supported) continue;
     Launch G = F;
     G.kind = StepKind::AttentionGrad;
     G.lowered = first;
-    G.c_tensor = 0;
-    G.attn_members = fm.backward;
-    G.attn_o = {am.t_out, F.ldc, F.stride_c, F.stride_c1};
-    G.attn_do = views[fm.t_do];
-    G.attn_dq = views[fm.t_dq];
-    G.attn_dk = views[fm.t_dk];
-    G.attn_dv = views[fm.t_dv];
+    Launch::Attn& A = G.attn;
+    A.members = fm.backward;
+    A.dout = {fm.t_do, views[fm.t_do]};
+    A.dq = {fm.t_dq, views[fm.t_dq]};
+    A.dk = {fm.t_dk, views[fm.t_dk]};
+    A.dv = {fm.t_dv, views[fm.t_dv]};
     eg::attention::GradProblem gp;
-    gp.batch0 = G.batch, gp.batch1 = G.batch1, gp.I = G.M, gp.J = G.N, gp.K = G.K, gp.D = G.attn_d;
-    auto operand = [](const Launch::AttnView& v) { return eg::attention::Operand{v.ld, v.stride0, v.stride1, true}; };
-    gp.q = fp.q, gp.k = fp.k, gp.v = fp.v, gp.o = fp.o;
-    gp.s = {0, G.stride_s, G.stride_s1, true};
-    gp.dout = operand(G.attn_do), gp.dq = operand(G.attn_dq), gp.dk = operand(G.attn_dk), gp.dv = operand(G.attn_dv);
+    static_cast<eg::attention::Extents&>(gp) = A.e;
+    gp.q = operand(A.q), gp.k = operand(A.k), gp.v = operand(A.v), gp.o = operand(A.o), gp.s = operand(A.sums);
+    gp.dout = operand(A.dout), gp.dq = operand(A.dq), gp.dk = operand(A.dk), gp.dv = operand(A.dv);
     gp.cus = m->ctx->compute_units;
     if (!eg::attention::plan_attention_grad(gp).supported) continue;
     for (int s : members) group_of[s] = ATTENTION_GROUP_CODE;

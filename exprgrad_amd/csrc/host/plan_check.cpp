@@ -72,22 +72,22 @@ void launch_io(eg_model* m, TargetState& ts, const Plan& plan, const Launch& L, 
       wr(L.ones_tensor, false);
       break;
     case StepKind::Attention:   // reads q, kk, v, writes the context; the intermediates are touched by nobody (checked below)
-      rd(L.a_tensor);
-      rd(L.b_tensor);
-      rd(L.v_tensor);
-      wr(L.c_tensor, L.accumulate);
-      wr(L.sums_tensor, false);   // a fit group's forward launch stores the row sums whole
+      rd(L.attn.q.tensor);
+      rd(L.attn.k.tensor);
+      rd(L.attn.v.tensor);
+      wr(L.attn.o.tensor, L.accumulate);
+      wr(L.attn.sums.tensor, false);   // a fit group's forward launch stores the row sums whole
       break;
     case StepKind::AttentionGrad:   // reads q, kk, v, the context, the sums and the context's gradient, writes dq, dk and dv
-      rd(L.a_tensor);
-      rd(L.b_tensor);
-      rd(L.v_tensor);
-      rd(L.attn_o.tensor);
-      rd(L.sums_tensor);
-      rd(L.attn_do.tensor);
-      wr(L.attn_dq.tensor, (L.attn_acc & 1) != 0);
-      wr(L.attn_dk.tensor, (L.attn_acc & 2) != 0);
-      wr(L.attn_dv.tensor, (L.attn_acc & 4) != 0);
+      rd(L.attn.q.tensor);
+      rd(L.attn.k.tensor);
+      rd(L.attn.v.tensor);
+      rd(L.attn.o.tensor);
+      rd(L.attn.sums.tensor);
+      rd(L.attn.dout.tensor);
+      wr(L.attn.dq.tensor, (L.attn.acc & 1) != 0);
+      wr(L.attn.dk.tensor, (L.attn.acc & 2) != 0);
+      wr(L.attn.dv.tensor, (L.attn.acc & 4) != 0);
       break;
     case StepKind::GemmFused: {
       const PlanEpilogue& pe = *plan.epilogues[L.epilogue];
@@ -207,7 +207,7 @@ int check_plan(eg_model* m, TargetState& ts, Plan& plan) {
           break;
         case StepKind::Attention:
         case StepKind::AttentionGrad:
-          for (int pos : L.attn_members) mark(pos);
+          for (int pos : L.attn.members) mark(pos);
           break;
         case StepKind::GemmFused:
           mark(L.lowered);

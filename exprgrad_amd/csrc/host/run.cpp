@@ -4,6 +4,7 @@
 #include <cstring>
 
 #include "model_types.hpp"
+#include "../kernels/attention.hpp"
 #include <random>
 
 namespace eg {
@@ -62,25 +63,15 @@ int run_launch(eg_model* m, TargetState& ts, Plan& plan, Launch& L) {
                                      tensor_ptr(m, ts, plan, L.b_tensor), L.ldb, L.stride_b, tensor_ptr(m, ts, plan, L.c_tensor), L.ldc,
                                      L.stride_c, L.accumulate, nullptr);
     case StepKind::Attention:
-      if (L.sums_tensor)   // a fit group's forward: the row sums are stored for the backward launch
-        return eg::attention::attention_sums_f32(ctx, L.batch, L.batch1, L.M, L.N, L.K, L.attn_d, L.attn_scale, tensor_ptr(m, ts, plan, L.a_tensor),
-                                                 {L.lda, L.stride_a, L.stride_a1}, tensor_ptr(m, ts, plan, L.b_tensor), {L.ldb, L.stride_b, L.stride_b1},
-                                                 tensor_ptr(m, ts, plan, L.v_tensor), {L.ldv, L.stride_v, L.stride_v1}, tensor_ptr(m, ts, plan, L.c_tensor),
-                                                 {L.ldc, L.stride_c, L.stride_c1}, L.accumulate, tensor_ptr(m, ts, plan, L.sums_tensor),
-                                                 {0, L.stride_s, L.stride_s1});
-      return eg::attention::attention_f32(ctx, L.batch, L.batch1, L.M, L.N, L.K, L.attn_d, L.attn_scale, tensor_ptr(m, ts, plan, L.a_tensor), L.lda,
-                                          L.stride_a, L.stride_a1, tensor_ptr(m, ts, plan, L.b_tensor), L.ldb, L.stride_b, L.stride_b1,
-                                          tensor_ptr(m, ts, plan, L.v_tensor), L.ldv, L.stride_v, L.stride_v1, tensor_ptr(m, ts, plan, L.c_tensor), L.ldc,
-                                          L.stride_c, L.stride_c1, L.accumulate);
     case StepKind::AttentionGrad: {
-      auto view = [](const Launch::AttnView& v) { return eg::attention::View{v.ld, v.stride0, v.stride1}; };
-      auto ptr = [&](const Launch::AttnView& v) { return tensor_ptr(m, ts, plan, v.tensor); };
-      return eg::attention::attention_grad_f32(ctx, L.batch, L.batch1, L.M, L.N, L.K, L.attn_d, L.attn_scale, tensor_ptr(m, ts, plan, L.a_tensor),
-                                               {L.lda, L.stride_a, L.stride_a1}, tensor_ptr(m, ts, plan, L.b_tensor), {L.ldb, L.stride_b, L.stride_b1},
-                                               tensor_ptr(m, ts, plan, L.v_tensor), {L.ldv, L.stride_v, L.stride_v1}, ptr(L.attn_o), view(L.attn_o),
-                                               tensor_ptr(m, ts, plan, L.sums_tensor), {0, L.stride_s, L.stride_s1}, ptr(L.attn_do), view(L.attn_do),
-                                               ptr(L.attn_dq), view(L.attn_dq), ptr(L.attn_dk), view(L.attn_dk), ptr(L.attn_dv), view(L.attn_dv),
-                                               L.attn_acc);
+      const Launch::Attn& A = L.attn;
+      auto ptr = [&](const Launch::Attn::Operand& x) -> float* { return x.tensor ? tensor_ptr(m, ts, plan, x.tensor) : nullptr; };
+      if (L.kind == StepKind::Attention)   // a fit group's forward has the row sums to store for the backward launch
+        return eg::attention::attention_forward(ctx, A.e, A.scale, ptr(A.q), A.q.view, ptr(A.k), A.k.view, ptr(A.v), A.v.view, ptr(A.o), A.o.view,
+                                                L.accumulate, ptr(A.sums), A.sums.view);
+      return eg::attention::attention_grad(ctx, A.e, A.scale, ptr(A.q), A.q.view, ptr(A.k), A.k.view, ptr(A.v), A.v.view, ptr(A.o), A.o.view,
+                                           ptr(A.sums), A.sums.view, ptr(A.dout), A.dout.view, ptr(A.dq), A.dq.view, ptr(A.dk), A.dk.view,
+                                           ptr(A.dv), A.dv.view, A.acc);
     }
     case StepKind::GemmFused: {
       PlanEpilogue& pe = *plan.epilogues[L.epilogue];
@@ -803,10 +794,11 @@ int plan_exchange(eg_model* m, TargetState& ts, Plan& plan, ExchangePlan& ex) {
         note(L.c_tensor, i);
         note(t.all[ts.lowered[plan.epilogues[L.epilogue]->consumer.lowered].all_index].write.tensor, i);
         break;
+      case StepKind::Attention: note(L.attn.o.tensor, i); break;
       case StepKind::AttentionGrad:
-        note(L.attn_dq.tensor, i);
-        note(L.attn_dk.tensor, i);
-        note(L.attn_dv.tensor, i);
+        note(L.attn.dq.tensor, i);
+        note(L.attn.dk.tensor, i);
+        note(L.attn.dv.tensor, i);
         break;
       default:
         note(L.c_tensor, i);

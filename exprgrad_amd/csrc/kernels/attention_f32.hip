@@ -21,42 +21,27 @@
 // A[row l & 15][k = l >> 4] and B[k = l >> 4][col l & 15]; it receives D[row 4 * (l >> 4) + r][col l & 15] in element r.
 // LDS row strides make every operand read and the E write conflict-free over the 64 banks: K rows of KP + 4 floats
 // (16 keys x 4 k), V rows of DP + 16 (4 keys x 16 columns), E rows of 68 (rows 4g + r: 16g + 4r + c + 16 nb).
-#include "gemm_f32_mfma.hpp"   // xcd_remap, f32x4
-#include "gemm_plan.hpp"       // batched2_c_distinct
-#include "attention_plan.hpp"
-#include "attention_tile.hpp"   // TileRegs, load_rows, store_rows, wave_sync
-#include "gemm_fused.hpp"       // View, the internal entries
+#include "gemm_plan.hpp"        // batched2_c_distinct
+#include "attention.hpp"        // the internal entry
+#include "attention_tile.hpp"   // kernel operands, tiles, the MFMA loops, the launcher
 
 #include <cmath>
-
-#include "../eg_internal.hpp"
 
 namespace {
 
 using eg::gemm::f32x4;
-using eg::gemm::xcd_remap;
 using namespace eg::attention;
 
 struct AttnArgs {
-  const float* Q;
-  const float* Kk;
-  const float* V;
-  float* O;
-  long ldq, ldk, ldv, ldo;
-  long sq0, sq1, sk0, sk1, sv0, sv1, so0, so1;   // floats per step of the outer / inner batch index
+  In q, k, v;
+  Out o;
+  Out s;   // eg_attention_sums: the row sums, I floats per item (SUMS instantiations only)
   long I, J;
   int K, D;
   float scale;
   int accumulate;
-  int vec_q, vec_k, vec_v;             // 16-byte loads of that operand (plan)
-  unsigned batch1;                     // extent of the inner index
-  unsigned first_outer, first_inner;   // the item the launch starts at: launches cut the flattened (o, i1) range
-  int tiles_i;                         // blocks per item
-  float* S;                            // eg_attention_sums: the row sums, I floats per item (SUMS instantiations only)
-  long ss0, ss1;
+  Items items;
 };
-
-constexpr int ES = TILE_J + 4;   // floats per E row
 
 // SUMS: also store each row's denominator (eg_attention_sums); a compile-time flag, so that eg_attention's kernels are the
 // ones they were.
@@ -68,18 +53,13 @@ __global__ __launch_bounds__(THREADS) void attention_f32_kernel(AttnArgs a) {
   float* const Vs = Ks + TILE_J * KS;         // [64][VS]
   float* const Es = Vs + TILE_J * VS;         // [4][16][ES]
 
-  // Block id -> (outer, inner, row tile): block-uniform 32-bit arithmetic as in gemm_batched2_kernel.
-  const int work = xcd_remap((int)blockIdx.x, (int)gridDim.x);
-  const int local = work / a.tiles_i;
-  const int tile = work - local * a.tiles_i;
-  unsigned inner = a.first_inner + (unsigned)local;
-  const unsigned outer = a.first_outer + inner / a.batch1;
-  inner %= a.batch1;
-  const long i0 = (long)tile * TILE_I;
-  const float* const Q = a.Q + (long)outer * a.sq0 + (long)inner * a.sq1 + i0 * a.ldq;
-  const float* const Kk = a.Kk + (long)outer * a.sk0 + (long)inner * a.sk1;
-  const float* const V = a.V + (long)outer * a.sv0 + (long)inner * a.sv1;
-  float* const O = a.O + (long)outer * a.so0 + (long)inner * a.so1;
+  const BlockItem b = block_item(a.items);
+  const long i0 = (long)b.tile * TILE_I;
+  const long ldq = a.q.v.ld, ldk = a.k.v.ld, ldv = a.v.v.ld;
+  const float* const Q = item_base(a.q, b.outer, b.inner) + i0 * ldq;
+  const float* const Kk = item_base(a.k, b.outer, b.inner);
+  const float* const V = item_base(a.v, b.outer, b.inner);
+  float* const O = item_base(a.o, b.outer, b.inner);
 
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, c = lane & 15, g = lane >> 4;
   float* const Ew = Es + w * 16 * ES;
@@ -88,11 +68,10 @@ __global__ __launch_bounds__(THREADS) void attention_f32_kernel(AttnArgs a) {
   float q[KP / 4];
   {
     TileRegs<KP> tq;
-    load_rows<KP>(tq, Q, a.ldq, a.I - i0, a.K, a.vec_q != 0, tid);
+    load_rows<KP>(tq, Q, ldq, a.I - i0, a.K, a.q.vec != 0, tid);
     store_rows<KP, KS>(tq, Ks, tid);
     __syncthreads();
-#pragma unroll
-    for (int kk = 0; kk < KP / 4; ++kk) q[kk] = Ks[(w * 16 + c) * KS + 4 * kk + g];
+    read_a_rows<KP, KS>(Ks, w, c, g, q);
   }
 
   f32x4 o[DP / 16];
@@ -104,8 +83,8 @@ __global__ __launch_bounds__(THREADS) void attention_f32_kernel(AttnArgs a) {
   TileRegs<DP> tv;
   const long nt = (a.J + TILE_J - 1) / TILE_J;
   if (nt > 0) {
-    load_rows<KP>(tk, Kk, a.ldk, a.J, a.K, a.vec_k != 0, tid);
-    load_rows<DP>(tv, V, a.ldv, a.J, a.D, a.vec_v != 0, tid);
+    load_rows<KP>(tk, Kk, ldk, a.J, a.K, a.k.vec != 0, tid);
+    load_rows<DP>(tv, V, ldv, a.J, a.D, a.v.vec != 0, tid);
   }
   for (long t = 0; t < nt; ++t) {
     const long j0 = t * TILE_J;
@@ -114,18 +93,14 @@ __global__ __launch_bounds__(THREADS) void attention_f32_kernel(AttnArgs a) {
     store_rows<DP, VS>(tv, Vs, tid);
     __syncthreads();
     if (t + 1 < nt) {   // in flight during this tile's MFMAs
-      load_rows<KP>(tk, Kk + (j0 + TILE_J) * a.ldk, a.ldk, a.J - j0 - TILE_J, a.K, a.vec_k != 0, tid);
-      load_rows<DP>(tv, V + (j0 + TILE_J) * a.ldv, a.ldv, a.J - j0 - TILE_J, a.D, a.vec_v != 0, tid);
+      load_rows<KP>(tk, Kk + (j0 + TILE_J) * ldk, ldk, a.J - j0 - TILE_J, a.K, a.k.vec != 0, tid);
+      load_rows<DP>(tv, V + (j0 + TILE_J) * ldv, ldv, a.J - j0 - TILE_J, a.D, a.v.vec != 0, tid);
     }
 
     f32x4 s[4];
 #pragma unroll
     for (int nb = 0; nb < 4; ++nb) s[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int kk = 0; kk < KP / 4; ++kk) {
-#pragma unroll
-      for (int nb = 0; nb < 4; ++nb) s[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(q[kk], Ks[(nb * 16 + c) * KS + 4 * kk + g], s[nb], 0, 0, 0);
-    }
+    mma_nt<KP, KS>(q, Ks, c, g, s);
 
 #pragma unroll
     for (int nb = 0; nb < 4; ++nb) {
@@ -141,12 +116,7 @@ __global__ __launch_bounds__(THREADS) void attention_f32_kernel(AttnArgs a) {
     }
     wave_sync();
 
-#pragma unroll
-    for (int jj = 0; jj < TILE_J / 4; ++jj) {
-      const float e = Ew[c * ES + 4 * jj + g];
-#pragma unroll
-      for (int nb = 0; nb < DP / 16; ++nb) o[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(e, Vs[(4 * jj + g) * VS + nb * 16 + c], o[nb], 0, 0, 0);
-    }
+    mma_nn<DP, VS, ES>(Ew, Vs, c, g, o);
     wave_sync();   // the wave's E rows are read before its next tile overwrites them
   }
 
@@ -164,7 +134,7 @@ __global__ __launch_bounds__(THREADS) void attention_f32_kernel(AttnArgs a) {
   }
   if constexpr (SUMS) {
     // the value row i is divided by, from the lane that holds column 0 of its group's rows; 0 when there are no keys
-    float* const S = a.S + (long)outer * a.ss0 + (long)inner * a.ss1;
+    float* const S = item_base(a.s, b.outer, b.inner);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const long row = i0 + w * 16 + 4 * g + r;
@@ -181,47 +151,19 @@ __global__ __launch_bounds__(THREADS) void attention_f32_kernel(AttnArgs a) {
       const int col = nb * 16 + c;
       if (col >= a.D) continue;
       const float v = empty ? 0.f : o[nb][r] / sum[r];
-      float* const p = O + row * a.ldo + col;
+      float* const p = O + row * a.o.v.ld + col;
       *p = a.accumulate ? *p + v : v;
     }
   }
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 template <int KP, int DP, bool SUMS>
-int launch_one(eg_ctx* ctx, unsigned grid, const Plan& p, const AttnArgs& args) {
-  // the attribute belongs to the device that is current (set_device has made it the context's): once per device
-  constexpr int MAX_DEVICES = 64;
-  static bool attr_set[MAX_DEVICES] = {};
-  const bool known = ctx->device >= 0 && ctx->device < MAX_DEVICES;
-  if (!known || !attr_set[ctx->device]) {
-    EG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_f32_kernel<KP, DP, SUMS>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)lds_bytes_for(KP, DP)));
-    if (known) attr_set[ctx->device] = true;
-  }
+int launch(eg_ctx* ctx, unsigned grid, const Plan& p, const AttnArgs& args) {
+  const int rc = dynamic_lds_once<&attention_f32_kernel<KP, DP, SUMS>>(ctx, {lds_bytes_for(KP, DP)});
+  if (rc) return rc;
   hipLaunchKernelGGL((attention_f32_kernel<KP, DP, SUMS>), dim3(grid), dim3(p.block), (size_t)p.lds_bytes, ctx->stream, args);
   EG_HIP_CHECK(hipGetLastError());
   return EG_OK;
-}
-
-template <int KP, bool SUMS>
-int launch_kp(eg_ctx* ctx, unsigned grid, const Plan& p, const AttnArgs& args) {
-  switch (p.dp) {
-    case 32: return launch_one<KP, 32, SUMS>(ctx, grid, p, args);
-    case 64: return launch_one<KP, 64, SUMS>(ctx, grid, p, args);
-    default: return launch_one<KP, 128, SUMS>(ctx, grid, p, args);
-  }
-}
-
-// 9 kernels: the padded K x the padded D; 9 more that store the row sums
-template <bool SUMS>
-int launch_config(eg_ctx* ctx, unsigned grid, const Plan& p, const AttnArgs& args) {
-  switch (p.kp) {
-    case 32: return launch_kp<32, SUMS>(ctx, grid, p, args);
-    case 64: return launch_kp<64, SUMS>(ctx, grid, p, args);
-    default: return launch_kp<128, SUMS>(ctx, grid, p, args);
-  }
 }
 
 }  // namespace
@@ -230,77 +172,53 @@ namespace eg {
 namespace attention {
 
 // The one launcher: eg_attention and the model layer's attention launches (host/run.cpp) come here with Sums == NULL,
-// eg_attention_sums with the row sums' view.  `name` is the entry the messages speak of.
-static int attention_launch(const char* name, eg_ctx* ctx, long batch0, long batch1, long I, long J, long K, long D, float scale, const float* Q,
-                            long ldq, long stride_q0, long stride_q1, const float* Kk, long ldk, long stride_k0, long stride_k1, const float* V,
-                            long ldv, long stride_v0, long stride_v1, float* O, long ldo, long stride_o0, long stride_o1, int accumulate, float* Sums,
-                            long stride_s0, long stride_s1) {
+// eg_attention_sums and a fit group's forward launch with the row sums' view.
+int attention_forward(eg_ctx* ctx, const Extents& e, float scale, const float* Q, View q, const float* Kk, View k, const float* V, View v, float* O,
+                      View o, int accumulate, float* Sums, View s) {
+  const char* const name = Sums ? "eg_attention_sums" : "eg_attention";   // the entry the messages speak of
+  const long batch0 = e.batch0, batch1 = e.batch1, I = e.I, J = e.J, K = e.K, D = e.D;
   EG_REQUIRE(ctx, EG_ERR_INVALID, "%s: ctx is NULL", name);
   EG_REQUIRE(batch0 >= 0 && batch1 >= 0 && I >= 0 && J >= 0 && K >= 0 && D >= 0, EG_ERR_INVALID, "%s: negative extent", name);
   EG_REQUIRE(batch0 < (1L << 31) && batch1 < (1L << 31), EG_ERR_INVALID, "%s: a batch extent of 2^31 or more", name);
-  EG_REQUIRE(stride_q0 >= 0 && stride_q1 >= 0 && stride_k0 >= 0 && stride_k1 >= 0 && stride_v0 >= 0 && stride_v1 >= 0, EG_ERR_INVALID,
+  EG_REQUIRE(q.stride0 >= 0 && q.stride1 >= 0 && k.stride0 >= 0 && k.stride1 >= 0 && v.stride0 >= 0 && v.stride1 >= 0, EG_ERR_INVALID,
              "%s: negative stride", name);
   if (batch0 == 0 || batch1 == 0 || I == 0 || (D == 0 && !Sums)) return EG_OK;
   EG_REQUIRE(D == 0 || O, EG_ERR_INVALID, "%s: O is NULL", name);
   EG_REQUIRE(J == 0 || D == 0 || V, EG_ERR_INVALID, "%s: NULL operand", name);
   EG_REQUIRE(J == 0 || K == 0 || (Q && Kk), EG_ERR_INVALID, "%s: NULL operand", name);
-  EG_REQUIRE(ldq >= K && ldk >= K && ldv >= D, EG_ERR_INVALID, "%s: leading dimension smaller than the row length", name);
-  EG_REQUIRE(D == 0 || eg::gemm::batched2_c_distinct(batch0, stride_o0, batch1, stride_o1, I, ldo, D), EG_ERR_INVALID,
+  EG_REQUIRE(q.ld >= K && k.ld >= K && v.ld >= D, EG_ERR_INVALID, "%s: leading dimension smaller than the row length", name);
+  EG_REQUIRE(D == 0 || eg::gemm::batched2_c_distinct(batch0, o.stride0, batch1, o.stride1, I, o.ld, D), EG_ERR_INVALID,
              "%s: ldo, stride_o0 and stride_o1 make elements of O share an address", name);
   // the row sums: one row of I columns per item
-  EG_REQUIRE(!Sums || eg::gemm::batched2_c_distinct(batch0, stride_s0, batch1, stride_s1, 1, I, I), EG_ERR_INVALID,
+  EG_REQUIRE(!Sums || eg::gemm::batched2_c_distinct(batch0, s.stride0, batch1, s.stride1, 1, I, I), EG_ERR_INVALID,
              "%s: stride_s0 and stride_s1 make elements of Sums share an address", name);
   EG_REQUIRE(K <= MAX_HEAD, EG_ERR_UNSUPPORTED, "%s: K = %ld is above the limit of %d", name, K, MAX_HEAD);
   EG_REQUIRE(D <= MAX_HEAD, EG_ERR_UNSUPPORTED, "%s: D = %ld is above the limit of %d", name, D, MAX_HEAD);
   if (J == 0 && accumulate && !Sums) return EG_OK;   // an empty sum adds nothing
-  int rc = eg::set_device(ctx);
+  const int rc = eg::set_device(ctx);
   if (rc) return rc;
 
   Problem pr;
-  pr.batch0 = batch0, pr.batch1 = batch1, pr.I = I, pr.J = J, pr.K = K, pr.D = D;
-  pr.q = {ldq, stride_q0, stride_q1, aligned16(Q)};
-  pr.k = {ldk, stride_k0, stride_k1, aligned16(Kk)};
-  pr.v = {ldv, stride_v0, stride_v1, aligned16(V)};
-  pr.o = {ldo, stride_o0, stride_o1, aligned16(O)};
+  static_cast<Extents&>(pr) = e;
+  pr.q = {q, aligned16(Q)}, pr.k = {k, aligned16(Kk)}, pr.v = {v, aligned16(V)}, pr.o = {o, aligned16(O)};
   pr.sums = Sums != nullptr;
   pr.cus = ctx->compute_units;
   const Plan p = plan_attention(pr);
   EG_REQUIRE(p.supported, EG_ERR_UNSUPPORTED, "%s: %s", name, p.reason);
 
-  for (long n = 0; n < p.launches; ++n) {
-    const Launch l = plan_launch(p, n);
-    EG_REQUIRE(l.items > 0 && l.grid > 0 && l.grid <= eg::gemm::BATCHED_MAX_BLOCKS, EG_ERR_INVALID, "%s: launch out of range", name);
-    AttnArgs args = {};
-    args.Q = Q, args.Kk = Kk, args.V = V, args.O = O;
-    args.ldq = ldq, args.ldk = ldk, args.ldv = ldv, args.ldo = ldo;
-    args.sq0 = stride_q0, args.sq1 = stride_q1, args.sk0 = stride_k0, args.sk1 = stride_k1;
-    args.sv0 = stride_v0, args.sv1 = stride_v1, args.so0 = stride_o0, args.so1 = stride_o1;
-    args.I = I, args.J = J, args.K = (int)K, args.D = (int)D;
-    args.scale = scale;
-    args.accumulate = accumulate;
-    args.vec_q = p.vec_q, args.vec_k = p.vec_k, args.vec_v = p.vec_v;
-    args.batch1 = (unsigned)batch1;
-    args.first_outer = (unsigned)(l.first / batch1);
-    args.first_inner = (unsigned)(l.first % batch1);
-    args.tiles_i = (int)p.tiles_i;
-    args.S = Sums, args.ss0 = stride_s0, args.ss1 = stride_s1;
-    rc = Sums ? launch_config<true>(ctx, (unsigned)l.grid, p, args) : launch_config<false>(ctx, (unsigned)l.grid, p, args);
-    if (rc) return rc;
-  }
-  return EG_OK;
-}
-
-int attention_f32(eg_ctx* ctx, long batch0, long batch1, long I, long J, long K, long D, float scale, const float* Q, long ldq, long stride_q0,
-                  long stride_q1, const float* Kk, long ldk, long stride_k0, long stride_k1, const float* V, long ldv, long stride_v0, long stride_v1,
-                  float* O, long ldo, long stride_o0, long stride_o1, int accumulate) {
-  return attention_launch("eg_attention", ctx, batch0, batch1, I, J, K, D, scale, Q, ldq, stride_q0, stride_q1, Kk, ldk, stride_k0, stride_k1, V,
-                          ldv, stride_v0, stride_v1, O, ldo, stride_o0, stride_o1, accumulate, nullptr, 0, 0);
-}
-
-int attention_sums_f32(eg_ctx* ctx, long batch0, long batch1, long I, long J, long K, long D, float scale, const float* Q, View q, const float* Kk, View k,
-                       const float* V, View v, float* O, View o, int accumulate, float* Sums, View s) {
-  return attention_launch(Sums ? "eg_attention_sums" : "eg_attention", ctx, batch0, batch1, I, J, K, D, scale, Q, q.ld, q.stride0, q.stride1, Kk, k.ld,
-                          k.stride0, k.stride1, V, v.ld, v.stride0, v.stride1, O, o.ld, o.stride0, o.stride1, accumulate, Sums, s.stride0, s.stride1);
+  AttnArgs args = {};
+  args.q = {Q, q, p.vec_q}, args.k = {Kk, k, p.vec_k}, args.v = {V, v, p.vec_v};
+  args.o = {O, o, 0}, args.s = {Sums, s, 0};
+  args.I = I, args.J = J, args.K = (int)K, args.D = (int)D;
+  args.scale = scale;
+  args.accumulate = accumulate;
+  // 9 kernels: the padded K x the padded D; 9 more that store the row sums
+  return for_each_launch(name, p.items, p.cut(), batch1, [&](const Items& items, unsigned grid) {
+    args.items = items;
+    return dispatch_heads(p.kp, p.dp, [&](auto KP, auto DP) {
+      return Sums ? launch<KP(), DP(), true>(ctx, grid, p, args) : launch<KP(), DP(), false>(ctx, grid, p, args);
+    });
+  });
 }
 
 }  // namespace attention
@@ -310,15 +228,14 @@ extern "C" int eg_attention(eg_ctx* ctx, int64_t batch0, int64_t batch1, int64_t
                             int64_t ldq, int64_t stride_q0, int64_t stride_q1, const float* Kk, int64_t ldk, int64_t stride_k0, int64_t stride_k1,
                             const float* V, int64_t ldv, int64_t stride_v0, int64_t stride_v1, float* O, int64_t ldo, int64_t stride_o0,
                             int64_t stride_o1, int accumulate) {
-  return eg::attention::attention_f32(ctx, batch0, batch1, I, J, K, D, scale, Q, ldq, stride_q0, stride_q1, Kk, ldk, stride_k0, stride_k1, V, ldv,
-                                      stride_v0, stride_v1, O, ldo, stride_o0, stride_o1, accumulate);
+  return eg::attention::attention_forward(ctx, {batch0, batch1, I, J, K, D}, scale, Q, {ldq, stride_q0, stride_q1}, Kk, {ldk, stride_k0, stride_k1}, V,
+                                          {ldv, stride_v0, stride_v1}, O, {ldo, stride_o0, stride_o1}, accumulate);
 }
 
 extern "C" int eg_attention_sums(eg_ctx* ctx, int64_t batch0, int64_t batch1, int64_t I, int64_t J, int64_t K, int64_t D, float scale, const float* Q,
                                  int64_t ldq, int64_t stride_q0, int64_t stride_q1, const float* Kk, int64_t ldk, int64_t stride_k0,
                                  int64_t stride_k1, const float* V, int64_t ldv, int64_t stride_v0, int64_t stride_v1, float* O, int64_t ldo,
                                  int64_t stride_o0, int64_t stride_o1, int accumulate, float* Sums, int64_t stride_s0, int64_t stride_s1) {
-  return eg::attention::attention_launch(Sums ? "eg_attention_sums" : "eg_attention", ctx, batch0, batch1, I, J, K, D, scale, Q, ldq, stride_q0,
-                                         stride_q1, Kk, ldk, stride_k0, stride_k1, V, ldv, stride_v0, stride_v1, O, ldo, stride_o0, stride_o1,
-                                         accumulate, Sums, stride_s0, stride_s1);
+  return eg::attention::attention_forward(ctx, {batch0, batch1, I, J, K, D}, scale, Q, {ldq, stride_q0, stride_q1}, Kk, {ldk, stride_k0, stride_k1}, V,
+                                          {ldv, stride_v0, stride_v1}, O, {ldo, stride_o0, stride_o1}, accumulate, Sums, {0, stride_s0, stride_s1});
 }

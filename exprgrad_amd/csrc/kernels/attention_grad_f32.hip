@@ -25,46 +25,28 @@
 // spread out.  A stride = 4 (mod 32), the forward's, is as good as an aligned stride gets for NT (c and c + 8 share a bank)
 // and poor for NN (rows g and g + 1 overlap in 12 of 16 banks); = 20 (mod 32) keeps NT where it was and leaves NN four
 // shared banks.  Tiles read both ways have rows of width + 20 floats, tiles read NT only of width + 4.
-#include "gemm_f32_mfma.hpp"   // xcd_remap, f32x4
-#include "gemm_plan.hpp"       // batched2_c_distinct
-#include "attention_plan.hpp"
-#include "attention_tile.hpp"
-#include "gemm_fused.hpp"       // View, the internal entries
+#include "gemm_plan.hpp"        // batched2_c_distinct
+#include "attention.hpp"        // the internal entry
+#include "attention_tile.hpp"   // kernel operands, tiles, the MFMA loops, the launcher
 
 #include <cmath>
-
-#include "../eg_internal.hpp"
 
 namespace {
 
 using eg::gemm::f32x4;
-using eg::gemm::xcd_remap;
 using namespace eg::attention;
 
 struct GradArgs {
-  const float* Q;
-  const float* Kk;
-  const float* V;
-  const float* O;
-  const float* S;
-  const float* dO;
-  float* dQ;
-  float* dK;
-  float* dV;
-  long ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv;
-  long sq0, sq1, sk0, sk1, sv0, sv1, so0, so1, ss0, ss1, sdo0, sdo1, sdq0, sdq1, sdk0, sdk1, sdv0, sdv1;
+  In q, k, v, o, s, dout;
+  Out dq, dk, dv;
   long I, J;
   int K, D;
   float scale;
   int acc_dq, acc_dk, acc_dv;          // that output is added to
   int put_dk, put_dv;                  // the dK/dV kernel stores that output
-  int vec_q, vec_k, vec_v, vec_o, vec_s, vec_do, vec_dq, vec_dk, vec_dv;
-  unsigned batch1;
-  unsigned first_outer, first_inner;   // the item the launch starts at
-  int tiles;                           // blocks per item
+  Items items;
 };
 
-constexpr int ES = 64 + 4;   // floats per row of a wave's [16][64] rows
 constexpr int TILE = 64;
 
 // A quarter of each of the tile's 64 rows of O per thread: thread tid holds columns 16 n + 4 (tid & 3) + {0, 1, 2, 3} of row
@@ -176,23 +158,6 @@ __device__ __forceinline__ void store_out(const float* __restrict__ lds, float* 
   }
 }
 
-// Block id -> (outer, inner, tile): block-uniform 32-bit arithmetic as in the forward.
-struct BlockItem {
-  unsigned outer, inner;
-  int tile;
-};
-
-__device__ __forceinline__ BlockItem block_item(const GradArgs& a) {
-  const int work = xcd_remap((int)blockIdx.x, (int)gridDim.x);
-  const int local = work / a.tiles;
-  BlockItem b;
-  b.tile = work - local * a.tiles;
-  const unsigned inner = a.first_inner + (unsigned)local;
-  b.outer = a.first_outer + inner / a.batch1;
-  b.inner = inner % a.batch1;
-  return b;
-}
-
 template <int KP, int DP>
 __global__ __launch_bounds__(THREADS) void attention_dq_kernel(GradArgs a) {
   constexpr int KS = KP + GRAD_PAD_BOTH, VS = DP + GRAD_PAD_NT;
@@ -202,17 +167,18 @@ __global__ __launch_bounds__(THREADS) void attention_dq_kernel(GradArgs a) {
   float* const Es = Vs + TILE * VS;       // [4][16][ES]
   float* const St = Es + 4 * 16 * ES;     // [64][2]: 1 / L, delta
 
-  const BlockItem b = block_item(a);
+  const BlockItem b = block_item(a.items);
   const long i0 = (long)b.tile * TILE;
   const long rows = a.I - i0;
   const long read_rows = a.J > 0 ? rows : 0;   // without keys nothing is read: dQ is zeros
-  const float* const Q = a.Q + (long)b.outer * a.sq0 + (long)b.inner * a.sq1 + i0 * a.ldq;
-  const float* const dO = a.dO + (long)b.outer * a.sdo0 + (long)b.inner * a.sdo1 + i0 * a.lddo;
-  const float* const O = a.O + (long)b.outer * a.so0 + (long)b.inner * a.so1 + i0 * a.ldo;
-  const float* const S = a.S + (long)b.outer * a.ss0 + (long)b.inner * a.ss1 + i0;
-  const float* const Kk = a.Kk + (long)b.outer * a.sk0 + (long)b.inner * a.sk1;
-  const float* const V = a.V + (long)b.outer * a.sv0 + (long)b.inner * a.sv1;
-  float* const dQ = a.dQ + (long)b.outer * a.sdq0 + (long)b.inner * a.sdq1 + i0 * a.lddq;
+  const long ldk = a.k.v.ld, ldv = a.v.v.ld;
+  const float* const Q = item_base(a.q, b.outer, b.inner) + i0 * a.q.v.ld;
+  const float* const dO = item_base(a.dout, b.outer, b.inner) + i0 * a.dout.v.ld;
+  const float* const O = item_base(a.o, b.outer, b.inner) + i0 * a.o.v.ld;
+  const float* const S = item_base(a.s, b.outer, b.inner) + i0;
+  const float* const Kk = item_base(a.k, b.outer, b.inner);
+  const float* const V = item_base(a.v, b.outer, b.inner);
+  float* const dQ = item_base(a.dq, b.outer, b.inner) + i0 * a.dq.v.ld;
 
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, c = lane & 15, g = lane >> 4;
   float* const Ew = Es + w * 16 * ES;
@@ -223,18 +189,16 @@ __global__ __launch_bounds__(THREADS) void attention_dq_kernel(GradArgs a) {
   float q[KP / 4], dout[DP / 4], inv[4], delta[4];
   {
     OPart<DP> po;
-    load_rows<KP>(tk, Q, a.ldq, read_rows, a.K, a.vec_q != 0, tid);
-    load_rows<DP>(tv, dO, a.lddo, read_rows, a.D, a.vec_do != 0, tid);
-    load_o_part<DP>(po, O, a.ldo, read_rows, a.D, a.vec_o != 0, tid);
-    const f32x4 sums = load_sums(S, read_rows, a.vec_s != 0, tid);
+    load_rows<KP>(tk, Q, a.q.v.ld, read_rows, a.K, a.q.vec != 0, tid);
+    load_rows<DP>(tv, dO, a.dout.v.ld, read_rows, a.D, a.dout.vec != 0, tid);
+    load_o_part<DP>(po, O, a.o.v.ld, read_rows, a.D, a.o.vec != 0, tid);
+    const f32x4 sums = load_sums(S, read_rows, a.s.vec != 0, tid);
     store_rows<KP, KS>(tk, Ks, tid);
     store_rows<DP, VS>(tv, Vs, tid);
     store_inverse_sums(sums, St, rows, tid);
     __syncthreads();
-#pragma unroll
-    for (int kk = 0; kk < KP / 4; ++kk) q[kk] = Ks[(w * 16 + c) * KS + 4 * kk + g];
-#pragma unroll
-    for (int dd = 0; dd < DP / 4; ++dd) dout[dd] = Vs[(w * 16 + c) * VS + 4 * dd + g];
+    read_a_rows<KP, KS>(Ks, w, c, g, q);
+    read_a_rows<DP, VS>(Vs, w, c, g, dout);
     const float d = row_delta<DP>(Vs, VS, po, tid);
     if ((tid & 3) == 0) St[2 * (tid >> 2) + 1] = d;
     __syncthreads();
@@ -251,8 +215,8 @@ __global__ __launch_bounds__(THREADS) void attention_dq_kernel(GradArgs a) {
 
   const long nt = (a.J + TILE - 1) / TILE;
   if (nt > 0) {
-    load_rows<KP>(tk, Kk, a.ldk, a.J, a.K, a.vec_k != 0, tid);
-    load_rows<DP>(tv, V, a.ldv, a.J, a.D, a.vec_v != 0, tid);
+    load_rows<KP>(tk, Kk, ldk, a.J, a.K, a.k.vec != 0, tid);
+    load_rows<DP>(tv, V, ldv, a.J, a.D, a.v.vec != 0, tid);
   }
   for (long t = 0; t < nt; ++t) {
     const long j0 = t * TILE;
@@ -261,8 +225,8 @@ __global__ __launch_bounds__(THREADS) void attention_dq_kernel(GradArgs a) {
     store_rows<DP, VS>(tv, Vs, tid);
     __syncthreads();
     if (t + 1 < nt) {   // in flight during this tile's MFMAs
-      load_rows<KP>(tk, Kk + (j0 + TILE) * a.ldk, a.ldk, a.J - j0 - TILE, a.K, a.vec_k != 0, tid);
-      load_rows<DP>(tv, V + (j0 + TILE) * a.ldv, a.ldv, a.J - j0 - TILE, a.D, a.vec_v != 0, tid);
+      load_rows<KP>(tk, Kk + (j0 + TILE) * ldk, ldk, a.J - j0 - TILE, a.K, a.k.vec != 0, tid);
+      load_rows<DP>(tv, V + (j0 + TILE) * ldv, ldv, a.J - j0 - TILE, a.D, a.v.vec != 0, tid);
     }
 
     f32x4 s[4], dp[4];
@@ -303,7 +267,7 @@ __global__ __launch_bounds__(THREADS) void attention_dq_kernel(GradArgs a) {
   __syncthreads();   // every wave is done with the K tile
   stage_acc<KP, KS>(dq, Ks, w, c, g);
   __syncthreads();
-  store_out<KP, KS>(Ks, dQ, a.lddq, rows, a.K, a.vec_dq != 0, a.acc_dq != 0, tid);
+  store_out<KP, KS>(Ks, dQ, a.dq.v.ld, rows, a.K, a.dq.vec != 0, a.acc_dq != 0, tid);
 }
 
 template <int KP, int DP>
@@ -315,18 +279,19 @@ __global__ __launch_bounds__(THREADS) void attention_dkv_kernel(GradArgs a) {
   float* const Es = Ds + TILE * DS;       // [4][16][ES]
   float* const St = Es + 4 * 16 * ES;     // [64][2]: 1 / L, delta of the query tile's rows
 
-  const BlockItem b = block_item(a);
+  const BlockItem b = block_item(a.items);
   const long j0 = (long)b.tile * TILE;
   const long keys = a.J - j0;
   const long read_keys = a.I > 0 ? keys : 0;   // without query rows nothing is read: dK and dV are zeros
-  const float* const Q = a.Q + (long)b.outer * a.sq0 + (long)b.inner * a.sq1;
-  const float* const dO = a.dO + (long)b.outer * a.sdo0 + (long)b.inner * a.sdo1;
-  const float* const O = a.O + (long)b.outer * a.so0 + (long)b.inner * a.so1;
-  const float* const S = a.S + (long)b.outer * a.ss0 + (long)b.inner * a.ss1;
-  const float* const Kk = a.Kk + (long)b.outer * a.sk0 + (long)b.inner * a.sk1 + j0 * a.ldk;
-  const float* const V = a.V + (long)b.outer * a.sv0 + (long)b.inner * a.sv1 + j0 * a.ldv;
-  float* const dK = a.dK + (long)b.outer * a.sdk0 + (long)b.inner * a.sdk1 + j0 * a.lddk;
-  float* const dV = a.dV + (long)b.outer * a.sdv0 + (long)b.inner * a.sdv1 + j0 * a.lddv;
+  const long ldq = a.q.v.ld, lddo = a.dout.v.ld, ldo = a.o.v.ld;
+  const float* const Q = item_base(a.q, b.outer, b.inner);
+  const float* const dO = item_base(a.dout, b.outer, b.inner);
+  const float* const O = item_base(a.o, b.outer, b.inner);
+  const float* const S = item_base(a.s, b.outer, b.inner);
+  const float* const Kk = item_base(a.k, b.outer, b.inner) + j0 * a.k.v.ld;
+  const float* const V = item_base(a.v, b.outer, b.inner) + j0 * a.v.v.ld;
+  float* const dK = item_base(a.dk, b.outer, b.inner) + j0 * a.dk.v.ld;
+  float* const dV = item_base(a.dv, b.outer, b.inner) + j0 * a.dv.v.ld;
 
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, c = lane & 15, g = lane >> 4;
   float* const Ew = Es + w * 16 * ES;
@@ -337,15 +302,13 @@ __global__ __launch_bounds__(THREADS) void attention_dkv_kernel(GradArgs a) {
   f32x4 sums = {1.f, 1.f, 1.f, 1.f};
   // the wave's K rows and V rows as A operands for the whole loop
   float kreg[KP / 4], vreg[DP / 4];
-  load_rows<KP>(tq, Kk, a.ldk, read_keys, a.K, a.vec_k != 0, tid);
-  load_rows<DP>(td, V, a.ldv, read_keys, a.D, a.vec_v != 0, tid);
+  load_rows<KP>(tq, Kk, a.k.v.ld, read_keys, a.K, a.k.vec != 0, tid);
+  load_rows<DP>(td, V, a.v.v.ld, read_keys, a.D, a.v.vec != 0, tid);
   store_rows<KP, QS>(tq, Qs, tid);
   store_rows<DP, DS>(td, Ds, tid);
   __syncthreads();
-#pragma unroll
-  for (int kk = 0; kk < KP / 4; ++kk) kreg[kk] = Qs[(w * 16 + c) * QS + 4 * kk + g];
-#pragma unroll
-  for (int dd = 0; dd < DP / 4; ++dd) vreg[dd] = Ds[(w * 16 + c) * DS + 4 * dd + g];
+  read_a_rows<KP, QS>(Qs, w, c, g, kreg);
+  read_a_rows<DP, DS>(Ds, w, c, g, vreg);
 
   f32x4 dk[KP / 16], dv[DP / 16];
 #pragma unroll
@@ -358,10 +321,10 @@ __global__ __launch_bounds__(THREADS) void attention_dkv_kernel(GradArgs a) {
 
   const long nt = (a.I + TILE - 1) / TILE;
   if (nt > 0) {
-    load_rows<KP>(tq, Q, a.ldq, a.I, a.K, a.vec_q != 0, tid);
-    load_rows<DP>(td, dO, a.lddo, a.I, a.D, a.vec_do != 0, tid);
-    load_o_part<DP>(po, O, a.ldo, a.I, a.D, a.vec_o != 0, tid);
-    sums = load_sums(S, a.I, a.vec_s != 0, tid);
+    load_rows<KP>(tq, Q, ldq, a.I, a.K, a.q.vec != 0, tid);
+    load_rows<DP>(td, dO, lddo, a.I, a.D, a.dout.vec != 0, tid);
+    load_o_part<DP>(po, O, ldo, a.I, a.D, a.o.vec != 0, tid);
+    sums = load_sums(S, a.I, a.s.vec != 0, tid);
   }
   for (long t = 0; t < nt; ++t) {
     const long i0 = t * TILE;
@@ -376,10 +339,10 @@ __global__ __launch_bounds__(THREADS) void attention_dkv_kernel(GradArgs a) {
     }
     if (t + 1 < nt) {   // in flight during this tile's MFMAs
       const long n0 = i0 + TILE;
-      load_rows<KP>(tq, Q + n0 * a.ldq, a.ldq, a.I - n0, a.K, a.vec_q != 0, tid);
-      load_rows<DP>(td, dO + n0 * a.lddo, a.lddo, a.I - n0, a.D, a.vec_do != 0, tid);
-      load_o_part<DP>(po, O + n0 * a.ldo, a.ldo, a.I - n0, a.D, a.vec_o != 0, tid);
-      sums = load_sums(S + n0, a.I - n0, a.vec_s != 0, tid);
+      load_rows<KP>(tq, Q + n0 * ldq, ldq, a.I - n0, a.K, a.q.vec != 0, tid);
+      load_rows<DP>(td, dO + n0 * lddo, lddo, a.I - n0, a.D, a.dout.vec != 0, tid);
+      load_o_part<DP>(po, O + n0 * ldo, ldo, a.I - n0, a.D, a.o.vec != 0, tid);
+      sums = load_sums(S + n0, a.I - n0, a.s.vec != 0, tid);
     }
     __syncthreads();   // delta of every row is in St
 
@@ -441,25 +404,15 @@ __global__ __launch_bounds__(THREADS) void attention_dkv_kernel(GradArgs a) {
   stage_acc<KP, QS>(dk, Qs, w, c, g);
   stage_acc<DP, DS>(dv, Ds, w, c, g);
   __syncthreads();
-  if (a.put_dk) store_out<KP, QS>(Qs, dK, a.lddk, keys, a.K, a.vec_dk != 0, a.acc_dk != 0, tid);
-  if (a.put_dv) store_out<DP, DS>(Ds, dV, a.lddv, keys, a.D, a.vec_dv != 0, a.acc_dv != 0, tid);
+  if (a.put_dk) store_out<KP, QS>(Qs, dK, a.dk.v.ld, keys, a.K, a.dk.vec != 0, a.acc_dk != 0, tid);
+  if (a.put_dv) store_out<DP, DS>(Ds, dV, a.dv.v.ld, keys, a.D, a.dv.vec != 0, a.acc_dv != 0, tid);
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
+// One launch of one of the two kernels; the attributes of both are set together, once per device and instantiation.
 template <int KP, int DP>
-int launch_one(eg_ctx* ctx, bool dkv, unsigned grid, const GradPlan& p, const GradArgs& args) {
-  // the attribute belongs to the device that is current (set_device has made it the context's): once per device
-  constexpr int MAX_DEVICES = 64;
-  static bool attr_set[MAX_DEVICES] = {};
-  const bool known = ctx->device >= 0 && ctx->device < MAX_DEVICES;
-  if (!known || !attr_set[ctx->device]) {
-    EG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_dq_kernel<KP, DP>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)grad_dq_lds_bytes(KP, DP)));
-    EG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_dkv_kernel<KP, DP>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)grad_dkv_lds_bytes(KP, DP)));
-    if (known) attr_set[ctx->device] = true;
-  }
+int launch(eg_ctx* ctx, bool dkv, unsigned grid, const GradPlan& p, const GradArgs& args) {
+  const int rc = dynamic_lds_once<&attention_dq_kernel<KP, DP>, &attention_dkv_kernel<KP, DP>>(ctx, {grad_dq_lds_bytes(KP, DP), grad_dkv_lds_bytes(KP, DP)});
+  if (rc) return rc;
   if (dkv)
     hipLaunchKernelGGL((attention_dkv_kernel<KP, DP>), dim3(grid), dim3(p.block), (size_t)p.dkv.lds_bytes, ctx->stream, args);
   else
@@ -468,54 +421,20 @@ int launch_one(eg_ctx* ctx, bool dkv, unsigned grid, const GradPlan& p, const Gr
   return EG_OK;
 }
 
-template <int KP>
-int launch_kp(eg_ctx* ctx, bool dkv, unsigned grid, const GradPlan& p, const GradArgs& args) {
-  switch (p.dp) {
-    case 32: return launch_one<KP, 32>(ctx, dkv, grid, p, args);
-    case 64: return launch_one<KP, 64>(ctx, dkv, grid, p, args);
-    default: return launch_one<KP, 128>(ctx, dkv, grid, p, args);
-  }
-}
-
-// 9 instantiations of each kernel: the padded K x the padded D
-int launch_config(eg_ctx* ctx, bool dkv, unsigned grid, const GradPlan& p, const GradArgs& args) {
-  switch (p.kp) {
-    case 32: return launch_kp<32>(ctx, dkv, grid, p, args);
-    case 64: return launch_kp<64>(ctx, dkv, grid, p, args);
-    default: return launch_kp<128>(ctx, dkv, grid, p, args);
-  }
-}
-
-int launch_kernel(eg_ctx* ctx, bool dkv, const GradPlan& p, const GradKernel& k, GradArgs args, long batch1) {
-  for (long n = 0; n < k.launches; ++n) {
-    const Launch l = plan_grad_launch(p, k, n);
-    EG_REQUIRE(l.items > 0 && l.grid > 0 && l.grid <= eg::gemm::BATCHED_MAX_BLOCKS, EG_ERR_INVALID, "eg_attention_grad: launch out of range");
-    args.first_outer = (unsigned)(l.first / batch1);
-    args.first_inner = (unsigned)(l.first % batch1);
-    args.tiles = (int)k.tiles;
-    const int rc = launch_config(ctx, dkv, (unsigned)l.grid, p, args);
-    if (rc) return rc;
-  }
-  return EG_OK;
-}
-
 }  // namespace
 
-extern "C" int eg_attention_grad(eg_ctx* ctx, int64_t batch0, int64_t batch1, int64_t I, int64_t J, int64_t K, int64_t D, float scale,
-                                 const float* Q, int64_t ldq, int64_t stride_q0, int64_t stride_q1,
-                                 const float* Kk, int64_t ldk, int64_t stride_k0, int64_t stride_k1,
-                                 const float* V, int64_t ldv, int64_t stride_v0, int64_t stride_v1,
-                                 const float* O, int64_t ldo, int64_t stride_o0, int64_t stride_o1,
-                                 const float* Sums, int64_t stride_s0, int64_t stride_s1,
-                                 const float* dO, int64_t lddo, int64_t stride_do0, int64_t stride_do1,
-                                 float* dQ, int64_t lddq, int64_t stride_dq0, int64_t stride_dq1,
-                                 float* dK, int64_t lddk, int64_t stride_dk0, int64_t stride_dk1,
-                                 float* dV, int64_t lddv, int64_t stride_dv0, int64_t stride_dv1, int accumulate) {
+namespace eg {
+namespace attention {
+
+int attention_grad(eg_ctx* ctx, const Extents& e, float scale, const float* Q, View q, const float* Kk, View k, const float* V, View v,
+                   const float* O, View o, const float* Sums, View s, const float* dO, View dout, float* dQ, View dq, float* dK, View dk, float* dV,
+                   View dv, int accumulate) {
+  const long batch0 = e.batch0, batch1 = e.batch1, I = e.I, J = e.J, K = e.K, D = e.D;
   EG_REQUIRE(ctx, EG_ERR_INVALID, "eg_attention_grad: ctx is NULL");
   EG_REQUIRE(batch0 >= 0 && batch1 >= 0 && I >= 0 && J >= 0 && K >= 0 && D >= 0, EG_ERR_INVALID, "eg_attention_grad: negative extent");
   EG_REQUIRE(batch0 < (1L << 31) && batch1 < (1L << 31), EG_ERR_INVALID, "eg_attention_grad: a batch extent of 2^31 or more");
-  EG_REQUIRE(stride_q0 >= 0 && stride_q1 >= 0 && stride_k0 >= 0 && stride_k1 >= 0 && stride_v0 >= 0 && stride_v1 >= 0 && stride_o0 >= 0 &&
-                 stride_o1 >= 0 && stride_s0 >= 0 && stride_s1 >= 0 && stride_do0 >= 0 && stride_do1 >= 0,
+  EG_REQUIRE(q.stride0 >= 0 && q.stride1 >= 0 && k.stride0 >= 0 && k.stride1 >= 0 && v.stride0 >= 0 && v.stride1 >= 0 && o.stride0 >= 0 &&
+                 o.stride1 >= 0 && s.stride0 >= 0 && s.stride1 >= 0 && dout.stride0 >= 0 && dout.stride1 >= 0,
              EG_ERR_INVALID, "eg_attention_grad: negative stride");
   EG_REQUIRE((accumulate & ~7) == 0, EG_ERR_INVALID, "eg_attention_grad: accumulate has bits other than 1 (dQ), 2 (dK) and 4 (dV)");
   if (batch0 == 0 || batch1 == 0) return EG_OK;
@@ -527,16 +446,16 @@ extern "C" int eg_attention_grad(eg_ctx* ctx, int64_t batch0, int64_t batch1, in
     EG_REQUIRE(K == 0 || (Q && Kk), EG_ERR_INVALID, "eg_attention_grad: NULL operand (Q or Kk)");
     EG_REQUIRE(D == 0 || (V && O && dO), EG_ERR_INVALID, "eg_attention_grad: NULL operand (V, O or dO)");
   }
-  EG_REQUIRE(ldq >= K && ldk >= K && lddq >= K && lddk >= K && ldv >= D && ldo >= D && lddo >= D && lddv >= D, EG_ERR_INVALID,
+  EG_REQUIRE(q.ld >= K && k.ld >= K && dq.ld >= K && dk.ld >= K && v.ld >= D && o.ld >= D && dout.ld >= D && dv.ld >= D, EG_ERR_INVALID,
              "eg_attention_grad: leading dimension smaller than the row length");
-  EG_REQUIRE(!want_dq || eg::gemm::batched2_c_distinct(batch0, stride_dq0, batch1, stride_dq1, I, lddq, K), EG_ERR_INVALID,
+  EG_REQUIRE(!want_dq || eg::gemm::batched2_c_distinct(batch0, dq.stride0, batch1, dq.stride1, I, dq.ld, K), EG_ERR_INVALID,
              "eg_attention_grad: lddq, stride_dq0 and stride_dq1 make elements of dQ share an address");
-  EG_REQUIRE(!want_dk || eg::gemm::batched2_c_distinct(batch0, stride_dk0, batch1, stride_dk1, J, lddk, K), EG_ERR_INVALID,
+  EG_REQUIRE(!want_dk || eg::gemm::batched2_c_distinct(batch0, dk.stride0, batch1, dk.stride1, J, dk.ld, K), EG_ERR_INVALID,
              "eg_attention_grad: lddk, stride_dk0 and stride_dk1 make elements of dK share an address");
-  EG_REQUIRE(!want_dv || eg::gemm::batched2_c_distinct(batch0, stride_dv0, batch1, stride_dv1, J, lddv, D), EG_ERR_INVALID,
+  EG_REQUIRE(!want_dv || eg::gemm::batched2_c_distinct(batch0, dv.stride0, batch1, dv.stride1, J, dv.ld, D), EG_ERR_INVALID,
              "eg_attention_grad: lddv, stride_dv0 and stride_dv1 make elements of dV share an address");
-  EG_REQUIRE(K <= MAX_HEAD, EG_ERR_UNSUPPORTED, "eg_attention_grad: K = %ld is above the limit of %d", (long)K, MAX_HEAD);
-  EG_REQUIRE(D <= MAX_HEAD, EG_ERR_UNSUPPORTED, "eg_attention_grad: D = %ld is above the limit of %d", (long)D, MAX_HEAD);
+  EG_REQUIRE(K <= MAX_HEAD, EG_ERR_UNSUPPORTED, "eg_attention_grad: K = %ld is above the limit of %d", K, MAX_HEAD);
+  EG_REQUIRE(D <= MAX_HEAD, EG_ERR_UNSUPPORTED, "eg_attention_grad: D = %ld is above the limit of %d", D, MAX_HEAD);
 
   // An output that is all zeros (an empty sum) is written as zeros when its bit is clear and left alone otherwise.
   const bool acc_dq = accumulate & 1, acc_dk = accumulate & 2, acc_dv = accumulate & 4;
@@ -548,54 +467,47 @@ extern "C" int eg_attention_grad(eg_ctx* ctx, int64_t batch0, int64_t batch1, in
   if (rc) return rc;
 
   GradProblem pr;
-  pr.batch0 = batch0, pr.batch1 = batch1, pr.I = I, pr.J = J, pr.K = K, pr.D = D;
-  pr.q = {ldq, stride_q0, stride_q1, aligned16(Q)};
-  pr.k = {ldk, stride_k0, stride_k1, aligned16(Kk)};
-  pr.v = {ldv, stride_v0, stride_v1, aligned16(V)};
-  pr.o = {ldo, stride_o0, stride_o1, aligned16(O)};
-  pr.s = {0, stride_s0, stride_s1, aligned16(Sums)};
-  pr.dout = {lddo, stride_do0, stride_do1, aligned16(dO)};
-  pr.dq = {lddq, stride_dq0, stride_dq1, aligned16(dQ)};
-  pr.dk = {lddk, stride_dk0, stride_dk1, aligned16(dK)};
-  pr.dv = {lddv, stride_dv0, stride_dv1, aligned16(dV)};
+  static_cast<Extents&>(pr) = e;
+  pr.q = {q, aligned16(Q)}, pr.k = {k, aligned16(Kk)}, pr.v = {v, aligned16(V)}, pr.o = {o, aligned16(O)}, pr.s = {s, aligned16(Sums)};
+  pr.dout = {dout, aligned16(dO)}, pr.dq = {dq, aligned16(dQ)}, pr.dk = {dk, aligned16(dK)}, pr.dv = {dv, aligned16(dV)};
   pr.cus = ctx->compute_units;
   const GradPlan p = plan_attention_grad(pr);
   EG_REQUIRE(p.supported, EG_ERR_UNSUPPORTED, "eg_attention_grad: %s", p.reason);
 
   GradArgs args = {};
-  args.Q = Q, args.Kk = Kk, args.V = V, args.O = O, args.S = Sums, args.dO = dO, args.dQ = dQ, args.dK = dK, args.dV = dV;
-  args.ldq = ldq, args.ldk = ldk, args.ldv = ldv, args.ldo = ldo, args.lddo = lddo, args.lddq = lddq, args.lddk = lddk, args.lddv = lddv;
-  args.sq0 = stride_q0, args.sq1 = stride_q1, args.sk0 = stride_k0, args.sk1 = stride_k1, args.sv0 = stride_v0, args.sv1 = stride_v1;
-  args.so0 = stride_o0, args.so1 = stride_o1, args.ss0 = stride_s0, args.ss1 = stride_s1, args.sdo0 = stride_do0, args.sdo1 = stride_do1;
-  args.sdq0 = stride_dq0, args.sdq1 = stride_dq1, args.sdk0 = stride_dk0, args.sdk1 = stride_dk1, args.sdv0 = stride_dv0, args.sdv1 = stride_dv1;
+  args.q = {Q, q, p.vec_q}, args.k = {Kk, k, p.vec_k}, args.v = {V, v, p.vec_v}, args.o = {O, o, p.vec_o}, args.s = {Sums, s, p.vec_s};
+  args.dout = {dO, dout, p.vec_do}, args.dq = {dQ, dq, p.vec_dq}, args.dk = {dK, dk, p.vec_dk}, args.dv = {dV, dv, p.vec_dv};
   args.I = I, args.J = J, args.K = (int)K, args.D = (int)D;
   args.scale = scale;
   args.acc_dq = acc_dq, args.acc_dk = acc_dk, args.acc_dv = acc_dv;
   args.put_dk = put_dk, args.put_dv = put_dv;
-  args.vec_q = p.vec_q, args.vec_k = p.vec_k, args.vec_v = p.vec_v, args.vec_o = p.vec_o, args.vec_s = p.vec_s, args.vec_do = p.vec_do;
-  args.vec_dq = p.vec_dq, args.vec_dk = p.vec_dk, args.vec_dv = p.vec_dv;
-  args.batch1 = (unsigned)batch1;
-  if (run_dq) {
-    rc = launch_kernel(ctx, false, p, p.dq, args, batch1);
-    if (rc) return rc;
-  }
-  if (put_dk || put_dv) {
-    rc = launch_kernel(ctx, true, p, p.dkv, args, batch1);
-    if (rc) return rc;
-  }
-  return EG_OK;
-}
-
-namespace eg {
-namespace attention {
-
-int attention_grad_f32(eg_ctx* ctx, long batch0, long batch1, long I, long J, long K, long D, float scale, const float* Q, View q, const float* Kk, View k,
-                       const float* V, View v, const float* O, View o, const float* Sums, View s, const float* dO, View dout, float* dQ, View dq,
-                       float* dK, View dk, float* dV, View dv, int accumulate) {
-  return eg_attention_grad(ctx, batch0, batch1, I, J, K, D, scale, Q, q.ld, q.stride0, q.stride1, Kk, k.ld, k.stride0, k.stride1, V, v.ld, v.stride0,
-                           v.stride1, O, o.ld, o.stride0, o.stride1, Sums, s.stride0, s.stride1, dO, dout.ld, dout.stride0, dout.stride1, dQ, dq.ld,
-                           dq.stride0, dq.stride1, dK, dk.ld, dk.stride0, dk.stride1, dV, dv.ld, dv.stride0, dv.stride1, accumulate);
+  // 9 instantiations of each kernel: the padded K x the padded D
+  auto run = [&](bool dkv, const GradKernel& kernel) {
+    return for_each_launch("eg_attention_grad", p.items, kernel, batch1, [&](const Items& items, unsigned grid) {
+      args.items = items;
+      return dispatch_heads(p.kp, p.dp, [&](auto KP, auto DP) { return launch<KP(), DP()>(ctx, dkv, grid, p, args); });
+    });
+  };
+  if (run_dq) rc = run(false, p.dq);
+  if (!rc && (put_dk || put_dv)) rc = run(true, p.dkv);
+  return rc;
 }
 
 }  // namespace attention
 }  // namespace eg
+
+extern "C" int eg_attention_grad(eg_ctx* ctx, int64_t batch0, int64_t batch1, int64_t I, int64_t J, int64_t K, int64_t D, float scale,
+                                 const float* Q, int64_t ldq, int64_t stride_q0, int64_t stride_q1,
+                                 const float* Kk, int64_t ldk, int64_t stride_k0, int64_t stride_k1,
+                                 const float* V, int64_t ldv, int64_t stride_v0, int64_t stride_v1,
+                                 const float* O, int64_t ldo, int64_t stride_o0, int64_t stride_o1,
+                                 const float* Sums, int64_t stride_s0, int64_t stride_s1,
+                                 const float* dO, int64_t lddo, int64_t stride_do0, int64_t stride_do1,
+                                 float* dQ, int64_t lddq, int64_t stride_dq0, int64_t stride_dq1,
+                                 float* dK, int64_t lddk, int64_t stride_dk0, int64_t stride_dk1,
+                                 float* dV, int64_t lddv, int64_t stride_dv0, int64_t stride_dv1, int accumulate) {
+  return eg::attention::attention_grad(ctx, {batch0, batch1, I, J, K, D}, scale, Q, {ldq, stride_q0, stride_q1}, Kk, {ldk, stride_k0, stride_k1}, V,
+                                       {ldv, stride_v0, stride_v1}, O, {ldo, stride_o0, stride_o1}, Sums, {0, stride_s0, stride_s1}, dO,
+                                       {lddo, stride_do0, stride_do1}, dQ, {lddq, stride_dq0, stride_dq1}, dK, {lddk, stride_dk0, stride_dk1}, dV,
+                                       {lddv, stride_dv0, stride_dv1}, accumulate);
+}

@@ -7,6 +7,23 @@
 namespace eg {
 namespace attention {
 
+Cut cut_items(long items, long tiles) {
+  Cut c;
+  c.tiles = tiles;
+  c.grid = items * tiles;
+  c.items_per_launch = std::max(1L, eg::gemm::BATCHED_MAX_BLOCKS / std::max(1L, tiles));
+  c.launches = tiles > 0 ? (items + c.items_per_launch - 1) / c.items_per_launch : 0;
+  return c;
+}
+
+Launch plan_launch(long items, const Cut& cut, long index) {
+  Launch l;
+  l.first = index * cut.items_per_launch;
+  l.items = std::min(cut.items_per_launch, items - l.first);
+  l.grid = l.items * cut.tiles;
+  return l;
+}
+
 Plan plan_attention(const Problem& p) {
   Plan r;
   if (p.batch0 < 1 || p.batch1 < 1 || p.I < 1 || p.J < 0 || p.K < 0 || p.D < (p.sums ? 0 : 1)) {
@@ -28,8 +45,8 @@ Plan plan_attention(const Problem& p) {
     r.reason = "the tiles exceed the LDS of a CU";
     return r;
   }
-  r.tiles_i = (p.I + TILE_I - 1) / TILE_I;
-  if (r.tiles_i > eg::gemm::BATCHED_MAX_BLOCKS) {
+  const long tiles_i = (p.I + TILE_I - 1) / TILE_I;
+  if (tiles_i > eg::gemm::BATCHED_MAX_BLOCKS) {
     r.reason = "an item has more row tiles than one launch has blocks";
     return r;
   }
@@ -37,26 +54,10 @@ Plan plan_attention(const Problem& p) {
   r.vec_k = operand_vec16(p.k);
   r.vec_v = operand_vec16(p.v);
   r.items = p.batch0 * p.batch1;
-  r.grid = r.items * r.tiles_i;
-  r.items_per_launch = std::max(1L, eg::gemm::BATCHED_MAX_BLOCKS / r.tiles_i);
-  r.launches = (r.items + r.items_per_launch - 1) / r.items_per_launch;
+  const Cut c = cut_items(r.items, tiles_i);
+  r.tiles_i = c.tiles, r.grid = c.grid, r.items_per_launch = c.items_per_launch, r.launches = c.launches;
   r.supported = true;
   return r;
-}
-
-Launch plan_launch(const Plan& plan, long index) {
-  Launch l;
-  l.first = index * plan.items_per_launch;
-  l.items = std::min(plan.items_per_launch, plan.items - l.first);
-  l.grid = l.items * plan.tiles_i;
-  return l;
-}
-
-static void cut(GradKernel& k, long items, long tiles) {
-  k.tiles = tiles;
-  k.grid = items * tiles;
-  k.items_per_launch = std::max(1L, eg::gemm::BATCHED_MAX_BLOCKS / std::max(1L, tiles));
-  k.launches = tiles > 0 ? (items + k.items_per_launch - 1) / k.items_per_launch : 0;
 }
 
 // Empty I, J, K and D are plans too (a kernel with no tiles has no launches; the entry decides what an empty extent
@@ -92,18 +93,10 @@ GradPlan plan_attention_grad(const GradProblem& p) {
   r.vec_s = operand_vec16(p.s), r.vec_do = operand_vec16(p.dout);
   r.vec_dq = operand_vec16(p.dq), r.vec_dk = operand_vec16(p.dk), r.vec_dv = operand_vec16(p.dv);
   r.items = p.batch0 * p.batch1;
-  cut(r.dq, r.items, tiles_i);
-  cut(r.dkv, r.items, tiles_j);
+  static_cast<Cut&>(r.dq) = cut_items(r.items, tiles_i);
+  static_cast<Cut&>(r.dkv) = cut_items(r.items, tiles_j);
   r.supported = true;
   return r;
-}
-
-Launch plan_grad_launch(const GradPlan& plan, const GradKernel& kernel, long index) {
-  Launch l;
-  l.first = index * kernel.items_per_launch;
-  l.items = std::min(kernel.items_per_launch, plan.items - l.first);
-  l.grid = l.items * kernel.tiles;
-  return l;
 }
 
 }  // namespace attention

@@ -15,23 +15,45 @@ constexpr int MAX_HEAD = 128;  // K and D
 constexpr int THREADS = 256;
 constexpr long LDS_LIMIT = 160 * 1024;   // per CU on gfx950
 
-// One operand: floats per row step and per step of the two batch indices, and whether item (0, 0) starts 16-byte aligned.
-struct Operand {
+// One item's view of an operand, the one description from the model's plan to the kernels' arguments: floats per row step
+// and per step of the outer and the inner batch index.  The row sums have no rows to step over: their ld is unused (0).
+struct View {
   long ld = 0, stride0 = 0, stride1 = 0;
+};
+inline bool operator==(const View& a, const View& b) { return a.ld == b.ld && a.stride0 == b.stride0 && a.stride1 == b.stride1; }
+
+// batch0 x batch1 items of I query rows and J keys, K the length of a query or key row, D of a value row
+struct Extents {
+  long batch0 = 0, batch1 = 0, I = 0, J = 0, K = 0, D = 0;
+};
+
+// The planner's operand: a view, and whether item (0, 0) starts 16-byte aligned.
+struct Operand : View {
   bool aligned = true;
 };
 
-struct Problem {
-  long batch0 = 0, batch1 = 0, I = 0, J = 0, K = 0, D = 0;
+struct Problem : Extents {
   Operand q, k, v, o;
   bool sums = false;   // eg_attention_sums: the row sums are stored too, and D == 0 still has them to store
   int cus = 256;
 };
 
-// Items [first, first + items) of the flattened (o, i1) range, o-major, as grid = items * tiles_i blocks.
+// How the flattened (o, i1) range of items, o-major, is cut into launches of one kernel with `tiles` blocks per item.
+struct Cut {
+  long tiles = 0;             // blocks per item
+  long grid = 0;              // blocks of all launches together: items * tiles
+  long items_per_launch = 0;  // at least 1; BATCHED_MAX_BLOCKS / tiles otherwise
+  long launches = 0;          // none for a kernel without tiles
+};
+Cut cut_items(long items, long tiles);
+
+// Items [first, first + items) of that range as grid = items * tiles blocks.
 struct Launch {
   long first = 0, items = 0, grid = 0;
 };
+
+// Launch `index` of a cut of `items` items, index in [0, cut.launches).
+Launch plan_launch(long items, const Cut& cut, long index);
 
 struct Plan {
   bool supported = false;
@@ -39,13 +61,12 @@ struct Plan {
   int tile_i = TILE_I, tile_j = TILE_J;
   int kp = 0, dp = 0;        // K and D as the kernel is instantiated: 32, 64 or 128, the rest zero-filled
   bool vec_q = false, vec_k = false, vec_v = false;   // 16-byte loads of that operand
-  long tiles_i = 0;          // blocks per item
+  long tiles_i = 0;          // blocks per item: ceil(I / 64)
   long items = 0;            // batch0 * batch1
-  long grid = 0;             // blocks of all launches together: items * tiles_i
-  long items_per_launch = 0; // at least 1; BATCHED_MAX_BLOCKS / tiles_i otherwise
-  long launches = 0;
+  long grid = 0, items_per_launch = 0, launches = 0;   // with tiles_i, the plan's Cut
   int block = THREADS;
   long lds_bytes = 0;
+  Cut cut() const { return {tiles_i, grid, items_per_launch, launches}; }
 };
 
 // 16-byte loads of an operand: the pointer of item (0, 0) 16-byte aligned, the leading dimension and both strides multiples
@@ -61,23 +82,20 @@ inline int padded_head(long n) { return n <= 32 ? 32 : n <= 64 ? 64 : 128; }
 inline long lds_bytes_for(int kp, int dp) { return 4L * (TILE_J * (kp + 4) + TILE_J * (dp + 16) + 4 * 16 * (TILE_J + 4)); }
 
 Plan plan_attention(const Problem& p);
-
-// Launch `index` of a plan, index in [0, plan.launches).
-Launch plan_launch(const Plan& plan, long index);
+// Launch `index` of a plan, index in [0, plan.launches): the cut's, for a caller that holds the plan.
+inline Launch plan_launch(const Plan& plan, long index) { return plan_launch(plan.items, plan.cut(), index); }
 
 // ---- The backward pass (attention_grad_f32.hip): two kernels, one over tiles of 64 query rows (dQ), one over tiles of 64
 // keys (dK and dV).  Both keep the block's own rows in registers and walk the other axis in tiles of 64.
-struct GradProblem {
-  long batch0 = 0, batch1 = 0, I = 0, J = 0, K = 0, D = 0;
-  Operand q, k, v, o, s, dout, dq, dk, dv;   // s: the row sums, ld unused (0)
+struct GradProblem : Extents {
+  Operand q, k, v, o, s, dout, dq, dk, dv;   // s: the row sums
   int cus = 256;
 };
 
-// One of the two kernels: `tiles` blocks per item, cut along the flattened item range like the forward.
-struct GradKernel {
+// One of the two kernels, cut along the flattened item range like the forward.
+struct GradKernel : Cut {
   int tile = 64;             // rows of the block's own axis
   int step = 64;             // rows of one pass of its loop over the other axis
-  long tiles = 0, grid = 0, items_per_launch = 0, launches = 0;
   long lds_bytes = 0;
 };
 
@@ -103,9 +121,8 @@ inline long grad_dq_lds_bytes(int kp, int dp) { return 4L * (64 * (kp + GRAD_PAD
 inline long grad_dkv_lds_bytes(int kp, int dp) { return 4L * (64 * (kp + GRAD_PAD_BOTH) + 64 * (dp + GRAD_PAD_BOTH) + 4 * 16 * 68 + 2 * 64); }
 
 GradPlan plan_attention_grad(const GradProblem& p);
-
-// Launch `index` of one of a plan's kernels, index in [0, kernel.launches).
-Launch plan_grad_launch(const GradPlan& plan, const GradKernel& kernel, long index);
+// Launch `index` of one of a plan's kernels, index in [0, kernel.launches): the cut's again.
+inline Launch plan_grad_launch(const GradPlan& plan, const GradKernel& kernel, long index) { return plan_launch(plan.items, kernel, index); }
 
 }  // namespace attention
 }  // namespace eg

@@ -69,26 +69,6 @@ int sgemm_batched(eg_ctx* ctx, int trans_a, int trans_b, long batch, long M, lon
 int sgemm_batched2(eg_ctx* ctx, int trans_a, int trans_b, long batch0, long batch1, long M, long N, long K, const float* A, long lda,
                    long stride_a0, long stride_a1, const float* B, long ldb, long stride_b0, long stride_b1, float* C, long ldc, long stride_c0,
                    long stride_c1, int accumulate, const float* bias);
-}  // namespace gemm
-namespace attention {
-// The fused attention forward over batch0 x batch1 items (attention_f32.hip): what eg_attention and the model layer's
-// attention launches run.
-int attention_f32(eg_ctx* ctx, long batch0, long batch1, long I, long J, long K, long D, float scale, const float* Q, long ldq, long stride_q0,
-                  long stride_q1, const float* Kk, long ldk, long stride_k0, long stride_k1, const float* V, long ldv, long stride_v0, long stride_v1,
-                  float* O, long ldo, long stride_o0, long stride_o1, int accumulate);
-// The same launch storing the row sums too (what eg_attention_sums runs), and the backward over what it left
-// (attention_grad_f32.hip, what eg_attention_grad runs): the model layer's fit route (host/plan_attention.cpp, form_attention_fit_groups).  One
-// item's view as (leading dimension, stride of batch0, stride of batch1); the sums have no leading dimension.
-struct View {
-  long ld = 0, stride0 = 0, stride1 = 0;
-};
-int attention_sums_f32(eg_ctx* ctx, long batch0, long batch1, long I, long J, long K, long D, float scale, const float* Q, View q, const float* Kk, View k,
-                       const float* V, View v, float* O, View o, int accumulate, float* Sums, View s);
-int attention_grad_f32(eg_ctx* ctx, long batch0, long batch1, long I, long J, long K, long D, float scale, const float* Q, View q, const float* Kk, View k,
-                       const float* V, View v, const float* O, View o, const float* Sums, View s, const float* dO, View dout, float* dQ, View dq,
-                       float* dK, View dk, float* dV, View dv, int accumulate);
-}  // namespace attention
-namespace gemm {
 // The float64 twins (gemm_f64_mfma.hip): the plain product behind eg_dgemm, and `batch` of them in one launch — what
 // eg_dgemm_batched and a float64 model's batched launches run.  Strides and leading dimensions in doubles.
 int dgemm(eg_ctx* ctx, int trans_a, int trans_b, long M, long N, long K, const double* A, long lda, const double* B, long ldb, double* C,
