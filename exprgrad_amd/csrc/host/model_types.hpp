@@ -10,7 +10,7 @@
 //                      (Launch::attn: extents and views as kernels/attention_plan.hpp has them; run.cpp calls kernels/attention.hpp)
 //   plan_epilogue.cpp  contraction + consumer epilogues
 //   plan_overlap.cpp   side-lane groups
-//   run.cpp            launches, HIP graphs
+//   run.cpp            one launch (whole or a half batch), ranges of launches, HIP graphs, batch pipeline, exchange plan
 //   fit.cpp            eg_model_fit
 //   serialize.cpp      eg_model_save / eg_model_load (io/serialize.nim layout)
 //   model_api.cpp      the remaining extern "C" entry points
@@ -249,7 +249,6 @@ struct Plan {
     // (row_finalize) is the side lane's first launch instead of the row kernel's tail on the main lane (-1: none)
     int deferred_row = -1;
   };
-  int defer_finalize_of = -1;   // set while a launch sequence is being issued: the row group whose fold the next fork runs
   std::vector<Overlap> overlaps;
   // Batch pipeline: the backward range [0, n_backward) runs as two half batches, the long contractions
   // of both halves back to back on the main lane, everything between them on the side lane — the
@@ -270,7 +269,6 @@ struct Plan {
     long epoch = 0;
   };
   Captured graphs[6];  // 0 whole call, 1 backward part, 2 update part; data-parallel split: 3 head, 4 side lane, 5 tail
-  int active_begin = 0, active_end = 0;  // the launch range being issued (run_range_eager): decides MODE of a row group with a tail
   long epoch = 0;      // Model.epoch the plan was made under (part of the key when the program has epoch_in_setup)
 };
 
@@ -366,6 +364,16 @@ inline long prod(const std::vector<long>& s) {
 
 inline long align4(long n) { return (n + 3) & ~3L; }
 
+// the tensor whose storage a tensor lives in (Plan::alias; check_plan refuses chains that do not end)
+inline int root_tensor(const Plan& plan, int tid) {
+  for (int guard = 0; guard < 64; ++guard) {
+    auto a = plan.alias.find(tid);
+    if (a == plan.alias.end()) break;
+    tid = a->second;
+  }
+  return tid;
+}
+
 // floats of arena storage a result tensor occupies in this plan
 inline long storage_floats(const Plan& plan, int tid) {
   const long n = prod(plan.shapes.at(tid));
@@ -412,9 +420,10 @@ constexpr int SAMPLE_GROUP_CODE = -1000000;  // group_of[] entry of a sample gro
 int form_sample_group(eg_model* m, TargetState& ts, Plan& plan, const std::vector<KernelInfo>& infos, const std::map<int, int>& first_writer,
                       std::vector<int>& group_of, std::set<int>& needs_zero);
 int fuse_row_tails(eg_model* m, TargetState& ts, Plan& plan, const std::vector<KernelInfo>& infos);
-bool row_tail_active(const Plan& plan, const Launch& row_launch);
+// (is the tail / the folding map group of this launch part of the range [begin, end) being issued?)
+bool row_tail_active(const Launch& row_launch, int begin, int end);
 int fuse_slab_fold(eg_model* m, TargetState& ts, Plan& plan, const std::vector<KernelInfo>& infos);
-bool slab_fold_active(const Plan& plan, const Launch& sample_launch);
+bool slab_fold_active(const Launch& sample_launch, int begin, int end);
 // plan_overlap.cpp
 int ensure_side_lane(eg_ctx* ctx);
 bool launch_tensors(const Plan& plan, const Launch& L, std::set<int>& reads, std::set<int>& writes);
@@ -435,7 +444,6 @@ int make_plan(eg_model* m, TargetState& ts, Plan& plan);
 int get_plan(eg_model* m, const char* target, TargetState** ts_out, Plan** plan_out);
 // run.cpp
 int ensure_rng(eg_model* m, uint64_t seed = 0x5eed5eed5eed5eedULL, bool reseed = false);
-int run_launch(eg_model* m, TargetState& ts, Plan& plan, Launch& L);
 // hook: called on the side lane of the overlap group whose contraction is launch `big`, after the group's
 // side launches and before the join (the data-parallel exchange of the gradients that are complete by then)
 struct SideHook {
@@ -463,13 +471,6 @@ int fold_bias_gradients(eg_model* m, TargetState& ts, Plan& plan, const std::vec
 int fold_row_products(eg_model* m, TargetState& ts, Plan& plan);
 // plan_pipeline.cpp
 void plan_pipeline(eg_model* m, TargetState& ts, Plan& plan);
-// One half of a sliced launch: rows [row0, row0 + rows) of the batch; second = the later half (reductions accumulate).
-struct Slice {
-  long row0 = 0, rows = 0;
-  bool second = false;
-};
-int run_launch_sliced(eg_model* m, TargetState& ts, Plan& plan, Launch& L, const Slice& sl);
-int run_pipelined(eg_model* m, TargetState& ts, Plan& plan, const SideHook* hook);
 // plan_check.cpp: invariants of a finished plan (read / write sets against the kernel list, arena
 // layout, overlap groups).  Returns EG_OK or EG_ERR_RUNTIME with the violated invariant named.
 int check_plan(eg_model* m, TargetState& ts, Plan& plan);

@@ -44,7 +44,7 @@ int build_plan_kernels(eg_model* m, Plan& plan) {
 }
 
 float* tensor_ptr(eg_model* m, TargetState& ts, Plan& plan, int tid) {
-  for (auto al = plan.alias.find(tid); al != plan.alias.end(); al = plan.alias.find(tid)) tid = al->second;
+  tid = root_tensor(plan, tid);
   const TensorDef& d = m->prog.tensors[tid];
   if (d.kind == TK::Param || d.kind == TK::Cache) return m->params[tid].ptr;
   if (d.kind == TK::Input) {

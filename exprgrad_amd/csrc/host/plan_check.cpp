@@ -31,18 +31,9 @@ struct IO {
   std::set<int> needs_prior;   // subset of writes that are accumulated into / partially written
 };
 
-int root(const Plan& plan, int t) {
-  for (int guard = 0; guard < 64; ++guard) {
-    auto a = plan.alias.find(t);
-    if (a == plan.alias.end()) break;
-    t = a->second;
-  }
-  return t;
-}
-
 void kernel_io(const Plan& plan, const Kernel& k, bool accumulate, IO& io) {
-  for (auto& rd : k.reads) io.reads.insert(root(plan, rd.tensor));
-  const int w = root(plan, k.write.tensor);
+  for (auto& rd : k.reads) io.reads.insert(root_tensor(plan, rd.tensor));
+  const int w = root_tensor(plan, k.write.tensor);
   io.writes.insert(w);
   if (accumulate) io.needs_prior.insert(w);
 }
@@ -51,12 +42,12 @@ void kernel_io(const Plan& plan, const Kernel& k, bool accumulate, IO& io) {
 void launch_io(eg_model* m, TargetState& ts, const Plan& plan, const Launch& L, IO& io) {
   const Target& t = *ts.target;
   auto rd = [&](int x) {
-    if (x) io.reads.insert(root(plan, x));
+    if (x) io.reads.insert(root_tensor(plan, x));
   };
   auto wr = [&](int x, bool acc) {
     if (!x) return;
-    io.writes.insert(root(plan, x));
-    if (acc) io.needs_prior.insert(root(plan, x));
+    io.writes.insert(root_tensor(plan, x));
+    if (acc) io.needs_prior.insert(root_tensor(plan, x));
   };
   switch (L.kind) {
     case StepKind::Seed: wr(L.c_tensor, false); break;
@@ -137,8 +128,8 @@ void launch_io(eg_model* m, TargetState& ts, const Plan& plan, const Launch& L, 
       for (size_t i = 0; i < sg.g.kernel_index.size(); ++i) {
         const Kernel& k = t.all[sg.g.kernel_index[i]];
         for (auto& r : k.reads)
-          if (!inside.count(root(plan, r.tensor))) rd(r.tensor);
-        const int w = root(plan, k.write.tensor);
+          if (!inside.count(root_tensor(plan, r.tensor))) rd(r.tensor);
+        const int w = root_tensor(plan, k.write.tensor);
         io.writes.insert(w);
         // a summed tensor is written whole by the fold behind the kernel; a plain store needs nothing before it
         // (a tensor that lives in the block's LDS starts from zero there)
@@ -155,8 +146,8 @@ void launch_io(eg_model* m, TargetState& ts, const Plan& plan, const Launch& L, 
       for (int ki : sg.g.kernel_index) {
         const Kernel& k = t.all[ki];
         for (auto& r : k.reads)
-          if (!inside.count(root(plan, r.tensor))) rd(r.tensor);
-        const int w = root(plan, k.write.tensor);
+          if (!inside.count(root_tensor(plan, r.tensor))) rd(r.tensor);
+        const int w = root_tensor(plan, k.write.tensor);
         io.writes.insert(w);
         if (!inside.count(w)) io.needs_prior.insert(w);
         inside.insert(w);
@@ -257,7 +248,7 @@ int check_plan(eg_model* m, TargetState& ts, Plan& plan) {
                       slots[i - 1].second, slots[i].first, slots[i].second);
     EG_PLAN_REQUIRE(plan.zero_floats >= 0 && plan.zero_floats <= plan.arena_floats, "zero prefix larger than the arena");
     for (auto& kv : plan.alias) {
-      const int r = root(plan, kv.first);
+      const int r = root_tensor(plan, kv.first);
       EG_PLAN_REQUIRE(!plan.alias.count(r), "storage-sharing chain of tensor %d does not end", kv.first);
       auto a = plan.shapes.find(kv.first), b = plan.shapes.find(r);
       EG_PLAN_REQUIRE(a != plan.shapes.end() && b != plan.shapes.end() && prod(a->second) == prod(b->second),

@@ -8,9 +8,20 @@ namespace model {
 bool row_fusion_enabled() { return !eg::sw::on(eg::Sw::NO_ROWFUSE); }
 bool row_tails_enabled() { return !eg::sw::on(eg::Sw::NO_ROW_TAIL); }
 
-// Is the tail of this RowFused launch part of the range being issued?  (run.cpp: MODE 2 and the tail launch skipped.)
-bool row_tail_active(const Plan& plan, const Launch& L) {
-  return L.kind == StepKind::RowFused && L.tail_launch >= 0 && L.tail_launch < plan.active_end && L.tail_launch >= plan.active_begin;
+// Is the tail of this RowFused launch part of the range [begin, end) being issued?  (run.cpp: MODE 2 and the tail launch skipped.)
+bool row_tail_active(const Launch& L, int begin, int end) {
+  return L.kind == StepKind::RowFused && L.tail_launch >= 0 && L.tail_launch >= begin && L.tail_launch < end;
+}
+
+// the generated source of a kernel of this plan that is still waiting to be built; false when none waits at that handle
+static bool replace_pending_source(Plan& plan, eg_kernel** slot, const std::string& source) {
+  bool replaced = false;
+  for (auto& pk : plan.pending)
+    if (pk.slot == slot) {
+      pk.source = source;
+      replaced = true;
+    }
+  return replaced;
 }
 
 // A small / map group (the optimizer updates of a small net) that DIRECTLY follows a multi-block row group whose last
@@ -44,30 +55,6 @@ int fuse_row_tails(eg_model* m, TargetState& ts, Plan& plan, const std::vector<K
     }
     if (!ok || work > 16384) continue;
     pg.g.tail_kernels = sg.g.kernel_index;
-    {  // the grid this launch will use (below), known to the generator: rowfuse.hpp grid_blocks
-      long row_floats = 0;
-      for (auto& tt : pg.g.tensors)
-        if (tt.second.role == RowGroupTensor::RowExternal || (tt.second.role == RowGroupTensor::RowLocal && (tt.second.store || tt.second.load_first)))
-          row_floats += tt.second.inner;
-      long cap = std::max(64L, (pg.g.B * std::max(1L, row_floats) * 4 + 12287) / 12288);
-      cap = eg::sw::integer(eg::Sw::ROW_TAIL_BLOCKS, cap);   // tuning aid
-      pg.g.grid_blocks = std::min<long>(pg.nblocks, std::max(1L, cap));
-    }
-    int rc = generate_row_group(t.all, infos, plan.shapes, pg.g);
-    if (rc) return rc;
-    bool replaced = false;
-    for (auto& pk : plan.pending)
-      if (pk.slot == &pg.handle) {
-        pk.source = pg.g.source;
-        replaced = true;
-      }
-    if (!replaced) {  // (cannot happen: the group's kernel is built with the plan)
-      pg.g.tail_kernels.clear();
-      return generate_row_group(t.all, infos, plan.shapes, pg.g);
-    }
-    pg.tail_group = S.row_group;
-    R.tail_launch = i + 1;
-    S.tail_of = i;
     // A launch-bound step: fewer, longer blocks (the kernel walks its samples with a grid stride) — 64 arrivals at the
     // ticket counter instead of 256 (a fan-in of 255 costs ~3.3 us, MI355X_MICROARCH.md price list) and 64 partial rows
     // for the last block; 786 KB of input do not need 256 CUs.  Per-thread totals then span several samples: the sums
@@ -82,14 +69,24 @@ int fuse_row_tails(eg_model* m, TargetState& ts, Plan& plan, const std::vector<K
     const long bytes_touched = pg.g.B * std::max(1L, row_floats) * 4;
     long cap = std::max(64L, (bytes_touched + 12287) / 12288);
     cap = std::max(1L, eg::sw::integer(eg::Sw::ROW_TAIL_BLOCKS, cap));   // tuning aid
+    pg.g.grid_blocks = std::min<long>(pg.nblocks, cap);   // the grid this launch will use, known to the generator (rowfuse.hpp)
+    int rc = generate_row_group(t.all, infos, plan.shapes, pg.g);
+    if (rc) return rc;
+    if (!replace_pending_source(plan, &pg.handle, pg.g.source)) {  // (cannot happen: the group's kernel is built with the plan)
+      pg.g.tail_kernels.clear();
+      return generate_row_group(t.all, infos, plan.shapes, pg.g);
+    }
+    pg.tail_group = S.row_group;
+    R.tail_launch = i + 1;
+    S.tail_of = i;
     if (pg.nblocks > cap) pg.nblocks = (int)cap;
   }
   return EG_OK;
 }
 
 
-bool slab_fold_active(const Plan& plan, const Launch& L) {
-  return L.kind == StepKind::SampleFused && L.fold_launch >= 0 && L.fold_launch >= plan.active_begin && L.fold_launch < plan.active_end;
+bool slab_fold_active(const Launch& L, int begin, int end) {
+  return L.kind == StepKind::SampleFused && L.fold_launch >= 0 && L.fold_launch >= begin && L.fold_launch < end;
 }
 
 // The optimizer's map group directly behind a sample group adds up the slab rows itself (rowfuse.hpp, SmallGroup::fold_*):
@@ -127,13 +124,7 @@ int fuse_slab_fold(eg_model* m, TargetState& ts, Plan& plan, const std::vector<K
     mg.g.fold_row_floats = sg.g.slab_floats;
     int rc = generate_map_group(m->prog, t.all, infos, plan.shapes, mg.g);
     if (rc) return rc;
-    bool replaced = false;
-    for (auto& pk : plan.pending)
-      if (pk.slot == &mg.handle) {
-        pk.source = mg.g.source;
-        replaced = true;
-      }
-    if (!replaced) {
+    if (!replace_pending_source(plan, &mg.handle, mg.g.source)) {
       mg.g.fold_offset.clear();
       return generate_map_group(m->prog, t.all, infos, plan.shapes, mg.g);
     }

@@ -18,21 +18,13 @@ int ensure_side_lane(eg_ctx* ctx) {
 // Tensors a launch reads / writes (storage-sharing tensors folded onto their source); false for
 // launch kinds that do not take part in overlap groups.
 bool launch_tensors(const Plan& plan, const Launch& L, std::set<int>& reads, std::set<int>& writes) {
-  auto root = [&](int t) {
-    for (int guard = 0; guard < 64; ++guard) {
-      auto a = plan.alias.find(t);
-      if (a == plan.alias.end()) break;
-      t = a->second;
-    }
-    return t;
-  };
   auto rd = [&](int t) {
-    if (t) reads.insert(root(t));
+    if (t) reads.insert(root_tensor(plan, t));
   };
   auto wr = [&](int t) {
     if (t) {
-      writes.insert(root(t));
-      reads.insert(root(t));  // accumulate / partial overwrite: conservative
+      writes.insert(root_tensor(plan, t));
+      reads.insert(root_tensor(plan, t));  // accumulate / partial overwrite: conservative
     }
   };
   switch (L.kind) {
@@ -109,15 +101,7 @@ void plan_overlap(eg_model* m, TargetState& ts, Plan& plan) {
         const PlanRowGroup& pg = *plan.row_groups[R.row_group];
         if (pg.g.single_block || pg.g.red_total <= 0 || pg.tail_group >= 0 || !pg.g.in_kernel_finalize) break;
         std::set<int> totals;
-        for (int tid : pg.red_tensors) {
-          int t = tid;
-          for (int guard = 0; guard < 64; ++guard) {
-            auto al = plan.alias.find(t);
-            if (al == plan.alias.end()) break;
-            t = al->second;
-          }
-          totals.insert(t);
-        }
+        for (int tid : pg.red_tensors) totals.insert(root_tensor(plan, tid));
         bool free_of_readers = true;
         for (int k = r + 1; k <= j && free_of_readers; ++k) {
           std::set<int> kr, kw;
