@@ -7,7 +7,7 @@
 //   plan.cpp           per-shape plans: launch list, overwrite / accumulate, arena   (+ plan_check.cpp)
 //   plan_groups.cpp    row / small / map fusion groups
 //   plan_attention.cpp attention groups: a forward attention chain as one launch, a training step over it as two
-//                      (Launch::attn: extents and views as kernels/attention_plan.hpp has them; run.cpp calls kernels/attention.hpp)
+//                      (Launch::attn: extents as kernels/attention_plan.hpp has them, views as kernels/item_grid.hpp; run.cpp calls kernels/attention.hpp)
 //   plan_epilogue.cpp  contraction + consumer epilogues
 //   plan_overlap.cpp   side-lane groups
 //   run.cpp            one launch (whole or a half batch), ranges of launches, HIP graphs, batch pipeline, exchange plan
@@ -41,7 +41,7 @@ using namespace eg::kd;
 using eg::set_error;
 
 // GemmBatched: one product per leading batch index in one launch (kernels/gemm_batched.hip); with Launch::batch1 > 0 one
-// product per pair of batch indices (kernels/gemm_batched2.hip), treated alike everywhere but in the call itself
+// product per pair of batch indices (the same kernel and launcher), treated alike everywhere, the call included
 // Attention: the forward attention chain (match_attention) as one eg_attention launch (kernels/attention_f32.hip), stand-alone
 // AttentionGrad: the chain's gradient kernels (match_attention_fit) as one eg_attention_grad call (kernels/attention_grad_f32.hip),
 // behind an Attention launch that stores the row sums too; formed only under eg_model_fuse_attention_fit
@@ -93,7 +93,7 @@ struct Launch {
   long batch1 = 0, stride_a1 = 0, stride_b1 = 0, stride_c1 = 0;   //   the inner index of a product with two (batch1 > 0)
   // Attention / AttentionGrad: everything of the launch but `accumulate`.  The extents live here — M, N, K, batch and
   // batch1 above stay 0, every reader of those asks for a gemm kind first — and each operand is a tensor and its view
-  // (kernels/attention_plan.hpp) in the launch's batch order.  None of the gemm fields is borrowed, c_tensor included: its
+  // (kernels/item_grid.hpp) in the launch's batch order.  None of the gemm fields is borrowed, c_tensor included: its
   // one reader that does not ask for the kind, the default branch of the exchange plan (run.cpp, plan_exchange), has a
   // case for each of the two kinds.
   struct Attn {

@@ -7,23 +7,6 @@
 namespace eg {
 namespace attention {
 
-Cut cut_items(long items, long tiles) {
-  Cut c;
-  c.tiles = tiles;
-  c.grid = items * tiles;
-  c.items_per_launch = std::max(1L, eg::gemm::BATCHED_MAX_BLOCKS / std::max(1L, tiles));
-  c.launches = tiles > 0 ? (items + c.items_per_launch - 1) / c.items_per_launch : 0;
-  return c;
-}
-
-Launch plan_launch(long items, const Cut& cut, long index) {
-  Launch l;
-  l.first = index * cut.items_per_launch;
-  l.items = std::min(cut.items_per_launch, items - l.first);
-  l.grid = l.items * cut.tiles;
-  return l;
-}
-
 Plan plan_attention(const Problem& p) {
   Plan r;
   if (p.batch0 < 1 || p.batch1 < 1 || p.I < 1 || p.J < 0 || p.K < 0 || p.D < (p.sums ? 0 : 1)) {

@@ -5,6 +5,7 @@
 #pragma once
 
 #include "gemm_plan.hpp"   // BATCHED_MAX_BLOCKS
+#include "item_grid.hpp"   // View, Cut, Launch
 
 namespace eg {
 namespace attention {
@@ -15,12 +16,12 @@ constexpr int MAX_HEAD = 128;  // K and D
 constexpr int THREADS = 256;
 constexpr long LDS_LIMIT = 160 * 1024;   // per CU on gfx950
 
-// One item's view of an operand, the one description from the model's plan to the kernels' arguments: floats per row step
-// and per step of the outer and the inner batch index.  The row sums have no rows to step over: their ld is unused (0).
-struct View {
-  long ld = 0, stride0 = 0, stride1 = 0;
-};
-inline bool operator==(const View& a, const View& b) { return a.ld == b.ld && a.stride0 == b.stride0 && a.stride1 == b.stride1; }
+// An operand's view and the cut of the item range into launches are the item grid's (item_grid.hpp).
+using eg::View;
+using eg::Cut;
+using eg::cut_items;
+using eg::Launch;
+using eg::plan_launch;
 
 // batch0 x batch1 items of I query rows and J keys, K the length of a query or key row, D of a value row
 struct Extents {
@@ -37,23 +38,6 @@ struct Problem : Extents {
   bool sums = false;   // eg_attention_sums: the row sums are stored too, and D == 0 still has them to store
   int cus = 256;
 };
-
-// How the flattened (o, i1) range of items, o-major, is cut into launches of one kernel with `tiles` blocks per item.
-struct Cut {
-  long tiles = 0;             // blocks per item
-  long grid = 0;              // blocks of all launches together: items * tiles
-  long items_per_launch = 0;  // at least 1; BATCHED_MAX_BLOCKS / tiles otherwise
-  long launches = 0;          // none for a kernel without tiles
-};
-Cut cut_items(long items, long tiles);
-
-// Items [first, first + items) of that range as grid = items * tiles blocks.
-struct Launch {
-  long first = 0, items = 0, grid = 0;
-};
-
-// Launch `index` of a cut of `items` items, index in [0, cut.launches).
-Launch plan_launch(long items, const Cut& cut, long index);
 
 struct Plan {
   bool supported = false;

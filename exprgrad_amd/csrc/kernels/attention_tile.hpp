@@ -8,8 +8,9 @@
 #include <type_traits>
 
 #include "../eg_internal.hpp"
-#include "gemm_f32_mfma.hpp"   // f32x4, xcd_remap
+#include "gemm_f32_mfma.hpp"   // f32x4
 #include "attention_plan.hpp"  // THREADS, View, Cut
+#include "item_launch.hpp"     // Items, block_item, item_base, for_each_launch
 
 namespace eg {
 namespace attention {
@@ -29,33 +30,16 @@ struct Arg {
 using In = Arg<const float>;
 using Out = Arg<float>;
 
-// The items of one launch: launches cut the flattened (o, i1) range, and every item has `tiles` blocks.
-struct Items {
-  unsigned batch1;                     // extent of the inner index
-  unsigned first_outer, first_inner;   // the item the launch starts at
-  int tiles;                           // blocks per item
-};
-
-// Block id -> (outer, inner, tile): block-uniform 32-bit arithmetic as in gemm_batched2_kernel.
-struct BlockItem {
-  unsigned outer, inner;
-  int tile;
-};
-
-__device__ __forceinline__ BlockItem block_item(const Items& it) {
-  const int work = eg::gemm::xcd_remap((int)blockIdx.x, (int)gridDim.x);
-  const int local = work / it.tiles;
-  BlockItem b;
-  b.tile = work - local * it.tiles;
-  const unsigned inner = it.first_inner + (unsigned)local;
-  b.outer = it.first_outer + inner / it.batch1;
-  b.inner = inner % it.batch1;
-  return b;
-}
+// The items of a launch, a block's item and the loop over a cut's launches are the item grid's (item_launch.hpp).
+using eg::Items;
+using eg::BlockItem;
+using eg::block_item;
+using eg::item_base;
+using eg::for_each_launch;
 
 template <class T>
 __device__ __forceinline__ T* item_base(const Arg<T>& x, unsigned outer, unsigned inner) {
-  return x.p + (long)outer * x.v.stride0 + (long)inner * x.v.stride1;
+  return item_base(x.p, x.v, outer, inner);
 }
 
 // ---- tiles ------------------------------------------------------------------------------------------------------------
@@ -182,19 +166,6 @@ int dynamic_lds_once(eg_ctx* ctx, const long (&bytes)[sizeof...(KERNELS)]) {
   for (size_t i = 0; i < sizeof...(KERNELS); ++i)
     EG_HIP_CHECK(hipFuncSetAttribute(kernels[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes[i]));
   if (known) attr_set[ctx->device] = true;
-  return EG_OK;
-}
-
-// One launch after the other of a cut: launch(items of the launch, grid).  `name` is the entry the message speaks of.
-template <class F>
-int for_each_launch(const char* name, long items, const Cut& cut, long batch1, F&& launch) {
-  for (long n = 0; n < cut.launches; ++n) {
-    const Launch l = plan_launch(items, cut, n);
-    EG_REQUIRE(l.items > 0 && l.grid > 0 && l.grid <= eg::gemm::BATCHED_MAX_BLOCKS, EG_ERR_INVALID, "%s: launch out of range", name);
-    const Items it = {(unsigned)batch1, (unsigned)(l.first / batch1), (unsigned)(l.first % batch1), (int)cut.tiles};
-    const int rc = launch(it, (unsigned)l.grid);
-    if (rc) return rc;
-  }
   return EG_OK;
 }
 

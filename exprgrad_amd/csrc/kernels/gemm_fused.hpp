@@ -11,6 +11,7 @@
 #include <string>
 
 #include "../eg_internal.hpp"
+#include "item_grid.hpp"   // View
 
 namespace eg {
 namespace gemm {
@@ -61,14 +62,18 @@ struct SplitPassOperand {
 int split_pass(eg_ctx* ctx, const SplitPassOperand& a, const SplitPassOperand& b, long K, void* planes, unsigned epoch);
 
 // `batch` exact f32 products of one shape, X_b = X + b * stride_x, in one launch (gemm_batched.hip): what eg_sgemm_batched
-// and the model layer's batched launches run.
+// and the model layer's launches with one batch index run.
 int sgemm_batched(eg_ctx* ctx, int trans_a, int trans_b, long batch, long M, long N, long K, const float* A, long lda, long stride_a,
                   const float* B, long ldb, long stride_b, float* C, long ldc, long stride_c, int accumulate, const float* bias);
-// batch0 x batch1 exact f32 products of one shape, X_{o,i} = X + o * stride_x0 + i * stride_x1 (gemm_batched2.hip): what
-// eg_sgemm_batched2 and the model layer's launches with two batch indices run.
+// batch0 x batch1 exact f32 products of one shape, X_{o,i} = X + o * stride_x0 + i * stride_x1, by the same kernel and
+// launcher (gemm_batched.hip): what eg_sgemm_batched2 and the model layer's launches with two batch indices run.
 int sgemm_batched2(eg_ctx* ctx, int trans_a, int trans_b, long batch0, long batch1, long M, long N, long K, const float* A, long lda,
                    long stride_a0, long stride_a1, const float* B, long ldb, long stride_b0, long stride_b1, float* C, long ldc, long stride_c0,
                    long stride_c1, int accumulate, const float* bias);
+// Either of the two with an operand as its View (item_grid.hpp), the model layer's one call: batch1 == 0 is sgemm_batched
+// over batch0 items with every view's stride0, batch1 > 0 is sgemm_batched2.
+int sgemm_batched_views(eg_ctx* ctx, int trans_a, int trans_b, long batch0, long batch1, long M, long N, long K, const float* A, const View& a,
+                        const float* B, const View& b, float* C, const View& c, int accumulate, const float* bias);
 // The float64 twins (gemm_f64_mfma.hip): the plain product behind eg_dgemm, and `batch` of them in one launch — what
 // eg_dgemm_batched and a float64 model's batched launches run.  Strides and leading dimensions in doubles.
 int dgemm(eg_ctx* ctx, int trans_a, int trans_b, long M, long N, long K, const double* A, long lda, const double* B, long ldb, double* C,

@@ -763,19 +763,14 @@ DgemmBatchedPlan plan_dgemm_batched(const DgemmBatchedProblem& p) {
   r.vec = dgemm_batched_vec(p);
   r.tiles_m = (int)((p.M + T - 1) / T);
   r.tiles_n = (int)((p.N + T - 1) / T);
-  r.tiles = (long)r.tiles_m * r.tiles_n;
-  r.items_per_launch = std::max(1L, BATCHED_MAX_BLOCKS / r.tiles);
-  r.launches = (p.batch + r.items_per_launch - 1) / r.items_per_launch;
+  const Cut c = cut_items(p.batch, (long)r.tiles_m * r.tiles_n);
+  r.tiles = c.tiles, r.items_per_launch = c.items_per_launch, r.launches = c.launches;
   return r;
 }
 
 DgemmBatchedLaunch dgemm_batched_launch(const DgemmBatchedPlan& plan, long batch, long index) {
-  DgemmBatchedLaunch l;
-  l.first = index * plan.items_per_launch;
-  l.items = std::min(plan.items_per_launch, batch - l.first);
-  l.grid = l.items * plan.tiles;
-  l.remap = dgemm_remap(l.grid);
-  return l;
+  const Launch l = plan_launch(batch, {plan.tiles, batch * plan.tiles, plan.items_per_launch, plan.launches}, index);
+  return {l.first, l.items, l.grid, dgemm_remap(l.grid)};
 }
 
 // ---- float64 convolutions ------------------------------------------------------------------------------------------------

@@ -3,6 +3,8 @@
 // kernel launches, and tests/test_gemm_plan_cpu.py checks plans without a GPU.
 #pragma once
 
+#include "item_grid.hpp"
+
 namespace eg {
 namespace gemm {
 
@@ -161,8 +163,7 @@ inline long dgemm_k_unsliced(long K) {
 DgemmPlan plan_dgemm(const DgemmProblem& p);
 
 // ---- float64: `batch` products of one shape (gemm_f64_mfma.hip, dgemm_batched_kernel) ---------------------------------
-// Blocks of one batched launch, float32 and float64: grid x block threads stays below 2^32 and the block id an int.
-constexpr long BATCHED_MAX_BLOCKS = 1L << 22;
+using eg::BATCHED_MAX_BLOCKS;   // blocks of one batched launch, float32 and float64 (item_grid.hpp)
 constexpr int DGEMM_BATCHED_TILE = 64;   // the one tile the batched float64 kernel is built for
 
 // One call as the planner sees it.  Leading dimensions and strides in doubles; a stride of 0 shares the operand.

@@ -197,7 +197,7 @@ int eg_sgemm_batched(eg_ctx* ctx, int trans_a, int trans_b, int64_t batch, int64
  * batch0 and batch1 must each be below 2^31 (EG_ERR_INVALID).
  * 16-byte loads of an operand, and the store of whole tiles through LDS, are taken when what they need of item 0 holds
  * for every item: the pointer 16-byte aligned and both of that operand's strides multiples of 4.
- * One launch of batch0 x batch1 x tiles blocks on 64 x 64 tiles (kernels/gemm_batched2.hip), split along the flattened
+ * One launch of batch0 x batch1 x tiles blocks on 64 x 64 tiles (kernels/gemm_batched.hip: eg_sgemm_batched's kernel and launcher), split along the flattened
  * (o, i) range when it would exceed 2^22 blocks; items that fill the chip by themselves run as a loop of exact products.
  * No k-slices, workspace or atomics, never the split-bf16 route: every output element is one k-ascending sum on the f32
  * matrix instruction.  Bits:

@@ -24,16 +24,17 @@ def driver(tmp_path_factory):
     return exe
 
 
-def plans(exe, cases):
-    """cases: (batch, M, N, K, lda, ldb, stride_a, stride_b, a_aligned, b_aligned, cus) -> [(plan, [launch, ...]), ...]"""
+def plans(exe, cases, mode=()):
+    """cases: (batch, M, N, K, lda, ldb, stride_a, stride_b, a_aligned, b_aligned, cus) -> [(plan, [launch, ...]), ...]
+    mode ("cut",): cases (items, tiles_m, tiles_n) -> [(cut, [launch, ...]), ...]"""
     text = "".join(" ".join(str(int(v)) for v in c) + "\n" for c in cases)
-    out = subprocess.run([exe], input=text, capture_output=True, text=True, timeout=120)
+    out = subprocess.run([exe, *mode], input=text, capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, out.stderr
     result = []
     for line in out.stdout.splitlines():
         kind, *fields = line.split()
         row = {k: int(v) for k, v in (f.split("=", 1) for f in fields)}
-        if kind == "plan":
+        if kind in ("plan", "cut"):
             result.append((row, []))
         else:
             result[-1][1].append(row)
@@ -164,3 +165,46 @@ def test_vec_of_a_batch_of_one_is_the_plain_rule(driver):
             assert plan["vec"] == int(plan["dgemm_vec"] and stride_a % 2 == 0 and stride_b % 2 == 0), c
         seen.add((batch, plan["vec"], plan["dgemm_vec"]))
     assert seen == {(1, 0, 0), (1, 1, 1), (2, 0, 0), (2, 1, 1), (2, 0, 1)}
+
+
+def cut_table():
+    """(items, tiles_m, tiles_n): for tiles of 1, of a few, of a non-divisor of 2^22, of half a launch, of exactly one launch
+    (2^22) and of more than one, `items` of 1 and one below, at and above a multiple of items_per_launch = max(1, 2^22 // tiles)."""
+    t = []
+    for tm, tn in [(1, 1), (3, 2), (7, 1), (2048, 1024), (2048, 2048), (2049, 2048), (4096, 4096)]:
+        ipl = max(1, MAX_BLOCKS // (tm * tn))
+        for items in sorted({1, ipl - 1, ipl, ipl + 1, 3 * ipl - 1, 3 * ipl, 3 * ipl + 1} - {0}):
+            t.append((items, tm, tn))
+    return t
+
+
+def test_the_item_grids_cut_covers_every_item_once_and_is_the_float64_planners(driver):
+    """cut_items / plan_launch (kernels/item_grid.hpp), which the float32 batched products, the attention kernels and — through
+    plan_dgemm_batched / dgemm_batched_launch — the float64 batched product all cut their launches with: every item in exactly
+    one launch, every grid within BATCHED_MAX_BLOCKS, and the float64 planner's figures equal to the cut's.  An item of more
+    than 2^22 tiles fits no launch: the cut still hands out every item once, one per launch, with grid == tiles, which is what
+    every launcher refuses ("launch out of range"), and every planner turns such an item away before it cuts (the float64
+    planner loops: d_loop); there dgemm_batched_launch is compared on a plan that holds the cut's figures."""
+    table = cut_table()
+    assert {tm * tn for _, tm, tn in table} >= {1, MAX_BLOCKS} and any(tm * tn > MAX_BLOCKS for _, tm, tn in table)
+    for (items, tm, tn), (cut, launches) in zip(table, plans(driver, table, mode=("cut",))):
+        tiles = tm * tn
+        ipl = max(1, MAX_BLOCKS // tiles)
+        want_launches = -(-items // ipl)
+        fits = tiles <= MAX_BLOCKS
+        assert cut["max_blocks"] == MAX_BLOCKS and cut["tiles"] == tiles, (items, tiles, cut)
+        assert cut["items_per_launch"] == ipl and cut["launches"] == want_launches == len(launches), (items, tiles, cut)
+        assert cut["d_loop"] == int(not fits), (items, tiles, cut)
+        if fits:
+            assert (cut["d_tiles"], cut["d_items_per_launch"], cut["d_launches"]) == (tiles, ipl, want_launches), (items, tiles, cut)
+        else:
+            assert cut["d_launches"] == 0 and ipl == 1, (items, tiles, cut)
+        nxt = 0
+        for i, l in enumerate(launches):
+            assert l["index"] == i and l["first"] == nxt and 1 <= l["items"] <= ipl, (items, tiles, l)
+            assert l["grid"] == l["items"] * tiles and l["grid"] > 0, (items, tiles, l)
+            assert (l["grid"] <= MAX_BLOCKS) == fits, (items, tiles, l)
+            assert (l["d_first"], l["d_items"], l["d_grid"]) == (l["first"], l["items"], l["grid"]), (items, tiles, l)
+            nxt += l["items"]
+        assert nxt == items, (items, tiles)
+        assert all(l["items"] == ipl for l in launches[:-1]), (items, tiles)

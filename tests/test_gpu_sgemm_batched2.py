@@ -1,4 +1,4 @@
-"""GPU parity of eg_sgemm_batched2 (kernels/gemm_batched2.hip) against the oracle and a float64 product.
+"""GPU parity of eg_sgemm_batched2 (kernels/gemm_batched.hip) against the oracle and a float64 product.
 
 Every item (o, i) is compared with refcpu.sgemm on that item's operands and with the float64 numpy product, within TOL
 (1e-5 relative to the item's largest value).  Inputs are U[-0.5, 0.5) and K <= 96 in the table (tests/batched2_cases.py),
@@ -109,6 +109,55 @@ def test_bits(gpu_ctx, refcpu):
     assert np.array_equal(dc.read().view(np.uint32), first.view(np.uint32))
     h = cases.head_in_row(16, 20, 0, 31)
     same_bits_as_single_calls(gpu_ctx, h, run(gpu_ctx, h))
+
+
+def one_index_cases():
+    """(id, constructor) of five items in a row, as both entries can address them.  Ragged: 70 x 66 x 19 is 2 x 2 ragged tiles
+    and a k tail, on element loads through an odd lda.  Whole: 64 x 64 x 32 with every stride a multiple of 4, 16-byte loads.
+    C is padded behind every row and every item, and poisoned there."""
+    t = []
+    for ta, tb in cases.LAYOUTS:
+        def ragged(ta=ta, tb=tb, **kw):
+            ra, ca = (19, 70) if ta else (70, 19)
+            rb, cb = (66, 19) if tb else (19, 66)
+            c = Case(1, 5, 70, 66, 19, ta, tb, a=cases.nested(5, ra, ca, 3 if ta else 2, 5), b=cases.nested(5, rb, cb, 3, 5),
+                     c=cases.nested(5, 70, 66, 3, 5), seed=80 + 2 * ta + tb, **kw)
+            assert c.a_lay[0] % 2 == 1
+            return c
+        t.append(("ragged-%d%d" % (ta, tb), ragged))
+    t.append(("ragged-00-accumulate-bias", lambda: t[0][1](accumulate=True, bias=True)))
+    t.append(("whole-16-byte", lambda: Case(1, 5, 64, 64, 32, a=cases.nested(5, 64, 32, 4, 8), b=cases.nested(5, 32, 64, 4, 8),
+                                            c=cases.nested(5, 64, 64, 4, 8), seed=90)))
+    return t
+
+
+@pytest.mark.parametrize("make", [m for _, m in one_index_cases()], ids=[n for n, _ in one_index_cases()])
+def test_one_kernel_behind_both_entries(gpu_ctx, make):
+    """eg_sgemm_batched(batch = 5, stride), eg_sgemm_batched2(1, 5, strides (0, stride)) and eg_sgemm_batched2(5, 1, strides
+    (stride, 0)) run one kernel through one launcher: the same bits in every element of C, the poisoned padding included.
+    The first result is also held to the float64 product (19 or 32 terms in order: well inside TOL)."""
+    c = make()
+    if c.accumulate:   # Case fills an accumulating C with values throughout: poison what lies between rows and items again
+        c0 = np.full_like(c.c0, POISON)
+        for o, i in c.items():
+            c.c_item(c0, o, i)[...] = c.c_item(c.c0, o, i)
+        c.c0 = c0
+    _, n, M, N, K = c.dims
+    (lda, _, sa), (ldb, _, sb), (ldc, _, sc) = c.a_lay, c.b_lay, c.c_lay
+    da, db = dev(gpu_ctx, c.a), dev(gpu_ctx, c.b)
+    dbias = dev(gpu_ctx, c.bias) if c.bias is not None else None
+    got = []
+    for b0, b1 in ((0, 0), (1, n), (n, 1)):   # (0, 0): the entry with one batch index
+        dc = dev(gpu_ctx, c.c0)
+        if b0 == 0:
+            ops.sgemm_batched(gpu_ctx, n, M, N, K, da, lda, sa, db, ldb, sb, dc, ldc, sc, c.ta, c.tb, c.accumulate, dbias)
+        else:
+            pair = lambda s: (0, s) if b0 == 1 else (s, 0)
+            ops.sgemm_batched2(gpu_ctx, b0, b1, M, N, K, da, lda, pair(sa), db, ldb, pair(sb), dc, ldc, pair(sc), c.ta, c.tb, c.accumulate, dbias)
+        got.append(dc.read())
+    check(c, None, got[0], oracle=False)
+    for other in got[1:]:
+        assert np.array_equal(got[0].view(np.uint32), other.view(np.uint32))
 
 
 def test_more_items_than_one_launch(gpu_ctx):
