@@ -17,6 +17,7 @@ SHAPES = [
     (1, 2, 130, 129, 128, 128),  # the largest instantiation, three tiles each way
     (3, 2, 7, 200, 33, 1),       # D = 1, K padded to 64, four key tiles
     (1, 1, 200, 7, 8, 40),       # many query tiles over one partial key tile: the dK/dV loop has them, the forward never had
+    (1, 2, 65, 64, 40, 72),      # K and D padded differently (64, 128); tests/test_gpu_attention_heads.py has the other pairs
 ]
 IDS = ["x".join(map(str, d)) for d in SHAPES]
 

@@ -21,7 +21,8 @@ from parity import Trio
 pytestmark = pytest.mark.gpu
 f32 = np.float32
 
-SHAPES = [(2, 3, 33, 70, 16, 16), (1, 2, 65, 64, 20, 12), (2, 1, 64, 64, 64, 64), (1, 1, 1, 1, 1, 1), (1, 2, 130, 129, 128, 128)]
+SHAPES = [(2, 3, 33, 70, 16, 16), (1, 2, 65, 64, 20, 12), (2, 1, 64, 64, 64, 64), (1, 1, 1, 1, 1, 1), (1, 2, 130, 129, 128, 128),
+          (1, 2, 65, 64, 40, 72)]
 PROJECTED = (2, 2, 70, 8, 16, 16)     # B, H, S, E, K, D
 ident = lambda d: "x".join(map(str, d))
 

@@ -62,7 +62,7 @@ def tensor_id(graphs, name):
 
 
 # ---- 1. the chain fuses ---------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("dims", [(2, 3, 33, 70, 16, 16), (1, 2, 65, 64, 20, 12)], ids=lambda d: "x".join(map(str, d)))
+@pytest.mark.parametrize("dims", [(2, 3, 33, 70, 16, 16), (1, 2, 65, 64, 20, 12), (1, 2, 65, 64, 40, 72)], ids=lambda d: "x".join(map(str, d)))
 def test_forward_is_one_launch(gpu_ctx, dims):
     """Fails without the feature: the plan is three launches."""
     trio = Trio(gpu_ctx, fp.attention_forward())

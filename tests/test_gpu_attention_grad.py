@@ -57,22 +57,26 @@ def sums_view(ctx, layout, b0, b1, I, offset):
 
 
 class Case:
-    """The operands of one call on the device: inputs from attention_grad_cases.inputs, outputs of NaN."""
+    """The operands of one call on the device: inputs from attention_grad_cases.inputs (or `given`: q, k, v, labels), outputs of
+    NaN.  shared: Kk and V have stride 0 along batch0 (True), along batch1 ("inner") or along both ("both")."""
 
-    def __init__(self, ctx, dims, layout, seed=None, offset=0, pad=0, shared=False, out_pad=None, bases=None):
+    def __init__(self, ctx, dims, layout, seed=None, offset=0, pad=0, shared=False, out_pad=None, bases=None, given=None, scale=SCALE):
         b0, b1, I, J, K, D = dims
-        self.ctx, self.dims, self.layout = ctx, dims, layout
-        self.q, self.k, self.v, self.labels = gc.inputs(dims, seed)
-        if shared:
+        self.ctx, self.dims, self.layout, self.scale = ctx, dims, layout, scale
+        self.q, self.k, self.v, self.labels = given or gc.inputs(dims, seed)
+        outer, inner = shared in (True, "both"), shared in ("inner", "both")
+        if outer:
             self.k, self.v = self.k[:1], self.v[:1]
+        if inner:
+            self.k, self.v = self.k[:, :1], self.v[:, :1]
         ldq, q0, q1 = lay(layout, b1, I, K, pad)
         ldk, k0, k1 = lay(layout, b1, J, K, pad)
         ldv, v0, v1 = lay(layout, b1, J, D, pad)
         self.layo = lay(layout, b1, I, D, pad)
         self.offset = offset
         self.Q = View(self.q, ldq, q0, q1, offset).upload(ctx)
-        self.Kk = View(self.k, ldk, 0 if shared else k0, k1, offset).upload(ctx)
-        self.V = View(self.v, ldv, 0 if shared else v0, v1, offset).upload(ctx)
+        self.Kk = View(self.k, ldk, 0 if outer else k0, 0 if inner else k1, offset).upload(ctx)
+        self.V = View(self.v, ldv, 0 if outer else v0, 0 if inner else v1, offset).upload(ctx)
         self.O = out_view(ctx, layout, (b0, b1, I, D), offset, out_pad)
         self.S = sums_view(ctx, layout, b0, b1, I, offset)
         bases = bases or {}
@@ -84,7 +88,7 @@ class Case:
     def forward(self, sums=True, O=None, accumulate=False):
         """eg_attention_sums (or eg_attention) into O; the O and Sums buffers as read back"""
         O = O or self.O
-        args = (self.ctx,) + self.dims + (SCALE, self.Q, self.Q.ld, self.Q.strides, self.Kk, self.Kk.ld, self.Kk.strides, self.V, self.V.ld,
+        args = (self.ctx,) + self.dims + (self.scale, self.Q, self.Q.ld, self.Q.strides, self.Kk, self.Kk.ld, self.Kk.strides, self.V, self.V.ld,
                                           self.V.strides, O, O.ld, O.strides)
         if sums:
             ops.attention_sums(*args, self.S, self.S.strides, accumulate)
@@ -100,7 +104,7 @@ class Case:
     def backward(self, accumulate=0, O=None):
         O = O or self.O
         x = lambda t: (t, t.ld, t.strides)
-        ops.attention_grad(self.ctx, *self.dims, SCALE, *x(self.Q), *x(self.Kk), *x(self.V), *x(O), self.S, self.S.strides, *x(self.dO), *x(self.dQ),
+        ops.attention_grad(self.ctx, *self.dims, self.scale, *x(self.Q), *x(self.Kk), *x(self.V), *x(O), self.S, self.S.strides, *x(self.dO), *x(self.dQ),
                            *x(self.dK), *x(self.dV), accumulate)
         return self.dQ.dev.read(), self.dK.dev.read(), self.dV.dev.read()
 
@@ -112,7 +116,7 @@ class Case:
         return self.backward(accumulate)
 
     def exact(self):
-        return gc.closed_form(self.q, self.k, self.v, self.d_out)
+        return gc.closed_form(self.q, self.k, self.v, self.d_out, self.scale)
 
 
 def check_grads(case, label, bufs, with_oracle, bases=None):
