@@ -99,6 +99,7 @@ _SIGS = {
     "eg_model_set_seed": (c_int, [c_void_p, ctypes.c_uint64]),
     "eg_model_keep_values": (c_int, [c_void_p, c_int]),
     "eg_model_fuse_attention_fit": (c_int, [c_void_p, c_int]),
+    "eg_model_batched2_f64": (c_int, [c_void_p, c_int]),
     "eg_fill_uniform": (c_int, [c_void_p, c_i64, ctypes.c_float, ctypes.c_float, c_void_p, ctypes.c_uint64, c_void_p]),
     "eg_rng_advance": (c_int, [c_void_p, c_void_p]),
     "eg_model_kernel_count": (c_int, [c_void_p, c_char_p]),
@@ -145,6 +146,8 @@ _SIGS = {
                          c_void_p, c_i64, c_int, c_void_p]),
     "eg_dgemm_batched": (c_int, [c_void_p, c_int, c_int, c_i64, c_i64, c_i64, c_i64, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_i64,
                                  c_void_p, c_i64, c_i64, c_int, c_void_p]),
+    "eg_dgemm_batched2": (c_int, [c_void_p, c_int, c_int, c_i64, c_i64, c_i64, c_i64, c_i64, c_void_p, c_i64, c_i64, c_i64,
+                                  c_void_p, c_i64, c_i64, c_i64, c_void_p, c_i64, c_i64, c_i64, c_int, c_void_p]),
     "eg_conv2_nhwc_f64": (c_int, [c_void_p] + [c_i64] * 7 + [c_void_p, c_void_p, c_void_p, c_int]),
     "eg_conv2_nhwc_grad_filter_f64": (c_int, [c_void_p] + [c_i64] * 7 + [c_void_p, c_void_p, c_void_p, c_int]),
     "eg_conv2_nhwc_grad_image_f64": (c_int, [c_void_p] + [c_i64] * 7 + [c_void_p, c_void_p, c_void_p, c_int]),

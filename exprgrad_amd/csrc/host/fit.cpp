@@ -76,18 +76,8 @@ int launch_group(eg_model* m, TargetState& ts, Plan& plan, long group, long b, R
   bool fresh = false;
   if (!fg.exec || fg.key != key) {
     fresh = true;
-    if (fg.exec) {
-      EG_HIP_CHECK(hipStreamSynchronize(ctx->stream));   // (an older group may still be running)
-      hipGraphExecDestroy(fg.exec);
-      fg.exec = nullptr;
-    }
-    if (fg.exec2) hipGraphExecDestroy(fg.exec2);
-    fg.exec2 = nullptr;
-    fg.launched[0] = fg.launched[1] = false;
-    fg.turn = 0;
-    if (fg.graph) hipGraphDestroy(fg.graph);
-    fg.graph = nullptr;
-    fg.copies.clear();
+    if (fg.exec) EG_HIP_CHECK(hipStreamSynchronize(ctx->stream));   // (an older group may still be running)
+    drop_fit_graph(m);
     hipGraph_t graph = nullptr;
     if (hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) {
       (void)hipGetLastError();

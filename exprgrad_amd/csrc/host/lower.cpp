@@ -33,7 +33,7 @@ void inline_producers(eg_model* m, TargetState& ts, bool batched_gemm) {
     BatchedGemmMatch bg;
     Batched2GemmMatch bg2;
     return k.is_seed || match_gemm(k, g) || (!prog.f64 && match_conv(k, c)) ||
-           (batched_gemm && (match_batched_gemm(k, bg) || (!prog.f64 && match_batched2_gemm(k, bg2))));
+           (batched_gemm && (match_batched_gemm(k, bg) || ((!prog.f64 || m->batched2_f64) && match_batched2_gemm(k, bg2))));
   };
   for (size_t p = 0; p < t.live.size(); ++p) {
     if (ts.lowered[p].absorbed || (int)p == t.first_update) continue;
@@ -258,8 +258,9 @@ int lower_target(eg_model* m, TargetState& ts) {
       continue;
     }
     // a product with two batch indices, the head index inside the rows included: one eg_sgemm_batched2 launch, stand-alone
-    // like the above.  (float64: no such entry yet — the generated kernel over `double` stays.)
-    if (batched_gemm && !m->prog.f64 && match_batched2_gemm(k, lo.bgemm2)) {
+    // like the above.  (float64: eg_dgemm_batched2's entry, only where the model asks for it — eg_model_batched2_f64, which
+    // lowers the targets again; by default the generated kernel over `double` stays.)
+    if (batched_gemm && (!m->prog.f64 || m->batched2_f64) && match_batched2_gemm(k, lo.bgemm2)) {
       lo.kind = StepKind::GemmBatched;
       lo.standalone = true;
       lo.two_batch = true;

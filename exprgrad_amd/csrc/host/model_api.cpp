@@ -124,6 +124,25 @@ int model_backward_with_exchange(eg_model* m, const char* target, const GradExch
 }
 EG_CATCH_ALL
 
+namespace model {
+// The captured group of batches goes: both executables, the graph its nodes are addressed through, and what was noted of
+// them.  The caller has waited for the stream where a launch of it may still be queued.  (The two events stay.)
+void drop_fit_graph(eg_model* m) {
+  eg_model::FitGraph& fg = m->fit_graph;
+  if (fg.exec) hipGraphExecDestroy(fg.exec);
+  fg.exec = nullptr;
+  if (fg.exec2) hipGraphExecDestroy(fg.exec2);
+  fg.exec2 = nullptr;
+  fg.launched[0] = fg.launched[1] = false;
+  fg.turn = 0;
+  if (fg.graph) hipGraphDestroy(fg.graph);
+  fg.graph = nullptr;
+  fg.copies.clear();
+  fg.readers.clear();
+  fg.key.clear();
+}
+
+}  // namespace model
 }  // namespace eg
 
 extern "C" {
@@ -183,6 +202,7 @@ int eg_model_compile(eg_ctx* ctx, const char* program_text, eg_model** out) try 
       EG_HIP_CHECK(hipMemsetAsync(ts.bucket, 0, (size_t)off * sizeof(float), ctx->stream));  // (ordered against the launches that follow)
       ts.bucket_owned = true;
     }
+    if (m->f64) ts.pristine = t.all;  // (eg_model_batched2_f64 lowers the target again)
     rc = lower_target(m.get(), ts);
     if (rc) return rc;
   }
@@ -198,14 +218,9 @@ int eg_model_free(eg_model* m) try {
   if (!m) return EG_OK;
   hipSetDevice(m->ctx->device);
   hipStreamSynchronize(m->ctx->stream);
-  if (m->fit_graph.exec) hipGraphExecDestroy(m->fit_graph.exec);
-  m->fit_graph.exec = nullptr;
-  if (m->fit_graph.exec2) hipGraphExecDestroy(m->fit_graph.exec2);
-  m->fit_graph.exec2 = nullptr;
+  drop_fit_graph(m);
   for (auto& ev : m->fit_graph.done)
     if (ev) hipEventDestroy(ev);
-  if (m->fit_graph.graph) hipGraphDestroy(m->fit_graph.graph);
-  m->fit_graph.graph = nullptr;
   for (auto& kv : m->targets) {
     for (auto& p : kv.second.plans) release_plan(*p.second);
     if (kv.second.bucket_owned && kv.second.bucket) hipFree(kv.second.bucket);
@@ -802,6 +817,61 @@ int eg_model_fuse_attention_fit(eg_model* m, int on) try {
     describe(m);      // eg_model_plan_text names the launches the setting asks for
   }
   return EG_OK;
+}
+EG_CATCH_ALL
+
+// Lowering decides which kernels are library launches, and producer inlining depends on that (a map is never recomputed
+// inside a library launch): the setting lowers every target again from its kernels as compiled.  The plans made so far
+// point into the old lowering and go, with the captured training graph that replays their launches and with the old
+// lowering's generated kernels.  If lowering or building fails, the model goes back to the setting it had (the same steps
+// the other way); if that fails too, the model has no usable lowering and the error says so.
+static void free_lowering_kernels(eg_model* m, TargetState& ts) {
+  auto drop = [&](Generic& g) {
+    if (!g.handle) return;
+    m->kernels.erase(std::remove(m->kernels.begin(), m->kernels.end(), g.handle), m->kernels.end());
+    eg_kernel_free(g.handle);
+    g.handle = nullptr;
+  };
+  for (Lowered& lo : ts.lowered) {
+    drop(lo.mode_a);
+    drop(lo.with_consumer_code);
+    for (auto& kv : lo.mode_b) drop(kv.second);
+  }
+}
+
+static int lower_again(eg_model* m, bool on) {
+  m->batched2_f64 = on;
+  m->inputs_gen++;  // the plan key changes: the next run looks its plan up again
+  m->pending.clear();
+  for (auto& kv : m->targets) {
+    TargetState& ts = kv.second;
+    for (auto& p : ts.plans) release_plan(*p.second);
+    ts.plans.clear();
+    ts.last = nullptr;
+    free_lowering_kernels(m, ts);
+    ts.target->all = ts.pristine;
+    int rc = lower_target(m, ts);
+    if (rc) return rc;
+  }
+  int rc = build_pending(m);
+  if (rc) return rc;
+  describe(m);  // eg_model_plan_text names the launches the setting asks for
+  return EG_OK;
+}
+
+int eg_model_batched2_f64(eg_model* m, int on) try {
+  EG_REQUIRE(m, EG_ERR_INVALID, "eg_model_batched2_f64: NULL model");
+  EG_REQUIRE(m->f64, EG_ERR_INVALID, "eg_model_batched2_f64: a float32 model (its products with two batch indices are eg_bgemm2 launches already)");
+  if (m->batched2_f64 == (on != 0)) return EG_OK;
+  EG_HIP_CHECK(hipSetDevice(m->ctx->device));
+  EG_HIP_CHECK(hipStreamSynchronize(m->ctx->stream));  // launches of the plans and kernels released below may still be queued
+  drop_fit_graph(m);
+  const int rc = lower_again(m, on != 0);
+  if (rc == EG_OK) return EG_OK;
+  const std::string why = eg_last_error();
+  if (lower_again(m, on == 0) != EG_OK) set_error("eg_model_batched2_f64: %s; going back failed as well: the model has no usable lowering", why.c_str());
+  else set_error("eg_model_batched2_f64: %s; the model keeps the setting it had", why.c_str());
+  return rc;
 }
 EG_CATCH_ALL
 

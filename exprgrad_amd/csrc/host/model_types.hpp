@@ -288,6 +288,9 @@ struct TargetState {
   // (GradExchange::group): host/dp_schedule.hpp ScheduleTable
   eg::dp::ScheduleTable dp_schedules;
   long last_epoch = -1;         // ... and Model.epoch (compared when the program computes host values from epoch())
+  // float64 models: target->all as it was before the first lowering.  Producer inlining edits the kernels in place, so
+  // lowering the target again (eg_model_batched2_f64) starts from this copy.
+  std::vector<Kernel> pristine;
 };
 
 struct BoundInput {
@@ -314,6 +317,7 @@ struct eg_model {
   int esz = 1;
   bool keep_values = false;  // eg_model_keep_values: plans keep result values where they would keep predicate bits
   bool fuse_attention_fit = false;  // eg_model_fuse_attention_fit: training steps over an attention chain run on the fused pair
+  bool batched2_f64 = false;  // eg_model_batched2_f64: a float64 model's products with two batch indices run as eg_bgemm2 launches
   uint64_t inputs_gen = 0;  // bumped by every change of `inputs` (bind, clear, fit): caches keyed on the bindings compare it
   float grad_scale = 1.0f;
   long epoch = 0;
@@ -396,6 +400,8 @@ struct LaneSwap {
   }
 };
 
+// model_api.cpp
+void drop_fit_graph(eg_model* m);
 // lower.cpp
 int build_generic(eg_model* m, Generic& g);
 void inline_producers(eg_model* m, TargetState& ts, bool batched_gemm);

@@ -211,6 +211,7 @@ std::string shape_key(eg_model* m) {
   os << "e" << (m->prog.epoch_in_setup ? m->epoch : 0);  // host values computed from epoch() are fixed per plan (kd.hpp)
   if (m->keep_values) os << "v";
   if (m->fuse_attention_fit) os << "a";
+  if (m->batched2_f64) os << "d";
   return os.str();
 }
 

@@ -122,12 +122,12 @@ int issue_gemm(eg_model* m, TargetState& ts, Plan& plan, const Launch& L, const 
 
 int issue_batched(eg_model* m, TargetState& ts, Plan& plan, const Launch& L) {
   eg_ctx* ctx = m->ctx;
+  const eg::View a = {L.lda, L.stride_a, L.stride_a1}, b = {L.ldb, L.stride_b, L.stride_b1}, c = {L.ldc, L.stride_c, L.stride_c1};
   if (m->f64) {
     auto dp = [&](int t) { return reinterpret_cast<double*>(tensor_ptr(m, ts, plan, t)); };
-    return eg::gemm::dgemm_batched(ctx, L.trans_a, L.trans_b, L.batch, L.M, L.N, L.K, dp(L.a_tensor), L.lda, L.stride_a, dp(L.b_tensor), L.ldb,
-                                   L.stride_b, dp(L.c_tensor), L.ldc, L.stride_c, L.accumulate, nullptr);
+    return eg::gemm::dgemm_batched_views(ctx, L.trans_a, L.trans_b, L.batch, L.batch1, L.M, L.N, L.K, dp(L.a_tensor), a, dp(L.b_tensor), b,
+                                         dp(L.c_tensor), c, L.accumulate, nullptr);
   }
-  const eg::View a = {L.lda, L.stride_a, L.stride_a1}, b = {L.ldb, L.stride_b, L.stride_b1}, c = {L.ldc, L.stride_c, L.stride_c1};
   return eg::gemm::sgemm_batched_views(ctx, L.trans_a, L.trans_b, L.batch, L.batch1, L.M, L.N, L.K, tensor_ptr(m, ts, plan, L.a_tensor), a,
                                        tensor_ptr(m, ts, plan, L.b_tensor), b, tensor_ptr(m, ts, plan, L.c_tensor), c, L.accumulate, nullptr);
 }

@@ -15,7 +15,12 @@
 //
 // eg_dgemm_batched — `out[g,i,j] ++= a[g,i,k] * b[g,k,j]` of a float64 program and its two derived gradients, which the
 // reference runs as one work-item per output element — is the same tile body, one block per (item, tile), in one launch:
-// dgemm_batched_kernel below, planned by plan_dgemm_batched (gemm_plan.cpp).
+// dgemm_batched1_kernel below, planned by plan_dgemm_batched (gemm_plan.cpp).
+// eg_dgemm_batched2 — the multi-head products `s[b,h,i,j] ++= q[b,i,h,k] * kk[b,j,h,k]`, `o[b,i,h,d] ++= p[b,h,i,j] * v[b,j,h,d]`
+// and the four gradients derive makes of them, two batch indices with two strides per operand — is the same tile body through
+// the same launcher: the items are the item grid's (item_grid.hpp, item_launch.hpp), as in gemm_batched.hip.  A float64 model
+// runs these products on it where it asks for it (eg_model_batched2_f64, host/lower.cpp).
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 
@@ -24,6 +29,7 @@
 #include "gemm_layout.hpp"
 #include "gemm_plan.hpp"
 #include "gemm_f64_tile.hpp"
+#include "item_launch.hpp"
 
 namespace {
 
@@ -41,23 +47,45 @@ __global__ __launch_bounds__(WR* WC * 64, 4) void dgemm_kernel(DgemmArgs a) {
   dgemm_tile_at<BM, BN, WR, WC, AKC, BKC, VEC>(a, tile, (long)blockIdx.y, kbeg, kend);
 }
 
-// `batch` products of one shape in ONE launch: the batch is folded into grid x (grid y and z stop at 65 535), block id ->
-// (item, tile), and the block runs dgemm_tile_at over the whole K on a copy of the arguments whose three pointers are
-// advanced to its item (block-uniform 64-bit values).  The 64 x 64 tile of eight waves, no k-slices: every output element
-// is one k-ascending chain of matrix instructions, the chain eg_dgemm gives it wherever that takes no slices, whatever
-// tile it picks.  remap (the launch's block count is a multiple of 8, gemm_plan.cpp): every XCD gets a contiguous range of
-// the launch's blocks, so the tiles of one item, which share its A rows and B columns, meet in one L2.
+// eg_dgemm_batched2: batch0 x batch1 products of one shape in ONE launch (an extent of 1 included): the items are the
+// item grid's (item_grid.hpp, item_launch.hpp) — folded into grid x, block id -> (outer, inner, tile) through
+// block_item, an operand a View in doubles — and the block runs dgemm_tile_at over the whole K on a copy of the arguments
+// whose three pointers are advanced to its item (block-uniform 64-bit values).  The 64 x 64 tile of eight waves, no
+// k-slices: every output element is one k-ascending chain of matrix instructions, the chain eg_dgemm gives it wherever
+// that takes no slices, whatever tile it picks — and whichever block of whichever launch computes it.
+// The members in the order of gemm_batched.hip's BatchedArgs.
 struct DgemmBatchedArgs {
-  DgemmArgs item;   // item 0 of the launch; splits = 1
-  long stride_a, stride_b, stride_c;   // doubles between consecutive items (0: the operand is shared)
-  int tiles;        // blocks per item
-  int remap;
+  eg::Items items;
+  eg::View a, b, c;   // doubles per row step and per step of the outer and the inner batch index (0: the operand is shared)
+  DgemmArgs item;     // item (0, 0) of the launch's range; splits = 1
 };
 
 constexpr int BT = 64;   // the batched tile, <BT, BT, 2, 4>
 
 template <bool AKC, bool BKC, bool VEC>
 __global__ __launch_bounds__(512, 4) void dgemm_batched_kernel(DgemmBatchedArgs b) {
+  const eg::BlockItem at = eg::block_item<true>(b.items);
+  DgemmArgs a = b.item;
+  a.A = eg::item_base(a.A, b.a, at.outer, at.inner);
+  a.B = eg::item_base(a.B, b.b, at.outer, at.inner);
+  a.C = eg::item_base(a.C, b.c, at.outer, at.inner);
+  dgemm_tile_at<BT, BT, 2, 4, AKC, BKC, VEC>(a, at.tile, 0, 0, a.K);
+}
+
+// One batch index (eg_dgemm_batched): the arguments and the block decode this launch had before the item grid.  Measured, the
+// item grid's arguments cost the one-index launch 0.5 - 0.9 us (profiles/dgemm_batched2.txt), more than repeated runs of it
+// differ by, so the entry keeps this kernel until that is gone: block id -> (item, tile) with three scalar strides; remap
+// (the launch's block count is a multiple of 8, dgemm_remap): every XCD gets a contiguous range of the launch's blocks.
+// The same tile body over the same k range as above: an item has the same bits through either kernel.
+struct DgemmBatched1Args {
+  DgemmArgs item;   // item 0 of the launch; splits = 1
+  long stride_a, stride_b, stride_c;   // doubles between consecutive items (0: the operand is shared)
+  int tiles;        // blocks per item
+  int remap;
+};
+
+template <bool AKC, bool BKC, bool VEC>
+__global__ __launch_bounds__(512, 4) void dgemm_batched1_kernel(DgemmBatched1Args b) {
   int work = (int)blockIdx.x;
   if (b.remap) {
     const int per = (int)(gridDim.x >> 3);
@@ -150,23 +178,30 @@ int launch_dgemm(eg_ctx* ctx, const DgemmPlan& p, const DgemmArgs& a, bool akc, 
   return rc;
 }
 
+// the kernel that takes `Args`: the item grid's (both entries' two-index form) or the one-index entry's own
 template <bool AKC, bool BKC, bool VEC>
-int launch_batched_one(eg_ctx* ctx, unsigned grid, const DgemmBatchedArgs& b) {
+constexpr auto batched_kernel(const DgemmBatchedArgs*) { return &dgemm_batched_kernel<AKC, BKC, VEC>; }
+template <bool AKC, bool BKC, bool VEC>
+constexpr auto batched_kernel(const DgemmBatched1Args*) { return &dgemm_batched1_kernel<AKC, BKC, VEC>; }
+
+template <bool AKC, bool BKC, bool VEC, class Args>
+int launch_batched_one(eg_ctx* ctx, unsigned grid, const Args& b) {
   using LA = TileLoader<BT, 512, AKC, VEC>;
   using LB = TileLoader<BT, 512, BKC, VEC>;
   constexpr size_t lds = (size_t)2 * (LA::LDS_DOUBLES + LB::LDS_DOUBLES) * sizeof(double);
-  static bool attr_set = false;
+  constexpr auto kernel = batched_kernel<AKC, BKC, VEC>(static_cast<const Args*>(nullptr));
+  static bool attr_set = false;   // (one per kernel: the function is instantiated per Args)
   if (!attr_set) {
-    EG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&dgemm_batched_kernel<AKC, BKC, VEC>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    EG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     attr_set = true;
   }
-  hipLaunchKernelGGL((dgemm_batched_kernel<AKC, BKC, VEC>), dim3(grid), dim3(512), lds, ctx->stream, b);
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(512), lds, ctx->stream, b);
   EG_HIP_CHECK(hipGetLastError());
   return EG_OK;
 }
 
-int launch_batched(eg_ctx* ctx, unsigned grid, const DgemmBatchedArgs& b, bool akc, bool bkc, bool vec) {
+template <class Args>
+int launch_batched(eg_ctx* ctx, unsigned grid, const Args& b, bool akc, bool bkc, bool vec) {
   int rc = EG_ERR_INVALID;
   eg::gemm::with_layout_vec(akc, bkc, vec, [&](auto ak, auto bk, auto v) { rc = launch_batched_one<ak, bk, v>(ctx, grid, b); });
   return rc;
@@ -264,10 +299,58 @@ int dgemm(eg_ctx* ctx, int trans_a, int trans_b, long M, long N, long K, const d
   return EG_OK;
 }
 
-// The one internal entry of the batched float64 product: eg_dgemm_batched and the model layer's batched launches
-// (host/run.cpp) both come here.  The one-launch side takes no workspace, so it may run under graph capture.  The loop
-// side is dgemm() per item: it takes the workspace wherever plan_dgemm slices the item (DgemmBatchedPlan::item says
-// whether and how much), which the model layer's eager run of a launch sequence sizes before the sequence is captured.
+namespace {
+
+// batch0 x batch1 items behind the entry `name`, whose checks have passed: the one launcher of both batched entries
+// (one_index: eg_dgemm_batched, batch1 == 1 and every view's stride1 unused).
+// The one-launch side takes no workspace, so it may run under graph capture.  The loop side is dgemm() per item: it takes
+// the workspace wherever plan_dgemm slices the item (DgemmBatchedPlan::item says whether and how much), which the model
+// layer's eager run of a launch sequence sizes before the sequence is captured.
+int launch_items(eg_ctx* ctx, const char* name, int trans_a, int trans_b, long batch0, long batch1, long M, long N, long K, const double* A,
+                 const eg::View& va, const double* B, const eg::View& vb, double* C, const eg::View& vc, int accumulate, const double* bias, bool one_index) {
+  int rc = eg::set_device(ctx);
+  if (rc) return rc;
+  DgemmBatchedProblem prob = {batch0, M, N, K, va.ld, vb.ld, va.stride0, vb.stride0, aligned16(A), aligned16(B), ctx->compute_units};
+  prob.batch1 = batch1, prob.stride_a1 = va.stride1, prob.stride_b1 = vb.stride1;
+  if (const char* e = eg::sw::text(eg::Sw::DGEMM_BATCHED_ROUTE)) prob.force = strcmp(e, "launch") == 0 ? 1 : strcmp(e, "loop") == 0 ? 2 : 0;
+  const DgemmBatchedPlan plan = plan_dgemm_batched(prob);
+  auto at = [](auto* p, const eg::View& v, long o, long i) { return p ? p + o * v.stride0 + i * v.stride1 : p; };
+  if (plan.loop) {   // every item fills the chip by itself: plain products on their own routes
+    for (long o = 0; o < batch0; ++o)
+      for (long i = 0; i < batch1; ++i) {
+        rc = dgemm(ctx, trans_a, trans_b, M, N, K, at(A, va, o, i), va.ld, at(B, vb, o, i), vb.ld, at(C, vc, o, i), vc.ld, accumulate, bias);
+        if (rc) return rc;
+      }
+    return EG_OK;
+  }
+  EG_REQUIRE(plan.tiles > 0 && plan.tiles <= BATCHED_MAX_BLOCKS, EG_ERR_INVALID, "%s: an item has too many tiles for one launch", name);
+  const bool akc = !trans_a, bkc = trans_b != 0;
+  if (one_index) {   // eg_dgemm_batched: its own kernel (above), the launches of the same cut; no 32-bit limit on the batch
+    for (long n = 0; n < plan.launches; ++n) {
+      const DgemmBatchedLaunch l = dgemm_batched_launch(plan, batch0, n);
+      EG_REQUIRE(l.items > 0 && l.grid > 0 && l.grid <= BATCHED_MAX_BLOCKS, EG_ERR_INVALID, "%s: launch out of range", name);
+      const DgemmArgs item = dgemm_args(at(A, va, l.first, 0), va.ld, at(B, vb, l.first, 0), vb.ld, at(C, vc, l.first, 0), vc.ld, bias, M, N, K, accumulate,
+                                        1, dgemm_k_unsliced(K), plan.tiles_m, plan.tiles_n, false);
+      const DgemmBatched1Args args = {item, va.stride0, vb.stride0, vc.stride0, (int)plan.tiles, l.remap ? 1 : 0};
+      rc = launch_batched(ctx, (unsigned)l.grid, args, akc, bkc, plan.vec);
+      if (rc) return rc;
+    }
+    return EG_OK;
+  }
+  // two batch indices: both extents are below 2^31 (dgemm_batched2 checks), which the kernel's 32-bit item decode relies on
+  const long items = batch0 * batch1;
+  DgemmBatchedArgs args = {};
+  args.item = dgemm_args(A, va.ld, B, vb.ld, C, vc.ld, bias, M, N, K, accumulate, 1, dgemm_k_unsliced(K), plan.tiles_m, plan.tiles_n, false);
+  args.a = va, args.b = vb, args.c = vc;
+  return eg::for_each_launch(name, items, eg::cut_items(items, plan.tiles), batch1, [&](const eg::Items& it, unsigned grid) {
+    args.items = it;
+    return launch_batched(ctx, grid, args, akc, bkc, plan.vec);
+  });
+}
+
+}  // namespace
+
+// The internal entry of one batch index: eg_dgemm_batched and the model layer's launches with one batch index come here.
 int dgemm_batched(eg_ctx* ctx, int trans_a, int trans_b, long batch, long M, long N, long K, const double* A, long lda, long stride_a,
                   const double* B, long ldb, long stride_b, double* C, long ldc, long stride_c, int accumulate, const double* bias) {
   bool empty = false;
@@ -275,32 +358,37 @@ int dgemm_batched(eg_ctx* ctx, int trans_a, int trans_b, long batch, long M, lon
   if (rc || empty) return rc;
   EG_REQUIRE(stride_a >= 0 && stride_b >= 0, EG_ERR_INVALID, "eg_dgemm_batched: negative stride");
   EG_REQUIRE(batch == 1 || stride_c >= (M - 1) * ldc + N, EG_ERR_INVALID, "eg_dgemm_batched: stride_c makes the items of C overlap");
-  rc = eg::set_device(ctx);
-  if (rc) return rc;
+  return launch_items(ctx, "eg_dgemm_batched", trans_a, trans_b, batch, 1, M, N, K, A, {lda, stride_a, 0}, B, {ldb, stride_b, 0}, C,
+                      {ldc, stride_c, 0}, accumulate, bias, true);
+}
 
-  DgemmBatchedProblem prob = {batch, M, N, K, lda, ldb, stride_a, stride_b, aligned16(A), aligned16(B), ctx->compute_units};
-  if (const char* e = eg::sw::text(eg::Sw::DGEMM_BATCHED_ROUTE)) prob.force = strcmp(e, "launch") == 0 ? 1 : strcmp(e, "loop") == 0 ? 2 : 0;
-  const DgemmBatchedPlan plan = plan_dgemm_batched(prob);
-  if (plan.loop) {   // every item fills the chip by itself: plain products on their own routes
-    for (long b = 0; b < batch; ++b) {
-      rc = dgemm(ctx, trans_a, trans_b, M, N, K, A ? A + b * stride_a : A, lda, B ? B + b * stride_b : B, ldb, C + b * stride_c, ldc, accumulate,
-                 bias);
-      if (rc) return rc;
-    }
-    return EG_OK;
-  }
-  EG_REQUIRE(plan.tiles > 0 && plan.tiles <= BATCHED_MAX_BLOCKS, EG_ERR_INVALID, "eg_dgemm_batched: an item has too many tiles for one launch");
-  const bool akc = !trans_a, bkc = trans_b != 0;
-  for (long i = 0; i < plan.launches; ++i) {
-    const DgemmBatchedLaunch l = dgemm_batched_launch(plan, batch, i);
-    EG_REQUIRE(l.items > 0 && l.grid > 0 && l.grid <= BATCHED_MAX_BLOCKS, EG_ERR_INVALID, "eg_dgemm_batched: launch out of range");
-    const DgemmArgs item = dgemm_args(A ? A + l.first * stride_a : A, lda, B ? B + l.first * stride_b : B, ldb, C + l.first * stride_c, ldc, bias, M, N, K,
-                                      accumulate, 1, dgemm_k_unsliced(K), plan.tiles_m, plan.tiles_n, false);
-    const DgemmBatchedArgs args = {item, stride_a, stride_b, stride_c, (int)plan.tiles, l.remap ? 1 : 0};
-    rc = launch_batched(ctx, (unsigned)l.grid, args, akc, bkc, plan.vec);
-    if (rc) return rc;
-  }
-  return EG_OK;
+// The internal entry of two batch indices: eg_dgemm_batched2 comes here.  The conventions of sgemm_batched2 (gemm_batched.hip).
+int dgemm_batched2(eg_ctx* ctx, int trans_a, int trans_b, long batch0, long batch1, long M, long N, long K, const double* A, long lda,
+                   long stride_a0, long stride_a1, const double* B, long ldb, long stride_b0, long stride_b1, double* C, long ldc, long stride_c0,
+                   long stride_c1, int accumulate, const double* bias) {
+  EG_REQUIRE(ctx, EG_ERR_INVALID, "eg_dgemm_batched2: ctx is NULL");
+  EG_REQUIRE(batch0 >= 0 && batch1 >= 0 && M >= 0 && N >= 0 && K >= 0, EG_ERR_INVALID, "eg_dgemm_batched2: negative extent");
+  EG_REQUIRE(batch0 < (1L << 31) && batch1 < (1L << 31), EG_ERR_INVALID, "eg_dgemm_batched2: a batch extent of 2^31 or more");
+  if (batch0 == 0 || batch1 == 0 || M == 0 || N == 0) return EG_OK;
+  EG_REQUIRE(C, EG_ERR_INVALID, "eg_dgemm_batched2: C is NULL");
+  EG_REQUIRE(K == 0 || (A && B), EG_ERR_INVALID, "eg_dgemm_batched2: NULL operand");
+  EG_REQUIRE(lda >= (trans_a ? M : K) && ldb >= (trans_b ? K : N), EG_ERR_INVALID,
+             "eg_dgemm_batched2: leading dimension smaller than the row length");
+  EG_REQUIRE(stride_a0 >= 0 && stride_a1 >= 0 && stride_b0 >= 0 && stride_b1 >= 0, EG_ERR_INVALID, "eg_dgemm_batched2: negative stride");
+  EG_REQUIRE(batched2_c_distinct(batch0, stride_c0, batch1, stride_c1, M, ldc, N), EG_ERR_INVALID,
+             "eg_dgemm_batched2: ldc, stride_c0 and stride_c1 make elements of C share an address");
+  if (M == 1 && ldc < N) ldc = N;   // a single row: ldc addresses nothing, and the plain product insists on ldc >= N
+  return launch_items(ctx, "eg_dgemm_batched2", trans_a, trans_b, batch0, batch1, M, N, K, A, {lda, stride_a0, stride_a1}, B,
+                      {ldb, stride_b0, stride_b1}, C, {ldc, stride_c0, stride_c1}, accumulate, bias, false);
+}
+
+// The model layer's batched launches (host/run.cpp): batch1 == 0 is a product with one batch index, its strides each view's stride0.
+int dgemm_batched_views(eg_ctx* ctx, int trans_a, int trans_b, long batch0, long batch1, long M, long N, long K, const double* A, const View& a,
+                        const double* B, const View& b, double* C, const View& c, int accumulate, const double* bias) {
+  if (batch1 > 0)
+    return dgemm_batched2(ctx, trans_a, trans_b, batch0, batch1, M, N, K, A, a.ld, a.stride0, a.stride1, B, b.ld, b.stride0, b.stride1, C, c.ld,
+                          c.stride0, c.stride1, accumulate, bias);
+  return dgemm_batched(ctx, trans_a, trans_b, batch0, M, N, K, A, a.ld, a.stride0, B, b.ld, b.stride0, C, c.ld, c.stride0, accumulate, bias);
 }
 
 }  // namespace gemm
@@ -316,6 +404,13 @@ extern "C" int eg_dgemm_batched(eg_ctx* ctx, int trans_a, int trans_b, int64_t b
                                 int64_t stride_c, int accumulate, const double* bias) {
   return eg::gemm::dgemm_batched(ctx, trans_a, trans_b, batch, M, N, K, A, lda, stride_a, B, ldb, stride_b, C, ldc, stride_c, accumulate,
                                  bias);
+}
+
+extern "C" int eg_dgemm_batched2(eg_ctx* ctx, int trans_a, int trans_b, int64_t batch0, int64_t batch1, int64_t M, int64_t N, int64_t K,
+                                 const double* A, int64_t lda, int64_t stride_a0, int64_t stride_a1, const double* B, int64_t ldb, int64_t stride_b0,
+                                 int64_t stride_b1, double* C, int64_t ldc, int64_t stride_c0, int64_t stride_c1, int accumulate, const double* bias) {
+  return eg::gemm::dgemm_batched2(ctx, trans_a, trans_b, batch0, batch1, M, N, K, A, lda, stride_a0, stride_a1, B, ldb, stride_b0, stride_b1, C, ldc,
+                                  stride_c0, stride_c1, accumulate, bias);
 }
 
 extern "C" int eg_fill_f64(eg_ctx* ctx, int64_t n, double value, double* out) {

@@ -80,6 +80,13 @@ int dgemm(eg_ctx* ctx, int trans_a, int trans_b, long M, long N, long K, const d
           long ldc, int accumulate, const double* bias);
 int dgemm_batched(eg_ctx* ctx, int trans_a, int trans_b, long batch, long M, long N, long K, const double* A, long lda, long stride_a,
                   const double* B, long ldb, long stride_b, double* C, long ldc, long stride_c, int accumulate, const double* bias);
+// batch0 x batch1 of them by the same tile body and launcher, on the item grid (what eg_dgemm_batched2 runs), and either entry with an operand as
+// its View, the float64 model layer's one call: batch1 == 0 is dgemm_batched, batch1 > 0 is dgemm_batched2.
+int dgemm_batched2(eg_ctx* ctx, int trans_a, int trans_b, long batch0, long batch1, long M, long N, long K, const double* A, long lda,
+                   long stride_a0, long stride_a1, const double* B, long ldb, long stride_b0, long stride_b1, double* C, long ldc, long stride_c0,
+                   long stride_c1, int accumulate, const double* bias);
+int dgemm_batched_views(eg_ctx* ctx, int trans_a, int trans_b, long batch0, long batch1, long M, long N, long K, const double* A, const View& a,
+                        const double* B, const View& b, double* C, const View& c, int accumulate, const double* bias);
 // The planner's switches as the exact product reads them (gemm_plan.hpp; gemm_f32_mfma.hip keeps them per thread).
 struct GemmSwitches;
 const GemmSwitches& current_switches();

@@ -727,8 +727,9 @@ DgemmPlan plan_dgemm(const DgemmProblem& p) {
 }
 
 bool dgemm_batched_vec(const DgemmBatchedProblem& p) {
-  const bool strides_even = p.batch <= 1 || (p.stride_a % 2 == 0 && p.stride_b % 2 == 0);
-  return dgemm_vec(p.lda, p.ldb, p.a_aligned, p.b_aligned) && strides_even;
+  const bool outer_even = p.batch <= 1 || (p.stride_a % 2 == 0 && p.stride_b % 2 == 0);
+  const bool inner_even = p.batch1 <= 1 || (p.stride_a1 % 2 == 0 && p.stride_b1 % 2 == 0);
+  return dgemm_vec(p.lda, p.ldb, p.a_aligned, p.b_aligned) && outer_even && inner_even;
 }
 
 // The rule: an item whose 64 x 64 tiles number at least DGEMM_LOOP_TILES_PER_CU per CU runs as a plain product — it
@@ -759,11 +760,11 @@ DgemmBatchedPlan plan_dgemm_batched(const DgemmBatchedProblem& p) {
     r.item = plan_dgemm({p.M, p.N, p.K, p.lda, p.ldb, p.a_aligned, p.b_aligned, p.cus});
     return r;
   }
-  if (p.batch <= 0 || p.M <= 0 || p.N <= 0) return r;
+  if (p.batch <= 0 || p.batch1 <= 0 || p.M <= 0 || p.N <= 0) return r;
   r.vec = dgemm_batched_vec(p);
   r.tiles_m = (int)((p.M + T - 1) / T);
   r.tiles_n = (int)((p.N + T - 1) / T);
-  const Cut c = cut_items(p.batch, (long)r.tiles_m * r.tiles_n);
+  const Cut c = cut_items(p.batch * p.batch1, (long)r.tiles_m * r.tiles_n);
   r.tiles = c.tiles, r.items_per_launch = c.items_per_launch, r.launches = c.launches;
   return r;
 }

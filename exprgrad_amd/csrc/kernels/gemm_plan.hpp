@@ -162,17 +162,19 @@ inline long dgemm_k_unsliced(long K) {
 
 DgemmPlan plan_dgemm(const DgemmProblem& p);
 
-// ---- float64: `batch` products of one shape (gemm_f64_mfma.hip, dgemm_batched_kernel) ---------------------------------
+// ---- float64: batch x batch1 products of one shape (gemm_f64_mfma.hip, dgemm_batched_kernel) --------------------------
 using eg::BATCHED_MAX_BLOCKS;   // blocks of one batched launch, float32 and float64 (item_grid.hpp)
 constexpr int DGEMM_BATCHED_TILE = 64;   // the one tile the batched float64 kernel is built for
 
-// One call as the planner sees it.  Leading dimensions and strides in doubles; a stride of 0 shares the operand.
+// One call as the planner sees it: eg_dgemm_batched (batch items) or eg_dgemm_batched2 (batch x batch1 items, `batch` the
+// outer index).  Leading dimensions and strides in doubles; a stride of 0 shares the operand.
 struct DgemmBatchedProblem {
   long batch = 0, M = 0, N = 0, K = 0;
-  long lda = 0, ldb = 0, stride_a = 0, stride_b = 0;
-  bool a_aligned = true, b_aligned = true;   // 16-byte aligned base pointers of item 0
+  long lda = 0, ldb = 0, stride_a = 0, stride_b = 0;   // the strides of the outer (or only) batch index
+  bool a_aligned = true, b_aligned = true;   // 16-byte aligned base pointers of item (0, 0)
   int cus = 256;
   int force = 0;   // EG_DGEMM_BATCHED_ROUTE (measurement aid), set by the caller: 1 one launch, 2 the loop
+  long batch1 = 1, stride_a1 = 0, stride_b1 = 0;   // the inner batch index and its strides (one batch index: extent 1)
 };
 
 struct DgemmBatchedPlan {
@@ -182,19 +184,23 @@ struct DgemmBatchedPlan {
   DgemmPlan item;
   bool vec = false;    // 16-byte loads (dgemm_batched_vec)
   int tiles_m = 0, tiles_n = 0;
-  long tiles = 0;             // blocks per item
-  long items_per_launch = 0;  // BATCHED_MAX_BLOCKS / tiles
-  long launches = 0;
+  long tiles = 0;             // blocks per item            } cut_items(batch * batch1, tiles) of the item grid
+  long items_per_launch = 0;  // BATCHED_MAX_BLOCKS / tiles  } (item_grid.hpp): the launches cut the flattened
+  long launches = 0;          //                             } (outer, inner) range, outer-major
 };
 
-// Launch `index` of a plan: items [first, first + items), grid = items x tiles blocks.  remap: dgemm_remap of the grid.
+// Launch `index` of a plan over `batch` items in all (batch x batch1 of the problem): items [first, first + items) of the
+// flattened range, grid = items x tiles blocks — plan_launch of the item grid.  The one-index entry launches from this
+// (dgemm_batched1_kernel, which takes `remap`: dgemm_remap of the grid); the two-index entry goes through for_each_launch
+// over the same cut, and its kernel's xcd_remap is a permutation of every grid, so it asks for no such flag.
 struct DgemmBatchedLaunch {
   long first = 0, items = 0, grid = 0;
   bool remap = false;
 };
 
-// 16-byte loads: dgemm_vec of item 0, and every further item 16-byte aligned as well (stride_a, stride_b even wherever the
-// batch has a second item; a shared operand's stride of 0 is even).  Anything else: 8-byte loads.
+// 16-byte loads: dgemm_vec of item (0, 0), and every further item 16-byte aligned as well: for A and for B, the stride of
+// each batch index is even wherever that index has a second value (an index of extent 1 never applies its stride; a shared
+// operand's stride of 0 is even).  Anything else: 8-byte loads.
 bool dgemm_batched_vec(const DgemmBatchedProblem& p);
 
 // Does one item fill the chip by itself?  Then the batch runs as a loop of plain float64 products, each on its own route

@@ -1,6 +1,6 @@
 // The item grid: many items of one shape, `tiles` blocks per item, cut into launches of at most BATCHED_MAX_BLOCKS blocks.
-// The one description that the batched products (gemm_batched.hip, gemm_f64_mfma.hip through gemm_plan.cpp) and the attention
-// kernels (attention_plan.hpp) share.  Plain C++ (no HIP, no unit of its own): item_launch.hpp has the kernels' side and
+// The one description that the batched products, float32 and float64, over one batch index and over two (gemm_batched.hip;
+// gemm_f64_mfma.hip, planned in gemm_plan.cpp) and the attention kernels (attention_plan.hpp) share.  Plain C++ (no HIP, no unit of its own): item_launch.hpp has the kernels' side and
 // the launch loop.
 #pragma once
 
@@ -11,7 +11,7 @@ namespace eg {
 // Blocks of one launch, float32 and float64: grid x block threads stays below 2^32 and the block id an int.
 constexpr long BATCHED_MAX_BLOCKS = 1L << 22;
 
-// One item's view of an operand, the one description from the model's plan to the kernels' arguments: floats per row step
+// One item's view of an operand, the one description from the model's plan to the kernels' arguments: elements per row step
 // and per step of the outer and the inner batch index.  The attention row sums have no rows to step over: their ld is unused (0).
 struct View {
   long ld = 0, stride0 = 0, stride1 = 0;

@@ -133,6 +133,13 @@ class Model:
         Off by default; part of the plan key, so turning it off returns to the plans made before."""
         call("eg_model_fuse_attention_fit", self.handle, 1 if on else 0)
 
+    def batched2_f64(self, on=True):
+        """A float64 model's products with two batch indices (the multi-head scores and context products and their gradients)
+        run as eg_bgemm2 launches on the float64 matrix instruction (eg_dgemm_batched2's kernel) instead of generated kernels.
+        Off by default; an error on a float32 model, whose products take the route already.  Toggling lowers the model again:
+        the next run plans, and a captured step captures, anew."""
+        call("eg_model_batched2_f64", self.handle, 1 if on else 0)
+
     def set_seed(self, seed):
         """Seed of the model's random tensors (`rand`, dropout masks); the reference uses Nim's global
         generator (`randomize(seed)`)."""

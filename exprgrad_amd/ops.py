@@ -83,6 +83,15 @@ def dgemm_batched(ctx, batch, M, N, K, A, lda, stride_a, B, ldb, stride_b, C, ld
          _p(C), ldc, stride_c, int(accumulate), _p(bias))
 
 
+def dgemm_batched2(ctx, batch0, batch1, M, N, K, A, lda, strides_a, B, ldb, strides_b, C, ldc, strides_c, trans_a=False, trans_b=False,
+                   accumulate=False, bias=None):
+    """The float64 form of sgemm_batched2: item (o, i) uses X + o * strides_x[0] + i * strides_x[1] (pairs of strides, and
+    leading dimensions, in doubles; a 0 in strides_a / strides_b shares the operand along that index; the items of C may
+    interleave but not overlap)."""
+    call("eg_dgemm_batched2", ctx.handle, int(trans_a), int(trans_b), batch0, batch1, M, N, K, _p(A), lda, strides_a[0], strides_a[1],
+         _p(B), ldb, strides_b[0], strides_b[1], _p(C), ldc, strides_c[0], strides_c[1], int(accumulate), _p(bias))
+
+
 def bias_add(ctx, rows, cols, bias, out, accumulate=True):
     call("eg_bias_add", ctx.handle, rows, cols, _p(bias), _p(out), int(accumulate))
 

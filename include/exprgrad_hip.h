@@ -390,6 +390,35 @@ int eg_dgemm(eg_ctx* ctx, int trans_a, int trans_b, int64_t M, int64_t N, int64_
 int eg_dgemm_batched(eg_ctx* ctx, int trans_a, int trans_b, int64_t batch, int64_t M, int64_t N, int64_t K,
                      const double* A, int64_t lda, int64_t stride_a, const double* B, int64_t ldb, int64_t stride_b,
                      double* C, int64_t ldc, int64_t stride_c, int accumulate, const double* bias);
+/* eg_dgemm_batched2: the float64 form of eg_sgemm_batched2, with its conventions word for word.
+ *   C_{o,i}[m,n] (+)= sum_k opA_{o,i}(m,k) * opB_{o,i}(k,n) (+ bias[n])   for o in [0, batch0), i in [0, batch1),
+ *   X_{o,i} = X + o * stride_x0 + i * stride_x1, leading dimensions and strides in doubles.
+ * The multi-head products of a compile[float64] program: s[b,h,i,j] ++= q[b,i,h,k] * kk[b,j,h,k] is trans_b = 1 with
+ * lda = ldb = H * K and stride_a1 = stride_b1 = K; o[b,i,h,d] ++= p[b,h,i,j] * v[b,j,h,d] writes a C whose items interleave
+ * (ldc = H * D, stride_c1 = D).  No alignment is required, elements of A and B outside an item's view are never read,
+ * elements of C outside the items are never written, C is not read when accumulate == 0, K == 0 writes bias or zeros,
+ * batch0 == 0, batch1 == 0 and empty products succeed and launch nothing.
+ * Strides of A and B: each of the four may be 0 (the operand is shared along that index).  C must not alias itself, and
+ * that is the only rule for ldc, stride_c0 and stride_c1: the rule of eg_sgemm_batched2's C (interleaved items are
+ * accepted, every tie and every 0 is refused; with M == 1, ldc addresses nothing and may be below N).
+ * EG_ERR_INVALID, with a message that names eg_dgemm_batched2: a NULL ctx, a negative extent, a batch extent of 2^31 or
+ * more, a NULL C or a NULL A or B with K > 0 of a non-empty call, lda or ldb shorter than a row, a negative stride of A or
+ * B, a C whose elements share an address.
+ * 16-byte loads are taken when eg_dgemm would take them for item (0, 0) (lda and ldb even, A and B 16-byte aligned) and,
+ * for A and for B, both batch strides are even wherever that index has extent above 1 (0 is even); 8-byte loads otherwise.
+ * One launch of batch0 x batch1 x tiles blocks on 64 x 64 tiles (kernels/gemm_f64_mfma.hip: eg_dgemm_batched's tile body and
+ * launcher, the items on the item grid), split along the flattened (o, i) range when it would exceed 2^22 blocks; items that fill the
+ * chip by themselves run as a loop of plain float64 products, as for eg_dgemm_batched.  The one-launch route takes no
+ * k-slices, no workspace and no atomics: every output element is one k-ascending chain of `v_mfma_f64_16x16x4_f64`.  Bits:
+ *   - item (o, i) has the bits of an eg_dgemm_batched call with batch 1 on its three pointers;
+ *   - with stride_x0 == batch1 * stride_x1 for all three operands, the call has the bits of eg_dgemm_batched with
+ *     batch = batch0 * batch1. */
+int eg_dgemm_batched2(eg_ctx* ctx, int trans_a, int trans_b, int64_t batch0, int64_t batch1,
+                      int64_t M, int64_t N, int64_t K,
+                      const double* A, int64_t lda, int64_t stride_a0, int64_t stride_a1,
+                      const double* B, int64_t ldb, int64_t stride_b0, int64_t stride_b1,
+                      double* C, int64_t ldc, int64_t stride_c0, int64_t stride_c1,
+                      int accumulate, const double* bias);
 /* eg_conv2_nhwc_f64 and its two gradients: the float64 forms of eg_conv2_nhwc, eg_conv2_nhwc_grad_filter and
  * eg_conv2_nhwc_grad_image, with their formulas, layouts, argument checks, error codes and empty-extent behaviour word for
  * word: EG_ERR_INVALID for a NULL ctx, a bad extent or a NULL tensor of a non-empty call, EG_ERR_SHAPE for a filter
@@ -532,6 +561,16 @@ int eg_model_keep_values(eg_model* model, int on);
  * it.  A NULL model is EG_ERR_INVALID.  The setting is part of the plan key; the default is off, and with it off every
  * plan, launch and bit is what it was. */
 int eg_model_fuse_attention_fit(eg_model* model, int on);
+/* The multi-head products of a compile[float64] model on the float64 matrix instruction.  on != 0: from the next run on,
+ * every kernel of the model that is a product with two batch indices (what a float32 model runs as eg_bgemm2: the scores
+ * and context products and the four gradients derived from them) and whose shapes suit runs as one eg_bgemm2 launch —
+ * eg_dgemm_batched2's internal entry — instead of the generated kernel with one work-item per output element; what the
+ * shapes decline (an empty extent, operands that are not rank 4) and every other kernel keeps the generated `double` code,
+ * and EG_NO_BATCHED_GEMM=1 turns the route off as it does for float32.  Toggling lowers the model's targets again: the
+ * plans made so far are dropped, the next run plans (and a captured step captures) again, and eg_model_plan_text names
+ * the launches of the setting; if lowering fails, the error is returned and the model keeps the setting it had.  EG_ERR_INVALID: a NULL model, a float32 model (its products take the route already).
+ * The default is off, and with it off every plan, launch and bit is what it was. */
+int eg_model_batched2_f64(eg_model* model, int on);
 
 /* Model.epoch (model.nim:39, bumped by fit at model.nim:436). */
 int eg_model_set_epoch(eg_model* model, int64_t epoch);

@@ -35,6 +35,7 @@ proc eg_model_param_read(model: ptr EgModel, tensor: cint, host: ptr float32, co
 proc eg_model_set_epoch(model: ptr EgModel, epoch: int64): cint
 proc eg_model_epoch(model: ptr EgModel): int64
 proc eg_model_keep_values(model: ptr EgModel, on: cint): cint
+proc eg_model_batched2_f64(model: ptr EgModel, on: cint): cint
 proc eg_model_plan_text(model: ptr EgModel): cstring
 proc eg_model_launch_text(model: ptr EgModel, target: cstring): cstring
 proc eg_model_state_bytes(model: ptr EgModel, bytes: ptr csize_t): cint
@@ -395,7 +396,7 @@ proc toKd*(source: Program): string =
   ## (model.nim:232-236).  The passes that only normalise — makeTensorLookups, deadCodeElim, foldLinearIndices,
   ## deduplicateReads (model.nim:47-50) — run here on a clone; generate and everything after it is the library's job.
   # the scalar type (Scalar32 / Scalar64, ir.nim; set by compile[T] through toScalarType, model.nim:253-260) is the header's
-  # third word: a float64 program runs on eg_dgemm + generated kernels over double
+  # third word: a float64 program runs on eg_dgemm / eg_dgemm_batched (eg_dgemm_batched2 under batched2F64) + generated kernels over double
   let program = source.clone()
   program.makeTensorLookups()
   program.deadCodeElim()
@@ -562,6 +563,11 @@ proc keepValues*[T](model: HipModel[T], on = true) =
   ## Plans keep the values of every result tensor (the reference's own behaviour: every kernel's output is a tensor,
   ## model.nim:295-300) instead of, where all readers allow it, one predicate bit per element — for debugging
   check eg_model_keep_values(model.handle, cint(ord(on)))
+proc batched2F64*[T](model: HipModel[T], on = true) =
+  ## A float64 model's products with two batch indices (the multi-head scores and context products and their gradients) run
+  ## as eg_bgemm2 launches on the float64 matrix instruction (eg_dgemm_batched2's kernel) instead of generated kernels; off
+  ## by default, an error for a HipModel[float32]
+  check eg_model_batched2_f64(model.handle, cint(ord(on)))
 proc emitIr*[T](model: HipModel[T]): string = $eg_model_plan_text(model.handle)                    # model.nim:262-264
 proc launches*[T](model: HipModel[T], target: string): string = $eg_model_launch_text(model.handle, target.cstring)
 
