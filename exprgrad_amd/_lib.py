@@ -81,6 +81,9 @@ _SIGS = {
                           [c_int, c_void_p, c_i64, c_i64]),
     "eg_attention_grad": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_f32] + [c_void_p, c_i64, c_i64, c_i64] * 4 +
                           [c_void_p, c_i64, c_i64] + [c_void_p, c_i64, c_i64, c_i64] * 4 + [c_int]),
+    "eg_attention_f64": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_f64] + [c_void_p, c_i64, c_i64, c_i64] * 4 + [c_int]),
+    "eg_attention_sums_f64": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_f64] + [c_void_p, c_i64, c_i64, c_i64] * 4 +
+                              [c_int, c_void_p, c_i64, c_i64]),
     "eg_bias_add": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_int]),
     "eg_colsum": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_int]),
     "eg_rowsum": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_int]),
@@ -100,6 +103,7 @@ _SIGS = {
     "eg_model_keep_values": (c_int, [c_void_p, c_int]),
     "eg_model_fuse_attention_fit": (c_int, [c_void_p, c_int]),
     "eg_model_batched2_f64": (c_int, [c_void_p, c_int]),
+    "eg_model_fuse_attention_f64": (c_int, [c_void_p, c_int]),
     "eg_fill_uniform": (c_int, [c_void_p, c_i64, ctypes.c_float, ctypes.c_float, c_void_p, ctypes.c_uint64, c_void_p]),
     "eg_rng_advance": (c_int, [c_void_p, c_void_p]),
     "eg_model_kernel_count": (c_int, [c_void_p, c_char_p]),

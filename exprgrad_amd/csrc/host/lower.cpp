@@ -324,7 +324,8 @@ void describe(eg_model* m) {
     os << "target " << kv.first << " (" << ts.target->live.size() << " kernels)\n";
     // forward attention chains (match_attention): one eg_attn launch when the plan fuses them (plan_attention.cpp)
     std::vector<std::pair<int, int>> attn(ts.lowered.size(), {-1, -1});
-    for (int p = 0; !m->prog.f64 && p < (int)ts.lowered.size(); ++p) {
+    // (a float64 model: where it asks for them, eg_model_fuse_attention_f64)
+    for (int p = 0; (!m->prog.f64 || m->fuse_attention_f64) && p < (int)ts.lowered.size(); ++p) {
       AttentionMatch am;
       if (!match_attention(m->prog, *ts.target, p, am)) continue;
       for (int s = p; s < p + am.n; ++s) attn[s] = {p, p + am.n - 1};

@@ -61,6 +61,7 @@ struct AttentionMatch {
   int n = 0;                           // kernels of the chain: 5 with a scale map, 4 without
   std::vector<int> at;                 // their live positions: p, p + 1, ... (match_attention_chain with gaps: ascending)
   float scale = 1.f;
+  double scale_f64 = 1.0;              // the literal as written: what a float64 model multiplies by
   Batched2GemmMatch scores, context;   // of kernels [0] and [n - 1]
   int t_scores = 0, t_scaled = 0, t_sums = 0, t_softmax = 0;   // t_scaled: 0 without a scale map
   int t_q = 0, t_k = 0, t_v = 0, t_out = 0;

@@ -102,6 +102,7 @@ bool match_attention_chain(const Target& t, int p, AttentionMatch& out, const ch
       if (!((mul->args[0] == x && mul->args[1] == lit->res) || (mul->args[1] == x && mul->args[0] == lit->res)))
         return fail(why, "the scale is not one multiplication by a literal");
       m.scale = (float)lit->lit;
+      m.scale_f64 = lit->lit;
       m.t_scaled = k.write.tensor;
       e = m.t_scaled;
       m.at.push_back(at);

@@ -303,7 +303,7 @@ const char* eg_model_launch_text(eg_model* m, const char* target) {
         };
         char scale[32];
         const Launch::Attn& A = L.attn;
-        snprintf(scale, sizeof(scale), "%g", (double)A.scale);
+        snprintf(scale, sizeof(scale), "%g", m->f64 ? A.scale_f64 : (double)A.scale);
         os << (grad ? "eg_attn_grad " : "eg_attn ") << A.e.batch0 << "x" << A.e.batch1 << " x " << A.e.I << "x" << A.e.J << "x" << A.e.K << "x" << A.e.D << " scale=" << scale << " (";
         for (size_t ki = 0; ki < A.members.size(); ++ki) {
           const int wt = ts.target->all[ts.target->live[A.members[ki]]].write.tensor;
@@ -813,6 +813,18 @@ int eg_model_fuse_attention_fit(eg_model* m, int on) try {
   EG_REQUIRE(m, EG_ERR_INVALID, "NULL model");
   if (m->fuse_attention_fit != (on != 0)) {
     m->fuse_attention_fit = on != 0;
+    m->inputs_gen++;  // the plan key changes: the next run looks its plan up again
+    describe(m);      // eg_model_plan_text names the launches the setting asks for
+  }
+  return EG_OK;
+}
+EG_CATCH_ALL
+
+int eg_model_fuse_attention_f64(eg_model* m, int on) try {
+  EG_REQUIRE(m, EG_ERR_INVALID, "eg_model_fuse_attention_f64: NULL model");
+  EG_REQUIRE(m->f64, EG_ERR_INVALID, "eg_model_fuse_attention_f64: a float32 model (its forward attention chains are eg_attn launches already)");
+  if (m->fuse_attention_f64 != (on != 0)) {
+    m->fuse_attention_f64 = on != 0;
     m->inputs_gen++;  // the plan key changes: the next run looks its plan up again
     describe(m);      // eg_model_plan_text names the launches the setting asks for
   }

@@ -103,6 +103,7 @@ struct Launch {
     };
     eg::attention::Extents e;
     float scale = 1.f;
+    double scale_f64 = 1.0;          // a float64 model: the scale literal without loss
     Operand q, k, v, o;              // o: the context
     Operand sums;                    // a fit group: the row sums, one dense row of I floats per item (tensor != 0)
     Operand dout, dq, dk, dv;        // AttentionGrad: the context's gradient and the three outputs
@@ -317,6 +318,7 @@ struct eg_model {
   int esz = 1;
   bool keep_values = false;  // eg_model_keep_values: plans keep result values where they would keep predicate bits
   bool fuse_attention_fit = false;  // eg_model_fuse_attention_fit: training steps over an attention chain run on the fused pair
+  bool fuse_attention_f64 = false;  // eg_model_fuse_attention_f64: a float64 model's forward attention chains run as one eg_attn launch each
   bool batched2_f64 = false;  // eg_model_batched2_f64: a float64 model's products with two batch indices run as eg_bgemm2 launches
   uint64_t inputs_gen = 0;  // bumped by every change of `inputs` (bind, clear, fit): caches keyed on the bindings compare it
   float grad_scale = 1.0f;

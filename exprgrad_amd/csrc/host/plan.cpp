@@ -212,6 +212,7 @@ std::string shape_key(eg_model* m) {
   if (m->keep_values) os << "v";
   if (m->fuse_attention_fit) os << "a";
   if (m->batched2_f64) os << "d";
+  if (m->fuse_attention_f64) os << "f";
   return os.str();
 }
 
@@ -396,6 +397,17 @@ int make_plan(eg_model* m, TargetState& ts, Plan& plan) {
     if (rc) return rc;
     rc = form_sample_group(m, ts, plan, infos, first_writer, group_of, needs_zero);
     if (rc) return rc;
+  }
+  if (!fuse) {
+    plan.attn_groups.clear();
+    plan.attn_grad_groups.clear();
+    plan.attn_hidden.clear();
+    // float64: the one group there is — a forward attention chain as one launch, where the model asks for it
+    // (eg_model_fuse_attention_f64); form_attention_groups has the conditions
+    if (m->fuse_attention_f64) {
+      int rc = form_attention_groups(m, ts, plan, infos, first_writer, group_of);
+      if (rc) return rc;
+    }
   }
   int rc_groups = fuse ? form_row_groups(m, ts, plan, infos, first_writer, group_of) : EG_OK;
   if (rc_groups) return rc_groups;

@@ -2,7 +2,9 @@
 // entry (kernels/attention_f32.hip) — scores, scale, row sums and softmax live in the registers of its blocks and get no
 // arena storage.  Formed before every other group, only when
 //   - row fusion and the batched products are both enabled (EG_NO_ROWFUSE, EG_NO_BATCHED_GEMM: the plan is then the unfused one);
-//   - the model does not keep values (eg_model_keep_values) and computes in float32 (make_plan calls this under `fuse`);
+//   - the model does not keep values (eg_model_keep_values) and computes in float32 (make_plan calls this under `fuse`), or
+//     computes in float64 and asks for it (eg_model_fuse_attention_f64: the launch is kernels/attention_f64.hip's, and the
+//     chain's products are two-index products only under eg_model_batched2_f64, so the group needs that setting too);
 //   - plan_batched2's checks pass for both products (loops from 0, extents at least 1, rank-4 dense shapes covered by the loops);
 //   - the three kernels between them run over exactly the scores' shape, which the products' loops cover exactly;
 //   - no intermediate is a gradient-bucket member, and the chain does not straddle the backward | update boundary;
@@ -111,6 +113,7 @@ bool plan_chain(eg_model* m, TargetState& ts, const Plan& plan, const std::vecto
   A.e = {i4.bounds[g4.lb[outer4]].second, i4.bounds[g4.lb[inner4]].second, L0.M, L0.N, L0.K, L4.N};
   if (A.e.batch0 != i0.bounds[g0.lb[outer0]].second || A.e.batch1 != i0.bounds[g0.lb[inner0]].second) return false;
   A.scale = am.scale;
+  A.scale_f64 = am.scale_f64;
   A.q = {am.t_q, {L0.lda, stride_of(Qs, g0.batch_dim[0][outer0]), stride_of(Qs, g0.batch_dim[0][inner0])}};
   A.k = {am.t_k, {L0.ldb, stride_of(Ks, g0.batch_dim[1][outer0]), stride_of(Ks, g0.batch_dim[1][inner0])}};
   A.v = {am.t_v, {L4.ldb, stride_of(Vs, g4.batch_dim[1][outer4]), stride_of(Vs, g4.batch_dim[1][inner4])}};
@@ -131,7 +134,16 @@ eg::attention::Problem problem_of(eg_model* m, const Launch::Attn& A) {
   return pr;
 }
 
-bool enabled(eg_model* m) { return row_fusion_enabled() && !eg::sw::on(eg::Sw::NO_BATCHED_GEMM) && !m->keep_values && !m->f64; }
+// (a float64 model: only under eg_model_fuse_attention_f64, and — plan_chain's two_batch check — only where
+// eg_model_batched2_f64 has lowered the chain's products as two-index products)
+bool enabled(eg_model* m) {
+  return row_fusion_enabled() && !eg::sw::on(eg::Sw::NO_BATCHED_GEMM) && !m->keep_values && (!m->f64 || m->fuse_attention_f64);
+}
+
+// The kernel's own planner for the model's scalar type: K and D at most 128.
+bool kernel_supports(eg_model* m, const Launch::Attn& A) {
+  return m->f64 ? eg::attention::plan_attention_f64(problem_of(m, A)).supported : eg::attention::plan_attention(problem_of(m, A)).supported;
+}
 
 }  // namespace
 
@@ -150,7 +162,7 @@ int form_attention_groups(eg_model* m, TargetState& ts, Plan& plan, const std::v
     Launch L;
     int outer_pos = 0;
     if (!ok || !plan_chain(m, ts, plan, infos, group_of, am, L, outer_pos)) continue;
-    if (!eg::attention::plan_attention(problem_of(m, L.attn)).supported) continue;   // K or D above 128: the unfused plan
+    if (!kernel_supports(m, L.attn)) continue;   // K or D above 128: the unfused plan
     for (int s = p; s <= last; ++s) group_of[s] = ATTENTION_GROUP_CODE;
     for (int x : {am.t_scores, am.t_scaled, am.t_sums, am.t_softmax})
       if (x) plan.attn_hidden.insert(x);
@@ -163,7 +175,7 @@ int form_attention_groups(eg_model* m, TargetState& ts, Plan& plan, const std::v
 int form_attention_fit_groups(eg_model* m, TargetState& ts, Plan& plan, const std::vector<KernelInfo>& infos, const std::map<int, int>& first_writer,
                               std::vector<int>& group_of) {
   (void)first_writer;
-  if (!m->fuse_attention_fit || !enabled(m)) return EG_OK;
+  if (!m->fuse_attention_fit || m->f64 || !enabled(m)) return EG_OK;   // (the fit route is float32-only)
   const Target& t = *ts.target;
   const Shapes& shapes = plan.shapes;
   const int n = (int)t.live.size();

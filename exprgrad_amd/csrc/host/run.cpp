@@ -134,6 +134,12 @@ int issue_batched(eg_model* m, TargetState& ts, Plan& plan, const Launch& L) {
 
 int issue_attention(eg_model* m, TargetState& ts, Plan& plan, const Launch& L) {
   const Launch::Attn& A = L.attn;
+  if (m->f64) {   // a forward group under eg_model_fuse_attention_f64: the fit route is float32-only
+    auto dp = [&](const Launch::Attn::Operand& x) -> double* { return x.tensor ? reinterpret_cast<double*>(tensor_ptr(m, ts, plan, x.tensor)) : nullptr; };
+    EG_REQUIRE(L.kind == StepKind::Attention, EG_ERR_INVALID, "a float64 plan has no attention backward launch");
+    return eg::attention::attention_forward_f64(m->ctx, A.e, A.scale_f64, dp(A.q), A.q.view, dp(A.k), A.k.view, dp(A.v), A.v.view, dp(A.o), A.o.view,
+                                                L.accumulate, dp(A.sums), A.sums.view);
+  }
   auto ptr = [&](const Launch::Attn::Operand& x) -> float* { return x.tensor ? tensor_ptr(m, ts, plan, x.tensor) : nullptr; };
   if (L.kind == StepKind::Attention)   // a fit group's forward has the row sums to store for the backward launch
     return eg::attention::attention_forward(m->ctx, A.e, A.scale, ptr(A.q), A.q.view, ptr(A.k), A.k.view, ptr(A.v), A.v.view, ptr(A.o), A.o.view,

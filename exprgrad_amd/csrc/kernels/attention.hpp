@@ -14,6 +14,11 @@ namespace attention {
 int attention_forward(eg_ctx* ctx, const Extents& e, float scale, const float* Q, View q, const float* Kk, View k, const float* V, View v, float* O,
                       View o, int accumulate, float* Sums = nullptr, View s = {});
 
+// The float64 forward (attention_f64.hip): eg_attention_f64, eg_attention_sums_f64 and the attention launches of a float64
+// model under eg_model_fuse_attention_f64.  The same contract in doubles; the scale is a double end to end.
+int attention_forward_f64(eg_ctx* ctx, const Extents& e, double scale, const double* Q, View q, const double* Kk, View k, const double* V, View v,
+                          double* O, View o, int accumulate, double* Sums = nullptr, View s = {});
+
 // The backward over what that launch left (attention_grad_f32.hip); accumulate: bits 1 (dQ), 2 (dK) and 4 (dV).
 int attention_grad(eg_ctx* ctx, const Extents& e, float scale, const float* Q, View q, const float* Kk, View k, const float* V, View v,
                    const float* O, View o, const float* Sums, View s, const float* dO, View dout, float* dQ, View dq, float* dK, View dk, float* dV,

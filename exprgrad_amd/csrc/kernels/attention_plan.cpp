@@ -1,5 +1,6 @@
 // plan_attention: see attention_plan.hpp.  One tile shape (64 query rows x 64 keys, four waves of 16 rows) for every
-// problem; what varies is the padded head dimensions, the load width per operand and the cut into launches.
+// float32 problem; what varies is the padded head dimensions, the load width per operand and the cut into launches.  The
+// float64 forward (plan_attention_f64) also varies the key tile: 64 keys, or 32 where 64 do not fit the LDS.
 #include "attention_plan.hpp"
 
 #include <algorithm>
@@ -7,7 +8,10 @@
 namespace eg {
 namespace attention {
 
-Plan plan_attention(const Problem& p) {
+namespace {
+
+// The forward's plan in either scalar type: the two differ in the key tile, the LDS rows and the 16-byte rule.
+Plan plan_forward(const Problem& p, bool f64) {
   Plan r;
   if (p.batch0 < 1 || p.batch1 < 1 || p.I < 1 || p.J < 0 || p.K < 0 || p.D < (p.sums ? 0 : 1)) {
     r.reason = "an empty or negative extent";
@@ -23,8 +27,9 @@ Plan plan_attention(const Problem& p) {
   }
   r.kp = padded_head(p.K);
   r.dp = padded_head(p.D);
-  r.lds_bytes = lds_bytes_for(r.kp, r.dp);
-  if (r.lds_bytes > LDS_LIMIT) {
+  if (f64) r.tile_j = key_tile_f64(r.kp, r.dp);
+  r.lds_bytes = f64 ? lds_bytes_for_f64(r.kp, r.dp, r.tile_j) : lds_bytes_for(r.kp, r.dp);
+  if (r.tile_j == 0 || r.lds_bytes > LDS_LIMIT) {
     r.reason = "the tiles exceed the LDS of a CU";
     return r;
   }
@@ -33,15 +38,20 @@ Plan plan_attention(const Problem& p) {
     r.reason = "an item has more row tiles than one launch has blocks";
     return r;
   }
-  r.vec_q = operand_vec16(p.q);
-  r.vec_k = operand_vec16(p.k);
-  r.vec_v = operand_vec16(p.v);
+  r.vec_q = f64 ? operand_vec16_f64(p.q) : operand_vec16(p.q);
+  r.vec_k = f64 ? operand_vec16_f64(p.k) : operand_vec16(p.k);
+  r.vec_v = f64 ? operand_vec16_f64(p.v) : operand_vec16(p.v);
   r.items = p.batch0 * p.batch1;
   const Cut c = cut_items(r.items, tiles_i);
   r.tiles_i = c.tiles, r.grid = c.grid, r.items_per_launch = c.items_per_launch, r.launches = c.launches;
   r.supported = true;
   return r;
 }
+
+}  // namespace
+
+Plan plan_attention(const Problem& p) { return plan_forward(p, false); }
+Plan plan_attention_f64(const Problem& p) { return plan_forward(p, true); }
 
 // Empty I, J, K and D are plans too (a kernel with no tiles has no launches; the entry decides what an empty extent
 // writes); empty batch extents are not.

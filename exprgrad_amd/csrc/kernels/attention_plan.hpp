@@ -69,6 +69,35 @@ Plan plan_attention(const Problem& p);
 // Launch `index` of a plan, index in [0, plan.launches): the cut's, for a caller that holds the plan.
 inline Launch plan_launch(const Plan& plan, long index) { return plan_launch(plan.items, plan.cut(), index); }
 
+// ---- The float64 forward (attention_f64.hip): the same tile of 64 query rows and the same padded head dimensions on
+// v_mfma_f64_16x16x4_f64.  Problem and Plan are the ones above; what differs is decided here, not in the kernel: the key tile
+// (Plan::tile_j, 64 or 32 keys), the LDS rows in doubles, and 16-byte loads that hold two elements.
+constexpr int TILE_J_F64[2] = {64, 32};   // the key tiles the kernel is instantiated on, largest first
+
+// 16-byte loads of a float64 operand: the pointer of item (0, 0) 16-byte aligned, the leading dimension and both strides
+// even (the rule of eg_dgemm_batched2).  A row's odd last element is read alone in either mode.
+inline bool operand_vec16_f64(const Operand& x) { return x.aligned && x.ld % 2 == 0 && x.stride0 % 2 == 0 && x.stride1 % 2 == 0; }
+
+// Doubles per row of the three LDS tiles.  A double spans two of the 64 banks and a wave's 8-byte accesses go half a wave at
+// a time, so 32 lanes must land on 32 different doubles modulo 32.  K rows [tile_j][kp + 2]: a half-wave reads 16 keys x 2 k,
+// at 2 c + g.  V rows [tile_j][dp + 16]: 2 keys x 16 columns, at 16 g + c.  E rows [4 waves][16][tile_j + 18]: the A-operand
+// read of 16 rows x 2 keys at 18 c + g is conflict-free, the accumulator-layout write of 2 rows x 16 columns at 18 g + c
+// meets itself on two doubles of 32 (a row step that is 16 modulo 32 would free the write and fold the read eight times).
+constexpr int F64_PAD_K = 2, F64_PAD_V = 16, F64_PAD_E = 18;
+constexpr long lds_bytes_for_f64(int kp, int dp, int tile_j) {
+  return 8L * (tile_j * (kp + F64_PAD_K) + tile_j * (dp + F64_PAD_V) + 4 * 16 * (tile_j + F64_PAD_E));
+}
+
+// The key tile of a pair of padded head dimensions: the largest whose three tiles fit the LDS of a CU (0: none does).  The
+// kernel is instantiated on this function's value, so a plan and its kernel cannot disagree.
+constexpr int key_tile_f64(int kp, int dp) {
+  for (int tj : TILE_J_F64)
+    if (lds_bytes_for_f64(kp, dp, tj) <= LDS_LIMIT) return tj;
+  return 0;
+}
+
+Plan plan_attention_f64(const Problem& p);
+
 // ---- The backward pass (attention_grad_f32.hip): two kernels, one over tiles of 64 query rows (dQ), one over tiles of 64
 // keys (dK and dV).  Both keep the block's own rows in registers and walk the other axis in tiles of 64.
 struct GradProblem : Extents {

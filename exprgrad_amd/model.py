@@ -140,6 +140,15 @@ class Model:
         the next run plans, and a captured step captures, anew."""
         call("eg_model_batched2_f64", self.handle, 1 if on else 0)
 
+    def fuse_attention_f64(self, on=True):
+        """A float64 model's forward attention chain (scores, optional scale by a literal, row sums of exp, softmax, context)
+        runs as one eg_attn launch on the float64 fused kernel (eg_attention_f64's); scores and softmax are never stored.
+        The group needs the chain's two products lowered as two-index products, so turning this on turns `batched2_f64` on
+        too; turning it off leaves `batched2_f64` as it is.  Off by default; an error on a float32 model."""
+        if on:
+            self.batched2_f64(True)
+        call("eg_model_fuse_attention_f64", self.handle, 1 if on else 0)
+
     def set_seed(self, seed):
         """Seed of the model's random tensors (`rand`, dropout masks); the reference uses Nim's global
         generator (`randomize(seed)`)."""

@@ -64,6 +64,23 @@ def attention_sums(ctx, batch0, batch1, I, J, K, D, scale, Q, ldq, strides_q, Kk
          strides_s[0], strides_s[1])
 
 
+def attention_f64(ctx, batch0, batch1, I, J, K, D, scale, Q, ldq, strides_q, Kk, ldk, strides_k, V, ldv, strides_v, O, ldo, strides_o,
+                  accumulate=False):
+    """The float64 form of `attention`: the same formula and addressing in doubles (leading dimensions and strides in doubles,
+    the scale a double), on the float64 matrix instruction.  K and D at most 128."""
+    call("eg_attention_f64", ctx.handle, batch0, batch1, I, J, K, D, float(scale), _p(Q), ldq, strides_q[0], strides_q[1], _p(Kk), ldk,
+         strides_k[0], strides_k[1], _p(V), ldv, strides_v[0], strides_v[1], _p(O), ldo, strides_o[0], strides_o[1], int(accumulate))
+
+
+def attention_sums_f64(ctx, batch0, batch1, I, J, K, D, scale, Q, ldq, strides_q, Kk, ldk, strides_k, V, ldv, strides_v, O, ldo, strides_o,
+                       Sums, strides_s, accumulate=False):
+    """The float64 form of `attention_sums`: item (o, i1) also writes its I denominators, doubles, at Sums + o * strides_s[0] +
+    i1 * strides_s[1].  O has the bits `attention_f64` gives; Sums is always overwritten; Sums = None is `attention_f64`."""
+    call("eg_attention_sums_f64", ctx.handle, batch0, batch1, I, J, K, D, float(scale), _p(Q), ldq, strides_q[0], strides_q[1], _p(Kk), ldk,
+         strides_k[0], strides_k[1], _p(V), ldv, strides_v[0], strides_v[1], _p(O), ldo, strides_o[0], strides_o[1], int(accumulate), _p(Sums),
+         strides_s[0], strides_s[1])
+
+
 def attention_grad(ctx, batch0, batch1, I, J, K, D, scale, Q, ldq, strides_q, Kk, ldk, strides_k, V, ldv, strides_v, O, ldo, strides_o, Sums,
                    strides_s, dO, lddo, strides_do, dQ, lddq, strides_dq, dK, lddk, strides_dk, dV, lddv, strides_dv, accumulate=0):
     """Fused attention backward, two launches that store nothing of size I x J: from Q, Kk, V, the forward's O and Sums

@@ -264,6 +264,51 @@ int eg_attention_sums(eg_ctx* ctx, int64_t batch0, int64_t batch1, int64_t I, in
                       float* O, int64_t ldo, int64_t stride_o0, int64_t stride_o1, int accumulate,
                       float* Sums, int64_t stride_s0, int64_t stride_s1);
 
+/* eg_attention in float64: the same formula, addressing and contract, word for word, in doubles — what a compile[float64]
+ * model computes between its two multi-head products.  One launch of batch0 x batch1 x ceil(I / 64) blocks
+ * (kernels/attention_f64.hip) on v_mfma_f64_16x16x4_f64, split along the flattened (o, i1) range when it would exceed 2^22
+ * blocks; e = exp(s * scale) is one double multiplication and the double exp, as the generated float64 kernels emit it,
+ * without the row maximum; the scale is a double end to end; no atomics, no workspace, no k-slices: two calls give the
+ * same bits, and an item has the same bits whatever batch it is part of.
+ *   - accumulate, the strides of Q, Kk and V (each may be 0, a negative one is EG_ERR_INVALID) and O's rule
+ *     (batched2_c_distinct(batch0, stride_o0, batch1, stride_o1, I, ldo, D), else EG_ERR_INVALID) are eg_attention's.
+ *   - EG_ERR_INVALID, with a message that names eg_attention_f64: a NULL ctx, a NULL operand of a non-empty call, a negative
+ *     extent, a leading dimension shorter than a row, a batch extent of 2^31 or more.
+ *   - EG_ERR_UNSUPPORTED, with a message that names the limit: K > 128 or D > 128.  I >= 1 and J >= 1 are arbitrary.
+ *   - batch0 == 0, batch1 == 0, I == 0 or D == 0 succeed and launch nothing; J == 0 writes zeros when accumulate == 0 and
+ *     nothing otherwise; K == 0: every score is 0, the result is the mean of V's rows.
+ *   - No alignment is required.  An operand is read with 16-byte loads (two doubles) when its pointer is 16-byte aligned and
+ *     its leading dimension and both its strides are even (the rule of eg_dgemm_batched2), with 8-byte loads otherwise; a
+ *     row's odd last element is read alone in either mode.  Both modes give the same bits.
+ *   - Elements of O outside the items are never written, and elements of Q, Kk and V outside the views are never read,
+ *     whatever they hold — NaN included.
+ * Special values are eg_attention's: a row whose scores hold +Inf or overflow exp is NaN; a NaN poisons its row; a row whose
+ * terms all underflow is 0 / 0 = NaN; -Inf terms add nothing.  The one departure: when the sum overflows while every term is
+ * finite, the program gives 0 for that row (finite / Inf) and this entry gives NaN. */
+int eg_attention_f64(eg_ctx* ctx, int64_t batch0, int64_t batch1, int64_t I, int64_t J, int64_t K, int64_t D, double scale,
+                     const double* Q, int64_t ldq, int64_t stride_q0, int64_t stride_q1,
+                     const double* Kk, int64_t ldk, int64_t stride_k0, int64_t stride_k1,
+                     const double* V, int64_t ldv, int64_t stride_v0, int64_t stride_v1,
+                     double* O, int64_t ldo, int64_t stride_o0, int64_t stride_o1, int accumulate);
+
+/* eg_attention_f64 that also stores its denominators — eg_attention_sums in doubles: the first 25 arguments are
+ * eg_attention_f64's, and item (o, i1) writes Sums[o * stride_s0 + i1 * stride_s1 + i] = L_i for i in [0, I): the value the
+ * kernel divides row i by, after its fixed-order sum (NaN where that sum overflowed, 0 when J == 0).
+ *   - O has the bits eg_attention_f64 gives on the same arguments, whether or not Sums is given; Sums == NULL is
+ *     eg_attention_f64.
+ *   - Sums is always overwritten, never read: accumulate concerns O only.  With J == 0 and accumulate != 0, O is left alone
+ *     and Sums is zeros; with D == 0, O is empty and Sums is still written.
+ *   - Rows i >= I and everything outside the items' I doubles are never written.
+ *   - Sums must not alias itself: batched2_c_distinct(batch0, stride_s0, batch1, stride_s1, 1, I, I), else EG_ERR_INVALID.
+ *   - Every other refusal is eg_attention_f64's, with a message that names eg_attention_sums_f64.
+ * The same kernels with one compile-time flag in the row sums' epilogue; two calls give the same bits. */
+int eg_attention_sums_f64(eg_ctx* ctx, int64_t batch0, int64_t batch1, int64_t I, int64_t J, int64_t K, int64_t D, double scale,
+                          const double* Q, int64_t ldq, int64_t stride_q0, int64_t stride_q1,
+                          const double* Kk, int64_t ldk, int64_t stride_k0, int64_t stride_k1,
+                          const double* V, int64_t ldv, int64_t stride_v0, int64_t stride_v1,
+                          double* O, int64_t ldo, int64_t stride_o0, int64_t stride_o1, int accumulate,
+                          double* Sums, int64_t stride_s0, int64_t stride_s1);
+
 /* Fused attention backward: for every item, with s_ij = q_i . k_j, p_ij = exp(scale * s_ij) / L_i, O the forward's result
  * (computed with accumulate == 0), Sums its denominators L_i (eg_attention_sums) and dO the gradient of O,
  *   delta_i = dO_i . o_i,  dP_ij = dO_i . v_j,  dS_ij = scale * p_ij * (dP_ij - delta_i),
@@ -571,6 +616,22 @@ int eg_model_fuse_attention_fit(eg_model* model, int on);
  * the launches of the setting; if lowering fails, the error is returned and the model keeps the setting it had.  EG_ERR_INVALID: a NULL model, a float32 model (its products take the route already).
  * The default is off, and with it off every plan, launch and bit is what it was. */
 int eg_model_batched2_f64(eg_model* model, int on);
+/* The forward attention chain of a compile[float64] model on the float64 fused kernel.  on != 0: from the next run on, a
+ * forward chain that holds what eg_attention_f64 computes (scores, optional scale by a literal, row sums of exp, softmax,
+ * context) runs as ONE launch of that entry's kernel; eg_model_launch_text names it eg_attn, the scale is the literal as a
+ * double, and the scores, the scaled scores, the sums and the softmax get no storage (eg_model_read_tensor_f64 refuses them
+ * as eg_model_read_tensor does for a float32 model).
+ * THIS SETTING ALONE FORMS NO GROUP: the group needs the chain's two products lowered as products with two batch indices,
+ * which a float64 model does only under eg_model_batched2_f64.  Turn both on; with eg_model_batched2_f64 off, this setting
+ * changes the plan key and nothing else.  (The Python and Nim wrappers turn both on in one call.)
+ * What is refused keeps the plan it had — everything the float32 forward group refuses: a mask, bounded columns, a transposed
+ * operand, rank 3 or 5, a scale by a tensor or by division, K or D above 128, eg_model_keep_values, EG_NO_ROWFUSE,
+ * EG_NO_BATCHED_GEMM, an intermediate that is a gradient-bucket member, read outside the chain or the target's output (so
+ * every `fit` target keeps its generated or eg_bgemm2 kernels: eg_model_fuse_attention_fit stays float32-only), a chain
+ * across the backward | update boundary, a member that producer inlining absorbed.  A group forms whole or not at all.
+ * EG_ERR_INVALID: a NULL model, a float32 model (its chains take the route already).  The setting is part of the plan key;
+ * the default is off, and with it off every plan, launch and bit is what it was. */
+int eg_model_fuse_attention_f64(eg_model* model, int on);
 
 /* Model.epoch (model.nim:39, bumped by fit at model.nim:436). */
 int eg_model_set_epoch(eg_model* model, int64_t epoch);

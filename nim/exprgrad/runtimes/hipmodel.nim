@@ -36,6 +36,7 @@ proc eg_model_set_epoch(model: ptr EgModel, epoch: int64): cint
 proc eg_model_epoch(model: ptr EgModel): int64
 proc eg_model_keep_values(model: ptr EgModel, on: cint): cint
 proc eg_model_batched2_f64(model: ptr EgModel, on: cint): cint
+proc eg_model_fuse_attention_f64(model: ptr EgModel, on: cint): cint
 proc eg_model_plan_text(model: ptr EgModel): cstring
 proc eg_model_launch_text(model: ptr EgModel, target: cstring): cstring
 proc eg_model_state_bytes(model: ptr EgModel, bytes: ptr csize_t): cint
@@ -568,6 +569,13 @@ proc batched2F64*[T](model: HipModel[T], on = true) =
   ## as eg_bgemm2 launches on the float64 matrix instruction (eg_dgemm_batched2's kernel) instead of generated kernels; off
   ## by default, an error for a HipModel[float32]
   check eg_model_batched2_f64(model.handle, cint(ord(on)))
+proc fuseAttentionF64*[T](model: HipModel[T], on = true) =
+  ## A float64 model's forward attention chain (scores, optional scale by a literal, row sums of exp, softmax, context) runs
+  ## as one eg_attn launch on the float64 fused kernel (eg_attention_f64's); scores and softmax are never stored.  The group
+  ## needs the chain's products lowered as two-index products, so turning this on turns batched2F64 on too; off by default,
+  ## an error for a HipModel[float32]
+  if on: check eg_model_batched2_f64(model.handle, cint(1))
+  check eg_model_fuse_attention_f64(model.handle, cint(ord(on)))
 proc emitIr*[T](model: HipModel[T]): string = $eg_model_plan_text(model.handle)                    # model.nim:262-264
 proc launches*[T](model: HipModel[T], target: string): string = $eg_model_launch_text(model.handle, target.cstring)
 
