@@ -84,6 +84,8 @@ _SIGS = {
     "eg_attention_f64": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_f64] + [c_void_p, c_i64, c_i64, c_i64] * 4 + [c_int]),
     "eg_attention_sums_f64": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_f64] + [c_void_p, c_i64, c_i64, c_i64] * 4 +
                               [c_int, c_void_p, c_i64, c_i64]),
+    "eg_attention_grad_f64": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_f64] + [c_void_p, c_i64, c_i64, c_i64] * 4 +
+                              [c_void_p, c_i64, c_i64] + [c_void_p, c_i64, c_i64, c_i64] * 4 + [c_int]),
     "eg_bias_add": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_int]),
     "eg_colsum": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_int]),
     "eg_rowsum": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_int]),

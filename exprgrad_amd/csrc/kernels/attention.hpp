@@ -1,4 +1,4 @@
-// The fused attention kernels' internal entries: what the C ABI (eg_attention, eg_attention_sums, eg_attention_grad) and
+// The fused attention kernels' internal entries: what the C ABI (eg_attention, eg_attention_sums, eg_attention_grad and their _f64 forms) and
 // the model layer's attention launches (host/run.cpp) call.  Every operand is a pointer to item (0, 0) and its View
 // (attention_plan.hpp); the row sums' view has no leading dimension.
 #pragma once
@@ -23,6 +23,11 @@ int attention_forward_f64(eg_ctx* ctx, const Extents& e, double scale, const dou
 int attention_grad(eg_ctx* ctx, const Extents& e, float scale, const float* Q, View q, const float* Kk, View k, const float* V, View v,
                    const float* O, View o, const float* Sums, View s, const float* dO, View dout, float* dQ, View dq, float* dK, View dk, float* dV,
                    View dv, int accumulate);
+
+// The float64 backward (attention_grad_f64.hip): eg_attention_grad_f64, over what attention_forward_f64 left with Sums.
+int attention_grad_f64(eg_ctx* ctx, const Extents& e, double scale, const double* Q, View q, const double* Kk, View k, const double* V, View v,
+                       const double* O, View o, const double* Sums, View s, const double* dO, View dout, double* dQ, View dq, double* dK, View dk,
+                       double* dV, View dv, int accumulate);
 
 }  // namespace attention
 }  // namespace eg

@@ -53,9 +53,12 @@ Plan plan_forward(const Problem& p, bool f64) {
 Plan plan_attention(const Problem& p) { return plan_forward(p, false); }
 Plan plan_attention_f64(const Problem& p) { return plan_forward(p, true); }
 
-// Empty I, J, K and D are plans too (a kernel with no tiles has no launches; the entry decides what an empty extent
-// writes); empty batch extents are not.
-GradPlan plan_attention_grad(const GradProblem& p) {
+namespace {
+
+// The backward's plan in either scalar type: the two differ in the steps, the LDS rows and the 16-byte rule.  Empty I, J, K
+// and D are plans too (a kernel with no tiles has no launches; the entry decides what an empty extent writes); empty batch
+// extents are not.
+GradPlan plan_backward(const GradProblem& p, bool f64) {
   GradPlan r;
   if (p.batch0 < 1 || p.batch1 < 1 || p.I < 0 || p.J < 0 || p.K < 0 || p.D < 0) {
     r.reason = "an empty batch or a negative extent";
@@ -71,9 +74,15 @@ GradPlan plan_attention_grad(const GradProblem& p) {
   }
   r.kp = padded_head(p.K);
   r.dp = padded_head(p.D);
-  r.dq.lds_bytes = grad_dq_lds_bytes(r.kp, r.dp);
-  r.dkv.lds_bytes = grad_dkv_lds_bytes(r.kp, r.dp);
-  if (r.dq.lds_bytes > LDS_LIMIT || r.dkv.lds_bytes > LDS_LIMIT) {
+  if (f64) {
+    r.dq.step = grad_dq_step_f64(r.kp, r.dp), r.dkv.step = grad_dkv_step_f64(r.kp, r.dp);
+    r.dq.lds_bytes = grad_dq_lds_bytes_f64(r.kp, r.dp, r.dq.step);
+    r.dkv.lds_bytes = grad_dkv_lds_bytes_f64(r.kp, r.dp, r.dkv.step);
+  } else {
+    r.dq.lds_bytes = grad_dq_lds_bytes(r.kp, r.dp);
+    r.dkv.lds_bytes = grad_dkv_lds_bytes(r.kp, r.dp);
+  }
+  if (r.dq.step == 0 || r.dkv.step == 0 || r.dq.lds_bytes > LDS_LIMIT || r.dkv.lds_bytes > LDS_LIMIT) {
     r.reason = "the tiles exceed the LDS of a CU";
     return r;
   }
@@ -82,15 +91,21 @@ GradPlan plan_attention_grad(const GradProblem& p) {
     r.reason = "an item has more tiles than one launch has blocks";
     return r;
   }
-  r.vec_q = operand_vec16(p.q), r.vec_k = operand_vec16(p.k), r.vec_v = operand_vec16(p.v), r.vec_o = operand_vec16(p.o);
-  r.vec_s = operand_vec16(p.s), r.vec_do = operand_vec16(p.dout);
-  r.vec_dq = operand_vec16(p.dq), r.vec_dk = operand_vec16(p.dk), r.vec_dv = operand_vec16(p.dv);
+  const auto vec = [f64](const Operand& x) { return f64 ? operand_vec16_f64(x) : operand_vec16(x); };
+  r.vec_q = vec(p.q), r.vec_k = vec(p.k), r.vec_v = vec(p.v), r.vec_o = vec(p.o);
+  r.vec_s = vec(p.s), r.vec_do = vec(p.dout);
+  r.vec_dq = vec(p.dq), r.vec_dk = vec(p.dk), r.vec_dv = vec(p.dv);
   r.items = p.batch0 * p.batch1;
   static_cast<Cut&>(r.dq) = cut_items(r.items, tiles_i);
   static_cast<Cut&>(r.dkv) = cut_items(r.items, tiles_j);
   r.supported = true;
   return r;
 }
+
+}  // namespace
+
+GradPlan plan_attention_grad(const GradProblem& p) { return plan_backward(p, false); }
+GradPlan plan_attention_grad_f64(const GradProblem& p) { return plan_backward(p, true); }
 
 }  // namespace attention
 }  // namespace eg

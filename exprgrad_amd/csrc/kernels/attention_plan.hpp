@@ -137,5 +137,57 @@ GradPlan plan_attention_grad(const GradProblem& p);
 // Launch `index` of one of a plan's kernels, index in [0, kernel.launches): the cut's again.
 inline Launch plan_grad_launch(const GradPlan& plan, const GradKernel& kernel, long index) { return plan_launch(plan.items, kernel, index); }
 
+// ---- The float64 backward (attention_grad_f64.hip): the same two kernels on v_mfma_f64_16x16x4_f64.  GradProblem and
+// GradPlan are the ones above; decided here: each kernel's step over the other axis (GradKernel::step, 64 or 32 rows), the LDS
+// rows in doubles, and the even rule of operand_vec16_f64 for all nine operands.
+//
+// Doubles per LDS row.  A half wave's 32 lanes must land on 32 different doubles modulo 32.  A tile read both ways has an NT
+// read at s c + g and an NN read at s g + c (c < 16, g < 2 per half wave) and cannot be free of conflicts both ways: a row
+// step s = 18 (mod 32) frees the NT read and folds the NN read on 2 doubles of 32 (the trade of the forward's E rows), where
+// s = 2 (mod 32) would fold the NN read on 14 of 16.  Tiles read both ways (the dQ kernel's K tile, the dK/dV kernel's Q and
+// dO tiles) have rows of width + 18, an NT-only tile (the dQ kernel's V tile) of width + 2, the waves' own rows of step + 18.
+// Derived from the bank map, not measured.
+constexpr int GRAD_F64_STEPS[2] = {64, 32};   // largest first
+constexpr int GRAD_F64_PAD_BOTH = 18, GRAD_F64_PAD_NT = 2, GRAD_F64_PAD_E = 18;
+
+// dQ kernel: K tile [step][kp + 18], V tile [step][dp + 2], the waves' dS rows [4][16][step + 18], 1 / L and delta of 64 rows.
+constexpr long grad_dq_lds_bytes_f64(int kp, int dp, int step) {
+  return 8L * (step * (kp + GRAD_F64_PAD_BOTH) + step * (dp + GRAD_F64_PAD_NT) + 4 * 16 * (step + GRAD_F64_PAD_E) + 2 * 64);
+}
+// dK/dV kernel: Q tile [step][kp + 18], dO tile [step][dp + 18], the waves' rows, 1 / L and delta of the tile's rows.
+constexpr long grad_dkv_lds_bytes_f64(int kp, int dp, int step) {
+  return 8L * (step * (kp + GRAD_F64_PAD_BOTH) + step * (dp + GRAD_F64_PAD_BOTH) + 4 * 16 * (step + GRAD_F64_PAD_E) + 2 * 64);
+}
+
+// 32-bit registers a lane of the dK/dV kernel holds across a tile's MFMAs: the A operands of its K and V rows and the dK
+// and dV accumulators (kp + dp together), S^T and dP^T (step), and with `ahead` the next Q tile, dO tile and O parts.  The
+// compiler's resource report draws the line: every instantiation at or below 320 of a lane's 512 has no scratch, and the
+// four that were above it (368 to 416, at the largest step their LDS allows) spilled 62 to 130 registers; the rest goes to
+// addresses and the exp's temporaries.  The line is this compiler's: nothing in the build checks for scratch, so when the
+// toolchain changes, regenerate the table of profiles/attention_grad_f64.txt (its section 1 has the command) and move the
+// budget if a kernel spills.
+constexpr int GRAD_F64_REG_BUDGET = 320;
+constexpr int grad_dkv_regs_f64(int kp, int dp, int step, bool ahead) {
+  return (kp + dp) + step + (ahead ? step * (kp + dp) / 128 + step * dp / 128 : 0);
+}
+
+// The step of each kernel at a pair of padded head dimensions: the largest whose LDS fits a CU (0: none does) and, in the
+// dK/dV kernel, whose registers fit with the look-ahead tile; where no step does, the dK/dV kernel takes the smallest step
+// without the look-ahead (grad_dkv_ahead_f64 false: its loads wait at the top of each pass).  The kernels are instantiated on
+// these functions' values, and the launcher checks them against the plan.  profiles/attention_grad_f64.txt has the table.
+constexpr int grad_dq_step_f64(int kp, int dp) {
+  for (int step : GRAD_F64_STEPS)
+    if (grad_dq_lds_bytes_f64(kp, dp, step) <= LDS_LIMIT) return step;
+  return 0;
+}
+constexpr int grad_dkv_step_f64(int kp, int dp) {
+  for (int step : GRAD_F64_STEPS)
+    if (grad_dkv_lds_bytes_f64(kp, dp, step) <= LDS_LIMIT && grad_dkv_regs_f64(kp, dp, step, true) <= GRAD_F64_REG_BUDGET) return step;
+  return grad_dkv_lds_bytes_f64(kp, dp, GRAD_F64_STEPS[1]) <= LDS_LIMIT ? GRAD_F64_STEPS[1] : 0;
+}
+constexpr bool grad_dkv_ahead_f64(int kp, int dp) { return grad_dkv_regs_f64(kp, dp, grad_dkv_step_f64(kp, dp), true) <= GRAD_F64_REG_BUDGET; }
+
+GradPlan plan_attention_grad_f64(const GradProblem& p);
+
 }  // namespace attention
 }  // namespace eg

@@ -348,6 +348,43 @@ int eg_attention_grad(eg_ctx* ctx, int64_t batch0, int64_t batch1, int64_t I, in
                       float* dK, int64_t lddk, int64_t stride_dk0, int64_t stride_dk1,
                       float* dV, int64_t lddv, int64_t stride_dv0, int64_t stride_dv1, int accumulate);
 
+/* eg_attention_grad in float64: the same formulas in doubles, the exponential the double exp of scale * s_ij as in
+ * eg_attention_f64, with O and Sums from eg_attention_sums_f64 (accumulate == 0) on the same operands.  Q, dQ are I x K, Kk,
+ * dK J x K, V, dV J x D, O, dO I x D, Sums I doubles per item; leading dimensions and strides in doubles.
+ * Two launches (kernels/attention_grad_f64.hip): batch0 x batch1 x ceil(I / 64) blocks for dQ, batch0 x batch1 x
+ * ceil(J / 64) blocks for dK and dV, each split along the flattened (o, i1) range when it would exceed 2^22 blocks.  Both
+ * recompute the probabilities tile by tile on v_mfma_f64_16x16x4_f64, walking the other axis in steps of 64 or 32 rows
+ * (kernels/attention_plan.hpp): nothing of size I x J is stored, no atomics, no workspace, every sum in a fixed order; two
+ * calls give the same bits, and an item has the same bits whatever batch it is part of.
+ *   - accumulate: bit 0 adds to dQ, bit 1 to dK, bit 2 to dV; an output whose bit is clear is not read.  Other bits are
+ *     EG_ERR_INVALID.
+ *   - Strides of the six inputs: each may be 0 (the operand is shared along that index); a negative one is EG_ERR_INVALID.
+ *   - Each output must not alias itself: batched2_c_distinct on its own shape, as for eg_attention_f64's O, else
+ *     EG_ERR_INVALID.  Aliasing between different operands is undefined.
+ *   - EG_ERR_INVALID, with a message that names eg_attention_grad_f64: a NULL ctx, a NULL operand of a non-empty call, a
+ *     negative extent, a leading dimension shorter than a row, a batch extent of 2^31 or more.
+ *   - EG_ERR_UNSUPPORTED, with a message that names the limit: K > 128 or D > 128.  I and J are arbitrary.
+ *   - A zero batch extent launches nothing.  I == 0 or J == 0: the outputs that have elements are zeros where their bit is
+ *     clear and untouched otherwise.  K == 0: dQ and dK are empty, dV is computed with every score 0.  D == 0: dV is empty, dQ
+ *     and dK are zeros where their bit is clear.
+ *   - No alignment is required.  Each of the nine operands, inputs and outputs alike, is accessed with 16-byte loads or stores
+ *     when its pointer is 16-byte aligned and its leading dimension and both its strides are even (the rule of
+ *     eg_dgemm_batched2), element by element otherwise; the bits are the same either way.
+ *   - Elements outside the views are never read and never written, whatever they hold; a row i >= I or a key j >= J of a
+ *     tile contributes exactly 0.
+ * Results for rows whose L_i is not finite (or 0) are unspecified: such rows may be NaN throughout their item, in dK and dV
+ * as well as in dQ. */
+int eg_attention_grad_f64(eg_ctx* ctx, int64_t batch0, int64_t batch1, int64_t I, int64_t J, int64_t K, int64_t D, double scale,
+                          const double* Q, int64_t ldq, int64_t stride_q0, int64_t stride_q1,
+                          const double* Kk, int64_t ldk, int64_t stride_k0, int64_t stride_k1,
+                          const double* V, int64_t ldv, int64_t stride_v0, int64_t stride_v1,
+                          const double* O, int64_t ldo, int64_t stride_o0, int64_t stride_o1,
+                          const double* Sums, int64_t stride_s0, int64_t stride_s1,
+                          const double* dO, int64_t lddo, int64_t stride_do0, int64_t stride_do1,
+                          double* dQ, int64_t lddq, int64_t stride_dq0, int64_t stride_dq1,
+                          double* dK, int64_t lddk, int64_t stride_dk0, int64_t stride_dk1,
+                          double* dV, int64_t lddv, int64_t stride_dv0, int64_t stride_dv1, int accumulate);
+
 /* out[y,x] (+)= bias[x]   — dense's second kernel, dnn.nim:22-24. out is [rows, cols]. */
 int eg_bias_add(eg_ctx* ctx, int64_t rows, int64_t cols, const float* bias, float* out,
                 int accumulate);
