@@ -51,6 +51,10 @@ struct Batched2GemmMatch {
 // The forward attention chain over consecutive live kernels of a target (match_attention.cpp):
 //   [0]       scores[b,h,i,j]  ++= q[..] * kk[..]              a product match_batched2_gemm takes as NT
 //   [1]       scaled[b,h,i,j]  ++= scores[b,h,i,j] * literal   optional, either operand order; absent: scale 1
+//             or, with `bias` (match_attention alone asks for it: the forward route of a float32 model),
+//             scaled[b,h,i,j]  ++= scores[b,h,i,j] * literal + m[...]   also literal * scores, m[...] first, or no literal:
+//             m an input or parameter indexed by bare registers of the scores in the scores' order, the last one present, each
+//             of the first three present or not (m[b,h,i,j], m[i,j], m[b,j], ...): eg_attention_bias' operand
 //   [n - 3]   sums[b,h,i]      ++= exp(e[b,h,i,j])             e: scaled, or scores without a scale map
 //   [n - 2]   softmax[b,h,i,j] ++= exp(e[b,h,i,j]) / sums[b,h,i]
 //   [n - 1]   context[..]      ++= softmax[b,h,i,j] * v[..]    a product match_batched2_gemm takes as NN, softmax its A
@@ -65,6 +69,8 @@ struct AttentionMatch {
   Batched2GemmMatch scores, context;   // of kernels [0] and [n - 1]
   int t_scores = 0, t_scaled = 0, t_sums = 0, t_softmax = 0;   // t_scaled: 0 without a scale map
   int t_q = 0, t_k = 0, t_v = 0, t_out = 0;
+  int t_bias = 0;                      // the added tensor of the scale map; 0: none
+  int bias_dim[4] = {-1, -1, -1, -1};  // per position of the scores: the dimension of the bias that runs over it, -1: absent
 };
 // The chain at live positions [p, p + m.n) of `t`?  why (optional): the reason of a refusal, a constant string.
 bool match_attention(const Program& prog, const Target& t, int p, AttentionMatch& m, const char** why = nullptr);
@@ -72,7 +78,8 @@ bool match_attention(const Program& prog, const Target& t, int p, AttentionMatch
 // The two halves of match_attention, shared with match_attention_fit (match_attention_grad.cpp):
 //   the kernels' structure at [p, p + m.n), nothing about who else touches the tensors (gaps: kernels that touch none of the
 //   chain's four intermediates may stand between its members — a projection of v between the softmax and the context);
-bool match_attention_chain(const Target& t, int p, AttentionMatch& m, const char** why = nullptr, bool gaps = false);
+//   (bias: the scale map may add a tensor; otherwise such a map is refused with a reason of its own)
+bool match_attention_chain(const Target& t, int p, AttentionMatch& m, const char** why = nullptr, bool gaps = false, bool bias = false);
 //   and the privacy of tensors: every xs[i] (0: skipped) is a Result, not the target's output, none of `operands`, read by
 //   no live kernel outside `members` (live positions; `read_outside` is the refusal's reason) and written by exactly
 //   writers[i] live kernels.

@@ -1,8 +1,11 @@
 // The forward attention chain (match.hpp, AttentionMatch): scores product, optional scale by a literal, row sum of exp,
-// exp / sums, context product — what eg_attention (kernels/attention_f32.hip) computes in one launch.  Structure only:
+// exp / sums, context product — what eg_attention (kernels/attention_f32.hip) computes in one launch; the scale map may add
+// an input or parameter m[...] to the scaled scores, which is then eg_attention_bias' operand (match_bias_map).  Structure only:
 // shapes, loop extents and the switches are the planner's business (plan_groups.cpp, form_attention_groups).
 // Refused, each with its reason: a mask (`select`), bounded column loops, a transposed row operand, rank 3 or 5 (the
-// products then do not match), a scale by a tensor or by division, a softmax or scores tensor with a second consumer or that
+// products then do not match), a scale by a tensor or by division, an added tensor that the target writes, whose indices
+// are out of the scores' order or lack the key index, a second added tensor, a bias in a float64 model or (the chain alone,
+// as match_attention_fit asks for it) any bias at all, a softmax or scores tensor with a second consumer or that
 // is the target's output — which includes every `fit` target, whose gradient kernels read them.
 #include "match.hpp"
 
@@ -43,9 +46,48 @@ bool fail(const char** why, const char* reason) {
   return false;
 }
 
+// The scale map with an added tensor (match.hpp): `k` reads the scores at reads[rs] and one other tensor, both with bare
+// registers, the scores' equal to the write's (w).  Fills scale, t_bias and bias_dim; false with the reason.
+bool match_bias_map(const Kernel& k, int rs, const std::vector<int>& w, AttentionMatch& m, const char** why) {
+  const Op& b = k.reads[1 - rs];
+  std::vector<int> br;
+  if (!bare_regs(k, b, br) || br.empty() || br.size() > 4) return fail(why, "the added tensor is not indexed by bare registers of the scores");
+  if (br.back() != w[3]) return fail(why, "the added tensor's last index is not the key index");
+  size_t at = 0;   // the registers in the scores' order: each one behind the one before
+  for (size_t d = 0; d < br.size(); ++d) {
+    while (at < 4 && w[at] != br[d]) ++at;
+    if (at == 4) return fail(why, "the added tensor's indices are not in the order of the scores");
+    m.bias_dim[at++] = (int)d;
+  }
+  // s * lit + b, lit * s + b, b + s * lit, s + b: at most a literal and a multiplication in front of the addition
+  const Instr* lit = nullptr;
+  const Instr* mul = nullptr;
+  const Instr* add = nullptr;
+  for (auto& ins : k.instrs) {
+    if (ins.kind == IK::Scalar && !lit) lit = &ins;
+    else if (ins.kind == IK::Mul && !mul) mul = &ins;
+    else if (ins.kind == IK::Add && !add) add = &ins;
+    else return fail(why, "the biased scale is not a multiplication by a literal and one addition");
+  }
+  const int x = k.reads[rs].reg;
+  if (!add || add->args.size() != 2 || k.result != add->res || !lit != !mul) return fail(why, "the biased scale is not a multiplication by a literal and one addition");
+  int scaled = x;
+  if (mul) {
+    if (mul->args.size() != 2 || !((mul->args[0] == x && mul->args[1] == lit->res) || (mul->args[1] == x && mul->args[0] == lit->res)))
+      return fail(why, "the scale is not one multiplication by a literal");
+    scaled = mul->res;
+    m.scale = (float)lit->lit;
+    m.scale_f64 = lit->lit;
+  }
+  if (!((add->args[0] == scaled && add->args[1] == b.reg) || (add->args[1] == scaled && add->args[0] == b.reg)))
+    return fail(why, "the addition does not add the tensor to the scaled scores");
+  m.t_bias = b.tensor;
+  return true;
+}
+
 }  // namespace
 
-bool match_attention_chain(const Target& t, int p, AttentionMatch& out, const char** why, bool gaps) {
+bool match_attention_chain(const Target& t, int p, AttentionMatch& out, const char** why, bool gaps, bool bias) {
   const int n_live = (int)t.live.size();
   if (p < 0 || p + 4 > n_live) return fail(why, "fewer than four kernels");
   AttentionMatch m;
@@ -88,7 +130,22 @@ bool match_attention_chain(const Target& t, int p, AttentionMatch& out, const ch
     const bool map_shape = plain_rank4(k) && k.reads.size() == 1 && k.reads[0].tensor == m.t_scores && bare_regs(k, k.reads[0], r) &&
                            bare_regs(k, k.write, w) && r.size() == 4 && r == w;
     const bool is_sum = k.write.dims.size() == 3;
-    if (!is_sum) {
+    // a map over the scores with an addition that reads more than the scores: the scale map with a bias
+    int rs = -1;
+    bool adds = false;
+    for (size_t i = 0; i < k.reads.size(); ++i)
+      if (k.reads[i].tensor == m.t_scores) rs = (int)i;
+    for (auto& ins : k.instrs) adds = adds || ins.kind == IK::Add;
+    if (!is_sum && adds && k.reads.size() > 1 && rs >= 0 && plain_rank4(k) && bare_regs(k, k.reads[rs], r) && bare_regs(k, k.write, w) && r.size() == 4 &&
+        r == w) {
+      if (k.reads.size() > 2) return fail(why, "the scale map adds a second tensor");
+      if (!bias) return fail(why, "the scale map adds a tensor, which only the forward route takes");
+      if (!match_bias_map(k, rs, w, m, why)) return false;
+      m.t_scaled = k.write.tensor;
+      e = m.t_scaled;
+      m.at.push_back(at);
+      at = next(at + 1);
+    } else if (!is_sum) {
       if (!map_shape) return fail(why, "the kernel behind the scores is neither a scale map over them nor the row sum");
       if (k.instrs.size() != 2) return fail(why, "the scale is not one multiplication by a literal");
       const Instr* lit = nullptr;
@@ -205,7 +262,12 @@ bool attention_private(const Program& prog, const Target& t, const std::vector<i
 
 bool match_attention(const Program& prog, const Target& t, int p, AttentionMatch& out, const char** why) {
   AttentionMatch m;
-  if (!match_attention_chain(t, p, m, why)) return false;
+  if (!match_attention_chain(t, p, m, why, false, true)) return false;
+  if (m.t_bias) {   // the bias is data of the caller's: eg_attention_bias in float32, read where the target's kernels left it alone
+    if (prog.f64) return fail(why, "a float64 model has no attention launch with a bias");
+    if (m.t_bias < 1 || m.t_bias >= (int)prog.tensors.size() || (prog.tensors[m.t_bias].kind != TK::Input && prog.tensors[m.t_bias].kind != TK::Param))
+      return fail(why, "the added tensor is neither an input nor a parameter");   // (a tensor that a kernel of the target writes is a result)
+  }
   // the intermediates exist for the chain alone
   if (!attention_private(prog, t, {m.t_scores, m.t_scaled, m.t_sums, m.t_softmax}, {1, 1, 1, 1}, {m.t_out, m.t_q, m.t_k, m.t_v}, m.at,
                          "an intermediate is read outside the chain", why))

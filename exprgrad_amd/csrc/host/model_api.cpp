@@ -317,6 +317,7 @@ const char* eg_model_launch_text(eg_model* m, const char* target) {
         }
         os << ")" << (L.accumulate ? " accumulate" : "");
         if (A.sums.tensor) os << " sums=" << tname(A.sums.tensor);
+        if (A.bias.tensor) os << " bias=" << tname(A.bias.tensor);
         break;
       }
       case StepKind::Conv: os << "conv2 -> t" << L.c_tensor << (L.accumulate ? " accumulate" : ""); break;

@@ -106,6 +106,8 @@ struct Launch {
     double scale_f64 = 1.0;          // a float64 model: the scale literal without loss
     Operand q, k, v, o;              // o: the context
     Operand sums;                    // a fit group: the row sums, one dense row of I floats per item (tensor != 0)
+    Operand bias;                    // Attention: the tensor added to the scaled scores (tensor != 0); an ld or a stride of 0
+                                     // where its index is absent (eg_attention_bias)
     Operand dout, dq, dk, dv;        // AttentionGrad: the context's gradient and the three outputs
     std::vector<int> members;        // live positions of the fused kernels, in order
     int acc = 0;                     // AttentionGrad: eg_attention_grad's accumulate bits: 1 dq, 2 dk, 4 dv

@@ -8,7 +8,9 @@
 //   - plan_batched2's checks pass for both products (loops from 0, extents at least 1, rank-4 dense shapes covered by the loops);
 //   - the three kernels between them run over exactly the scores' shape, which the products' loops cover exactly;
 //   - no intermediate is a gradient-bucket member, and the chain does not straddle the backward | update boundary;
-//   - plan_attention (kernels/attention_plan.cpp) supports the shape: K and D at most 128.
+//   - plan_attention (kernels/attention_plan.cpp) supports the shape: K and D at most 128;
+//   - a bias (match.hpp: the scale map adds an input or parameter m[...]) is dense and has the scores' extents where its
+//     indices stand; it becomes the launch's bias operand, with a stride or leading dimension of 0 for an absent index.
 // Anything else keeps the plan it had: two eg_bgemm2 launches around a collapsed wide row group, or generated kernels.
 //
 // Fit groups (form_attention_fit_groups, only under eg_model_fuse_attention_fit): a training step over the chain
@@ -44,19 +46,21 @@ long stride_of(const std::vector<long>& dims, int d) {
 
 // A map or a row sum of a group at live position s runs over exactly the scores' shape S: its rank-4 operands have that
 // shape with the loops covering it, its rank-3 operands the shape's first three extents.
-bool rows_cover(const Target& t, const std::vector<KernelInfo>& infos, const Shapes& shapes, int s, const std::vector<long>& S) {
+// (`bias`: a tensor the map adds, whose shape plan_chain holds to the positions of its indices)
+bool rows_cover(const Target& t, const std::vector<KernelInfo>& infos, const Shapes& shapes, int s, const std::vector<long>& S, int bias = 0) {
   const Kernel& k = t.all[t.live[s]];
   const KernelInfo& info = infos[t.live[s]];
   bool ok = info.ok;
   const Op* e = nullptr;   // the rank-4 read: all four registers in the positions of the scores
   for (auto& rd : k.reads)
-    if (rd.dims.size() == 4) e = &rd;
+    if (rd.dims.size() == 4 && rd.tensor != bias) e = &rd;
   ok = ok && e;
   for (int d = 0; ok && d < 4; ++d) {
     const int l = loop_index(k, e->dims[d].only_register());
     ok = l >= 0 && info.bounds[l].first == 0 && info.bounds[l].second == S[d];
   }
   for (auto& rd : k.reads) {
+    if (rd.tensor == bias) continue;
     auto sh = shapes.find(rd.tensor);
     ok = ok && sh != shapes.end() && sh->second == (rd.dims.size() == 4 ? S : std::vector<long>(S.begin(), S.begin() + 3));
   }
@@ -88,7 +92,19 @@ bool plan_chain(eg_model* m, TargetState& ts, const Plan& plan, const std::vecto
   ok = S.size() == 4 && L0.M == L4.M && L0.N == L4.K && S[2] == L0.M && S[3] == L0.N;
   for (int q = 0; ok && q < 2; ++q)
     ok = S[g0.batch_dim[2][q]] == i0.bounds[g0.lb[q]].second && S[g4.batch_dim[0][q]] == i4.bounds[g4.lb[q]].second;
-  for (size_t s = 1; ok && s + 1 < am.at.size(); ++s) ok = rows_cover(t, infos, shapes, am.at[s], S);
+  for (size_t s = 1; ok && s + 1 < am.at.size(); ++s) ok = rows_cover(t, infos, shapes, am.at[s], S, am.t_bias);
+  // the bias: a dense tensor whose extents are the scores' at the positions of its indices
+  if (ok && am.t_bias) {
+    auto bs = shapes.find(am.t_bias);
+    ok = bs != shapes.end();
+    int present = 0;
+    for (int d = 0; ok && d < 4; ++d) {
+      if (am.bias_dim[d] < 0) continue;
+      ok = am.bias_dim[d] < (int)bs->second.size() && bs->second[am.bias_dim[d]] == S[d];
+      ++present;
+    }
+    ok = ok && present == (int)bs->second.size();
+  }
   if (!ok) return false;
   // The context's batch register with the larger stride in its output is the outer index (as plan_batched2 has it); the
   // scores' batch register at the same position of the scores is its partner.
@@ -118,6 +134,11 @@ bool plan_chain(eg_model* m, TargetState& ts, const Plan& plan, const std::vecto
   A.k = {am.t_k, {L0.ldb, stride_of(Ks, g0.batch_dim[1][outer0]), stride_of(Ks, g0.batch_dim[1][inner0])}};
   A.v = {am.t_v, {L4.ldb, stride_of(Vs, g4.batch_dim[1][outer4]), stride_of(Vs, g4.batch_dim[1][inner4])}};
   A.o = {am.t_out, {L4.ldc, stride_of(Os, g4.batch_dim[2][outer4]), stride_of(Os, g4.batch_dim[2][inner4])}};
+  if (am.t_bias) {   // an absent index is a stride or a leading dimension of 0
+    const std::vector<long>& Bs = shapes.at(am.t_bias);
+    auto step = [&](int pos) { return am.bias_dim[pos] >= 0 ? stride_of(Bs, am.bias_dim[pos]) : 0L; };
+    A.bias = {am.t_bias, {step(2), step(outer_pos), step(1 - outer_pos)}};
+  }
   A.members = am.at;
   return true;
 }
@@ -130,6 +151,8 @@ eg::attention::Problem problem_of(eg_model* m, const Launch::Attn& A) {
   static_cast<eg::attention::Extents&>(pr) = A.e;
   pr.q = operand(A.q), pr.k = operand(A.k), pr.v = operand(A.v), pr.o = operand(A.o);
   pr.sums = A.sums.tensor != 0;
+  pr.has_bias = A.bias.tensor != 0;
+  pr.bias = operand(A.bias);
   pr.cus = m->ctx->compute_units;
   return pr;
 }

@@ -66,6 +66,7 @@ void launch_io(eg_model* m, TargetState& ts, const Plan& plan, const Launch& L, 
       rd(L.attn.q.tensor);
       rd(L.attn.k.tensor);
       rd(L.attn.v.tensor);
+      if (L.attn.bias.tensor) rd(L.attn.bias.tensor);
       wr(L.attn.o.tensor, L.accumulate);
       wr(L.attn.sums.tensor, false);   // a fit group's forward launch stores the row sums whole
       break;

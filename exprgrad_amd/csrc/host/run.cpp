@@ -143,7 +143,7 @@ int issue_attention(eg_model* m, TargetState& ts, Plan& plan, const Launch& L) {
   auto ptr = [&](const Launch::Attn::Operand& x) -> float* { return x.tensor ? tensor_ptr(m, ts, plan, x.tensor) : nullptr; };
   if (L.kind == StepKind::Attention)   // a fit group's forward has the row sums to store for the backward launch
     return eg::attention::attention_forward(m->ctx, A.e, A.scale, ptr(A.q), A.q.view, ptr(A.k), A.k.view, ptr(A.v), A.v.view, ptr(A.o), A.o.view,
-                                            L.accumulate, ptr(A.sums), A.sums.view);
+                                            L.accumulate, ptr(A.sums), A.sums.view, ptr(A.bias), A.bias.view);
   return eg::attention::attention_grad(m->ctx, A.e, A.scale, ptr(A.q), A.q.view, ptr(A.k), A.k.view, ptr(A.v), A.v.view, ptr(A.o), A.o.view,
                                        ptr(A.sums), A.sums.view, ptr(A.dout), A.dout.view, ptr(A.dq), A.dq.view, ptr(A.dk), A.dk.view,
                                        ptr(A.dv), A.dv.view, A.acc);

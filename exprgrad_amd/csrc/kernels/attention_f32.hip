@@ -11,7 +11,8 @@
 //   S      = Q_rows * K_tile^T   16 x 64 per wave: four accumulators of v_mfma_f32_16x16x4_f32, Q from registers;
 //   e      = expf(S * scale)     one multiplication, then expf, as the generated kernels emit it; keys j >= J are zeroed
 //          with a select; e is added into four per-lane row sums and written to the wave's own [16][64] LDS rows
-//          (accumulator layout -> A-operand layout: wave-private, no block barrier);
+//          (accumulator layout -> A-operand layout: wave-private, no block barrier); the BIAS instantiations
+//          (eg_attention_bias) add a bias tile, loaded in accumulator layout a tile ahead, before the expf;
 //   O_acc += E * V_tile          16 x D per wave, D / 16 accumulators.
 // After the last tile the row sums are folded across the 16 lanes that share a row (xor shuffles 1, 2, 4, 8: a fixed
 // order), the accumulators divided, and the rows stored.  No atomics, no workspace, one launch per 2^22 blocks: two runs
@@ -43,10 +44,23 @@ struct AttnArgs {
   Items items;
 };
 
+// eg_attention_bias: the additive score bias, I x J per item.  Arguments of their own for the BIAS kernels, so that the
+// others take the arguments they took.
+struct AttnBiasArgs : AttnArgs {
+  In b;
+};
+
 // SUMS: also store each row's denominator (eg_attention_sums); a compile-time flag, so that eg_attention's kernels are the
 // ones they were.
-template <int KP, int DP, bool SUMS>
-__global__ __launch_bounds__(THREADS) void attention_f32_kernel(AttnArgs a) {
+// BIAS: e = expf(S * scale + bias), the bias an operand with a view of its own whose ld and strides may each be 0
+// (eg_attention_bias); again a compile-time flag, and the instantiations without it are the kernels they were.  The wave's
+// 16 x 64 bias tile is loaded in accumulator layout (attention_tile.hpp, load_bias) together with the K/V prefetch, one key
+// tile ahead: 16 scalar loads and 2 x 16 registers per lane, no LDS.  The addition is not fused with the multiplication:
+// the generated map kernel for `s * scale + m[...]` is two statements, `const float r5 = r3 * r4; const float r6 = r5 + r2;`
+// (host/codegen.cpp: one per instruction), compiled with -ffp-contract=off (rtc.cpp): two roundings, and so here, under the
+// same flag (Makefile).
+template <int KP, int DP, bool SUMS, bool BIAS>
+__global__ __launch_bounds__(THREADS) void attention_f32_kernel(std::conditional_t<BIAS, AttnBiasArgs, AttnArgs> a) {
   constexpr int KS = KP + 4, VS = DP + 16;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float* const Ks = lds;                      // [64][KS]; the Q tile first
@@ -81,10 +95,20 @@ __global__ __launch_bounds__(THREADS) void attention_f32_kernel(AttnArgs a) {
 
   TileRegs<KP> tk;
   TileRegs<DP> tv;
+  // the lane's bias: rows 4 g + r of the wave's, keys c + 16 nb of a tile; `next` is a tile ahead
+  [[maybe_unused]] BiasTile bias, bias_next;
+  [[maybe_unused]] const long bias_rows = a.I - i0 - w * 16 - 4 * g;
+  [[maybe_unused]] long ldb = 0;
+  [[maybe_unused]] const float* Bl = nullptr;
+  if constexpr (BIAS) {
+    ldb = a.b.v.ld;
+    Bl = item_base(a.b, b.outer, b.inner) + (i0 + w * 16 + 4 * g) * ldb + c;
+  }
   const long nt = (a.J + TILE_J - 1) / TILE_J;
   if (nt > 0) {
     load_rows<KP>(tk, Kk, ldk, a.J, a.K, a.k.vec != 0, tid);
     load_rows<DP>(tv, V, ldv, a.J, a.D, a.v.vec != 0, tid);
+    if constexpr (BIAS) load_bias(bias_next, Bl, ldb, bias_rows, a.J - c);
   }
   for (long t = 0; t < nt; ++t) {
     const long j0 = t * TILE_J;
@@ -92,9 +116,11 @@ __global__ __launch_bounds__(THREADS) void attention_f32_kernel(AttnArgs a) {
     store_rows<KP, KS>(tk, Ks, tid);
     store_rows<DP, VS>(tv, Vs, tid);
     __syncthreads();
+    if constexpr (BIAS) bias = bias_next;
     if (t + 1 < nt) {   // in flight during this tile's MFMAs
       load_rows<KP>(tk, Kk + (j0 + TILE_J) * ldk, ldk, a.J - j0 - TILE_J, a.K, a.k.vec != 0, tid);
       load_rows<DP>(tv, V + (j0 + TILE_J) * ldv, ldv, a.J - j0 - TILE_J, a.D, a.v.vec != 0, tid);
+      if constexpr (BIAS) load_bias(bias_next, Bl + j0 + TILE_J, ldb, bias_rows, a.J - j0 - TILE_J - c);
     }
 
     f32x4 s[4];
@@ -107,7 +133,8 @@ __global__ __launch_bounds__(THREADS) void attention_f32_kernel(AttnArgs a) {
       const bool live = j0 + nb * 16 + c < a.J;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const float x = s[nb][r] * a.scale;
+        float x = s[nb][r] * a.scale;
+        if constexpr (BIAS) x = x + bias.x[nb][r];
         float e = expf(x);
         e = live ? e : 0.f;   // a select: a key outside the problem adds exactly 0, whatever its score
         sum[r] += e;
@@ -157,11 +184,12 @@ __global__ __launch_bounds__(THREADS) void attention_f32_kernel(AttnArgs a) {
   }
 }
 
-template <int KP, int DP, bool SUMS>
-int launch(eg_ctx* ctx, unsigned grid, const Plan& p, const AttnArgs& args) {
-  const int rc = dynamic_lds_once<&attention_f32_kernel<KP, DP, SUMS>>(ctx, {lds_bytes_for(KP, DP)});
+// One launch of KERNEL with its own argument struct, Args: AttnBiasArgs, or its AttnArgs part.
+template <auto KERNEL, class Args, int KP, int DP>
+int launch(eg_ctx* ctx, unsigned grid, const Plan& p, const Args& args) {
+  const int rc = dynamic_lds_once<KERNEL>(ctx, {lds_bytes_for(KP, DP)});
   if (rc) return rc;
-  hipLaunchKernelGGL((attention_f32_kernel<KP, DP, SUMS>), dim3(grid), dim3(p.block), (size_t)p.lds_bytes, ctx->stream, args);
+  hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(p.block), (size_t)p.lds_bytes, ctx->stream, args);
   EG_HIP_CHECK(hipGetLastError());
   return EG_OK;
 }
@@ -172,16 +200,19 @@ namespace eg {
 namespace attention {
 
 // The one launcher: eg_attention and the model layer's attention launches (host/run.cpp) come here with Sums == NULL,
-// eg_attention_sums and a fit group's forward launch with the row sums' view.
+// eg_attention_sums and a fit group's forward launch with the row sums' view, eg_attention_bias and a model's biased
+// attention launch with the bias and its view.  Without a bias everything below is what it was.
 int attention_forward(eg_ctx* ctx, const Extents& e, float scale, const float* Q, View q, const float* Kk, View k, const float* V, View v, float* O,
-                      View o, int accumulate, float* Sums, View s) {
-  const char* const name = Sums ? "eg_attention_sums" : "eg_attention";   // the entry the messages speak of
+                      View o, int accumulate, float* Sums, View s, const float* Bias, View bv, const char* entry) {
+  const char* const name = entry ? entry : Sums ? "eg_attention_sums" : "eg_attention";   // the entry the messages speak of
   const long batch0 = e.batch0, batch1 = e.batch1, I = e.I, J = e.J, K = e.K, D = e.D;
   EG_REQUIRE(ctx, EG_ERR_INVALID, "%s: ctx is NULL", name);
   EG_REQUIRE(batch0 >= 0 && batch1 >= 0 && I >= 0 && J >= 0 && K >= 0 && D >= 0, EG_ERR_INVALID, "%s: negative extent", name);
   EG_REQUIRE(batch0 < (1L << 31) && batch1 < (1L << 31), EG_ERR_INVALID, "%s: a batch extent of 2^31 or more", name);
   EG_REQUIRE(q.stride0 >= 0 && q.stride1 >= 0 && k.stride0 >= 0 && k.stride1 >= 0 && v.stride0 >= 0 && v.stride1 >= 0, EG_ERR_INVALID,
              "%s: negative stride", name);
+  EG_REQUIRE(!Bias || (bv.stride0 >= 0 && bv.stride1 >= 0), EG_ERR_INVALID, "%s: negative stride of Bias", name);
+  EG_REQUIRE(!Bias || bv.ld == 0 || bv.ld >= J, EG_ERR_INVALID, "%s: ldb is neither 0 nor at least J", name);
   if (batch0 == 0 || batch1 == 0 || I == 0 || (D == 0 && !Sums)) return EG_OK;
   EG_REQUIRE(D == 0 || O, EG_ERR_INVALID, "%s: O is NULL", name);
   EG_REQUIRE(J == 0 || D == 0 || V, EG_ERR_INVALID, "%s: NULL operand", name);
@@ -202,21 +233,28 @@ int attention_forward(eg_ctx* ctx, const Extents& e, float scale, const float* Q
   static_cast<Extents&>(pr) = e;
   pr.q = {q, aligned16(Q)}, pr.k = {k, aligned16(Kk)}, pr.v = {v, aligned16(V)}, pr.o = {o, aligned16(O)};
   pr.sums = Sums != nullptr;
+  pr.has_bias = Bias != nullptr;
+  pr.bias = {bv, aligned16(Bias)};
   pr.cus = ctx->compute_units;
   const Plan p = plan_attention(pr);
   EG_REQUIRE(p.supported, EG_ERR_UNSUPPORTED, "%s: %s", name, p.reason);
 
-  AttnArgs args = {};
+  AttnBiasArgs args = {};
   args.q = {Q, q, p.vec_q}, args.k = {Kk, k, p.vec_k}, args.v = {V, v, p.vec_v};
-  args.o = {O, o, 0}, args.s = {Sums, s, 0};
+  args.o = {O, o, 0}, args.s = {Sums, s, 0}, args.b = {Bias, bv, p.vec_b};
   args.I = I, args.J = J, args.K = (int)K, args.D = (int)D;
   args.scale = scale;
   args.accumulate = accumulate;
-  // 9 kernels: the padded K x the padded D; 9 more that store the row sums
+  // 9 kernels: the padded K x the padded D; 9 more that store the row sums; as many again that add a bias
   return for_each_launch(name, p.items, p.cut(), batch1, [&](const Items& items, unsigned grid) {
     args.items = items;
     return dispatch_heads(p.kp, p.dp, [&](auto KP, auto DP) {
-      return Sums ? launch<KP(), DP(), true>(ctx, grid, p, args) : launch<KP(), DP(), false>(ctx, grid, p, args);
+      constexpr int kp = KP(), dp = DP();
+      if (Bias)
+        return Sums ? launch<&attention_f32_kernel<kp, dp, true, true>, AttnBiasArgs, kp, dp>(ctx, grid, p, args)
+                    : launch<&attention_f32_kernel<kp, dp, false, true>, AttnBiasArgs, kp, dp>(ctx, grid, p, args);
+      return Sums ? launch<&attention_f32_kernel<kp, dp, true, false>, AttnArgs, kp, dp>(ctx, grid, p, args)
+                  : launch<&attention_f32_kernel<kp, dp, false, false>, AttnArgs, kp, dp>(ctx, grid, p, args);
     });
   });
 }
@@ -238,4 +276,14 @@ extern "C" int eg_attention_sums(eg_ctx* ctx, int64_t batch0, int64_t batch1, in
                                  int64_t stride_o0, int64_t stride_o1, int accumulate, float* Sums, int64_t stride_s0, int64_t stride_s1) {
   return eg::attention::attention_forward(ctx, {batch0, batch1, I, J, K, D}, scale, Q, {ldq, stride_q0, stride_q1}, Kk, {ldk, stride_k0, stride_k1}, V,
                                           {ldv, stride_v0, stride_v1}, O, {ldo, stride_o0, stride_o1}, accumulate, Sums, {0, stride_s0, stride_s1});
+}
+
+extern "C" int eg_attention_bias(eg_ctx* ctx, int64_t batch0, int64_t batch1, int64_t I, int64_t J, int64_t K, int64_t D, float scale, const float* Q,
+                                 int64_t ldq, int64_t stride_q0, int64_t stride_q1, const float* Kk, int64_t ldk, int64_t stride_k0,
+                                 int64_t stride_k1, const float* V, int64_t ldv, int64_t stride_v0, int64_t stride_v1, float* O, int64_t ldo,
+                                 int64_t stride_o0, int64_t stride_o1, int accumulate, float* Sums, int64_t stride_s0, int64_t stride_s1,
+                                 const float* Bias, int64_t ldb, int64_t stride_b0, int64_t stride_b1) {
+  return eg::attention::attention_forward(ctx, {batch0, batch1, I, J, K, D}, scale, Q, {ldq, stride_q0, stride_q1}, Kk, {ldk, stride_k0, stride_k1}, V,
+                                          {ldv, stride_v0, stride_v1}, O, {ldo, stride_o0, stride_o1}, accumulate, Sums, {0, stride_s0, stride_s1}, Bias,
+                                          {ldb, stride_b0, stride_b1}, "eg_attention_bias");
 }

@@ -47,6 +47,14 @@ struct GradArgs {
   Items items;
 };
 
+// eg_attention_bias_grad: the forward's score bias.  Arguments of their own for the BIAS kernels, so that the others take the
+// arguments they took.
+struct GradBiasArgs : GradArgs {
+  In b;
+};
+template <bool BIAS>
+using ArgsOf = std::conditional_t<BIAS, GradBiasArgs, GradArgs>;
+
 constexpr int TILE = 64;
 
 // A quarter of each of the tile's 64 rows of O per thread: thread tid holds columns 16 n + 4 (tid & 3) + {0, 1, 2, 3} of row
@@ -158,8 +166,14 @@ __device__ __forceinline__ void store_out(const float* __restrict__ lds, float* 
   }
 }
 
-template <int KP, int DP>
-__global__ __launch_bounds__(THREADS) void attention_dq_kernel(GradArgs a) {
+// BIAS (both kernels): p_ij = expf(scale * s_ij + bias_ij) / L_i, the bias an operand with a view of its own whose ld and
+// strides may each be 0; a compile-time flag, and the instantiations without it are the kernels they were.  One
+// multiplication, one addition, not fused: what the forward computes, so that L is the sum of these very terms.  The dQ kernel
+// holds the wave's 16 x 64 bias tile in accumulator layout, as the forward does; the dK/dV kernel holds its transpose, where
+// a lane's four elements are four consecutive keys of one query row: one 16-byte load per nb when the plan's vec_b allows it.
+// Both load a tile ahead, with the other operands' next tiles, straight into registers: no LDS.  No gradient of the bias.
+template <int KP, int DP, bool BIAS>
+__global__ __launch_bounds__(THREADS) void attention_dq_kernel(ArgsOf<BIAS> a) {
   constexpr int KS = KP + GRAD_PAD_BOTH, VS = DP + GRAD_PAD_NT;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float* const Ks = lds;                  // [64][KS]: the Q tile first, dQ last
@@ -213,10 +227,20 @@ __global__ __launch_bounds__(THREADS) void attention_dq_kernel(GradArgs a) {
 #pragma unroll
   for (int nb = 0; nb < KP / 16; ++nb) dq[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
 
+  // the lane's bias: rows 4 g + r of the wave's, keys c + 16 nb of a tile; `next` is a tile ahead
+  [[maybe_unused]] BiasTile bias, bias_next;
+  [[maybe_unused]] const long bias_rows = rows - w * 16 - 4 * g;
+  [[maybe_unused]] long ldb = 0;
+  [[maybe_unused]] const float* Bl = nullptr;
+  if constexpr (BIAS) {
+    ldb = a.b.v.ld;
+    Bl = item_base(a.b, b.outer, b.inner) + (i0 + w * 16 + 4 * g) * ldb + c;
+  }
   const long nt = (a.J + TILE - 1) / TILE;
   if (nt > 0) {
     load_rows<KP>(tk, Kk, ldk, a.J, a.K, a.k.vec != 0, tid);
     load_rows<DP>(tv, V, ldv, a.J, a.D, a.v.vec != 0, tid);
+    if constexpr (BIAS) load_bias(bias_next, Bl, ldb, bias_rows, a.J - c);
   }
   for (long t = 0; t < nt; ++t) {
     const long j0 = t * TILE;
@@ -224,9 +248,11 @@ __global__ __launch_bounds__(THREADS) void attention_dq_kernel(GradArgs a) {
     store_rows<KP, KS>(tk, Ks, tid);
     store_rows<DP, VS>(tv, Vs, tid);
     __syncthreads();
+    if constexpr (BIAS) bias = bias_next;
     if (t + 1 < nt) {   // in flight during this tile's MFMAs
       load_rows<KP>(tk, Kk + (j0 + TILE) * ldk, ldk, a.J - j0 - TILE, a.K, a.k.vec != 0, tid);
       load_rows<DP>(tv, V + (j0 + TILE) * ldv, ldv, a.J - j0 - TILE, a.D, a.v.vec != 0, tid);
+      if constexpr (BIAS) load_bias(bias_next, Bl + j0 + TILE, ldb, bias_rows, a.J - j0 - TILE - c);
     }
 
     f32x4 s[4], dp[4];
@@ -248,7 +274,9 @@ __global__ __launch_bounds__(THREADS) void attention_dq_kernel(GradArgs a) {
       const bool live = j0 + nb * 16 + c < a.J;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const float p = expf(s[nb][r] * a.scale) * inv[r];
+        float x = s[nb][r] * a.scale;
+        if constexpr (BIAS) x = x + bias.x[nb][r];
+        const float p = expf(x) * inv[r];
         const float ds = (a.scale * p) * (dp[nb][r] - delta[r]);
         Ew[(4 * g + r) * ES + nb * 16 + c] = live ? ds : 0.f;   // a select: a key outside the problem adds exactly 0
       }
@@ -270,8 +298,8 @@ __global__ __launch_bounds__(THREADS) void attention_dq_kernel(GradArgs a) {
   store_out<KP, KS>(Ks, dQ, a.dq.v.ld, rows, a.K, a.dq.vec != 0, a.acc_dq != 0, tid);
 }
 
-template <int KP, int DP>
-__global__ __launch_bounds__(THREADS) void attention_dkv_kernel(GradArgs a) {
+template <int KP, int DP, bool BIAS>
+__global__ __launch_bounds__(THREADS) void attention_dkv_kernel(ArgsOf<BIAS> a) {
   constexpr int QS = KP + GRAD_PAD_BOTH, DS = DP + GRAD_PAD_BOTH;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float* const Qs = lds;                  // [64][QS]: the K tile first, dK last
@@ -319,12 +347,23 @@ __global__ __launch_bounds__(THREADS) void attention_dkv_kernel(GradArgs a) {
 #pragma unroll
   for (int r = 0; r < 4; ++r) klive[r] = w * 16 + 4 * g + r < keys;
 
+  // the lane's bias, transposed: keys 4 g + r of the wave's, query rows c + 16 nb of a tile; `next` is a tile ahead
+  [[maybe_unused]] BiasTile bias, bias_next;
+  [[maybe_unused]] const long bias_keys = keys - w * 16 - 4 * g;
+  [[maybe_unused]] long ldb = 0;
+  [[maybe_unused]] const float* Bl = nullptr;
+  [[maybe_unused]] bool vec_b = false;
+  if constexpr (BIAS) {
+    ldb = a.b.v.ld, vec_b = a.b.vec != 0;
+    Bl = item_base(a.b, b.outer, b.inner) + c * ldb + j0 + w * 16 + 4 * g;
+  }
   const long nt = (a.I + TILE - 1) / TILE;
   if (nt > 0) {
     load_rows<KP>(tq, Q, ldq, a.I, a.K, a.q.vec != 0, tid);
     load_rows<DP>(td, dO, lddo, a.I, a.D, a.dout.vec != 0, tid);
     load_o_part<DP>(po, O, ldo, a.I, a.D, a.o.vec != 0, tid);
     sums = load_sums(S, a.I, a.s.vec != 0, tid);
+    if constexpr (BIAS) load_bias_t(bias_next, Bl, ldb, a.I - c, bias_keys, vec_b);
   }
   for (long t = 0; t < nt; ++t) {
     const long i0 = t * TILE;
@@ -337,12 +376,14 @@ __global__ __launch_bounds__(THREADS) void attention_dkv_kernel(GradArgs a) {
       const float d = row_delta<DP>(Ds, DS, po, tid);
       if ((tid & 3) == 0) St[2 * (tid >> 2) + 1] = d;
     }
+    if constexpr (BIAS) bias = bias_next;
     if (t + 1 < nt) {   // in flight during this tile's MFMAs
       const long n0 = i0 + TILE;
       load_rows<KP>(tq, Q + n0 * ldq, ldq, a.I - n0, a.K, a.q.vec != 0, tid);
       load_rows<DP>(td, dO + n0 * lddo, lddo, a.I - n0, a.D, a.dout.vec != 0, tid);
       load_o_part<DP>(po, O + n0 * ldo, ldo, a.I - n0, a.D, a.o.vec != 0, tid);
       sums = load_sums(S + n0, a.I - n0, a.s.vec != 0, tid);
+      if constexpr (BIAS) load_bias_t(bias_next, Bl + n0 * ldb, ldb, a.I - n0 - c, bias_keys, vec_b);
     }
     __syncthreads();   // delta of every row is in St
 
@@ -371,7 +412,9 @@ __global__ __launch_bounds__(THREADS) void attention_dkv_kernel(GradArgs a) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const bool live = qlive && klive[r];
-        const float p = expf(s[nb][r] * a.scale) * inv;
+        float x = s[nb][r] * a.scale;
+        if constexpr (BIAS) x = x + bias.x[nb][r];
+        const float p = expf(x) * inv;
         const float ds = (a.scale * p) * (dp[nb][r] - delta);
         Ew[(4 * g + r) * ES + col] = live ? p : 0.f;
         s[nb][r] = live ? ds : 0.f;
@@ -409,14 +452,14 @@ __global__ __launch_bounds__(THREADS) void attention_dkv_kernel(GradArgs a) {
 }
 
 // One launch of one of the two kernels; the attributes of both are set together, once per device and instantiation.
-template <int KP, int DP>
-int launch(eg_ctx* ctx, bool dkv, unsigned grid, const GradPlan& p, const GradArgs& args) {
-  const int rc = dynamic_lds_once<&attention_dq_kernel<KP, DP>, &attention_dkv_kernel<KP, DP>>(ctx, {grad_dq_lds_bytes(KP, DP), grad_dkv_lds_bytes(KP, DP)});
+template <auto DQ_KERNEL, auto DKV_KERNEL, class Args, int KP, int DP>
+int launch(eg_ctx* ctx, bool dkv, unsigned grid, const GradPlan& p, const Args& args) {
+  const int rc = dynamic_lds_once<DQ_KERNEL, DKV_KERNEL>(ctx, {grad_dq_lds_bytes(KP, DP), grad_dkv_lds_bytes(KP, DP)});
   if (rc) return rc;
   if (dkv)
-    hipLaunchKernelGGL((attention_dkv_kernel<KP, DP>), dim3(grid), dim3(p.block), (size_t)p.dkv.lds_bytes, ctx->stream, args);
+    hipLaunchKernelGGL(DKV_KERNEL, dim3(grid), dim3(p.block), (size_t)p.dkv.lds_bytes, ctx->stream, args);
   else
-    hipLaunchKernelGGL((attention_dq_kernel<KP, DP>), dim3(grid), dim3(p.block), (size_t)p.dq.lds_bytes, ctx->stream, args);
+    hipLaunchKernelGGL(DQ_KERNEL, dim3(grid), dim3(p.block), (size_t)p.dq.lds_bytes, ctx->stream, args);
   EG_HIP_CHECK(hipGetLastError());
   return EG_OK;
 }
@@ -428,34 +471,37 @@ namespace attention {
 
 int attention_grad(eg_ctx* ctx, const Extents& e, float scale, const float* Q, View q, const float* Kk, View k, const float* V, View v,
                    const float* O, View o, const float* Sums, View s, const float* dO, View dout, float* dQ, View dq, float* dK, View dk, float* dV,
-                   View dv, int accumulate) {
+                   View dv, int accumulate, const float* Bias, View bv, const char* entry) {
+  const char* const name = entry ? entry : "eg_attention_grad";   // the entry the messages speak of
   const long batch0 = e.batch0, batch1 = e.batch1, I = e.I, J = e.J, K = e.K, D = e.D;
-  EG_REQUIRE(ctx, EG_ERR_INVALID, "eg_attention_grad: ctx is NULL");
-  EG_REQUIRE(batch0 >= 0 && batch1 >= 0 && I >= 0 && J >= 0 && K >= 0 && D >= 0, EG_ERR_INVALID, "eg_attention_grad: negative extent");
-  EG_REQUIRE(batch0 < (1L << 31) && batch1 < (1L << 31), EG_ERR_INVALID, "eg_attention_grad: a batch extent of 2^31 or more");
+  EG_REQUIRE(ctx, EG_ERR_INVALID, "%s: ctx is NULL", name);
+  EG_REQUIRE(batch0 >= 0 && batch1 >= 0 && I >= 0 && J >= 0 && K >= 0 && D >= 0, EG_ERR_INVALID, "%s: negative extent", name);
+  EG_REQUIRE(batch0 < (1L << 31) && batch1 < (1L << 31), EG_ERR_INVALID, "%s: a batch extent of 2^31 or more", name);
   EG_REQUIRE(q.stride0 >= 0 && q.stride1 >= 0 && k.stride0 >= 0 && k.stride1 >= 0 && v.stride0 >= 0 && v.stride1 >= 0 && o.stride0 >= 0 &&
                  o.stride1 >= 0 && s.stride0 >= 0 && s.stride1 >= 0 && dout.stride0 >= 0 && dout.stride1 >= 0,
-             EG_ERR_INVALID, "eg_attention_grad: negative stride");
-  EG_REQUIRE((accumulate & ~7) == 0, EG_ERR_INVALID, "eg_attention_grad: accumulate has bits other than 1 (dQ), 2 (dK) and 4 (dV)");
+             EG_ERR_INVALID, "%s: negative stride", name);
+  EG_REQUIRE(!Bias || (bv.stride0 >= 0 && bv.stride1 >= 0), EG_ERR_INVALID, "%s: negative stride of Bias", name);
+  EG_REQUIRE(!Bias || bv.ld == 0 || bv.ld >= J, EG_ERR_INVALID, "%s: ldb is neither 0 nor at least J", name);
+  EG_REQUIRE((accumulate & ~7) == 0, EG_ERR_INVALID, "%s: accumulate has bits other than 1 (dQ), 2 (dK) and 4 (dV)", name);
   if (batch0 == 0 || batch1 == 0) return EG_OK;
   const bool want_dq = I > 0 && K > 0, want_dk = J > 0 && K > 0, want_dv = J > 0 && D > 0;   // the outputs that have elements
   if (!want_dq && !want_dk && !want_dv) return EG_OK;
-  EG_REQUIRE((!want_dq || dQ) && (!want_dk || dK) && (!want_dv || dV), EG_ERR_INVALID, "eg_attention_grad: NULL output");
+  EG_REQUIRE((!want_dq || dQ) && (!want_dk || dK) && (!want_dv || dV), EG_ERR_INVALID, "%s: NULL output", name);
   if (I > 0 && J > 0) {
-    EG_REQUIRE(Sums, EG_ERR_INVALID, "eg_attention_grad: NULL operand (Sums)");
-    EG_REQUIRE(K == 0 || (Q && Kk), EG_ERR_INVALID, "eg_attention_grad: NULL operand (Q or Kk)");
-    EG_REQUIRE(D == 0 || (V && O && dO), EG_ERR_INVALID, "eg_attention_grad: NULL operand (V, O or dO)");
+    EG_REQUIRE(Sums, EG_ERR_INVALID, "%s: NULL operand (Sums)", name);
+    EG_REQUIRE(K == 0 || (Q && Kk), EG_ERR_INVALID, "%s: NULL operand (Q or Kk)", name);
+    EG_REQUIRE(D == 0 || (V && O && dO), EG_ERR_INVALID, "%s: NULL operand (V, O or dO)", name);
   }
   EG_REQUIRE(q.ld >= K && k.ld >= K && dq.ld >= K && dk.ld >= K && v.ld >= D && o.ld >= D && dout.ld >= D && dv.ld >= D, EG_ERR_INVALID,
-             "eg_attention_grad: leading dimension smaller than the row length");
+             "%s: leading dimension smaller than the row length", name);
   EG_REQUIRE(!want_dq || eg::gemm::batched2_c_distinct(batch0, dq.stride0, batch1, dq.stride1, I, dq.ld, K), EG_ERR_INVALID,
-             "eg_attention_grad: lddq, stride_dq0 and stride_dq1 make elements of dQ share an address");
+             "%s: lddq, stride_dq0 and stride_dq1 make elements of dQ share an address", name);
   EG_REQUIRE(!want_dk || eg::gemm::batched2_c_distinct(batch0, dk.stride0, batch1, dk.stride1, J, dk.ld, K), EG_ERR_INVALID,
-             "eg_attention_grad: lddk, stride_dk0 and stride_dk1 make elements of dK share an address");
+             "%s: lddk, stride_dk0 and stride_dk1 make elements of dK share an address", name);
   EG_REQUIRE(!want_dv || eg::gemm::batched2_c_distinct(batch0, dv.stride0, batch1, dv.stride1, J, dv.ld, D), EG_ERR_INVALID,
-             "eg_attention_grad: lddv, stride_dv0 and stride_dv1 make elements of dV share an address");
-  EG_REQUIRE(K <= MAX_HEAD, EG_ERR_UNSUPPORTED, "eg_attention_grad: K = %ld is above the limit of %d", K, MAX_HEAD);
-  EG_REQUIRE(D <= MAX_HEAD, EG_ERR_UNSUPPORTED, "eg_attention_grad: D = %ld is above the limit of %d", D, MAX_HEAD);
+             "%s: lddv, stride_dv0 and stride_dv1 make elements of dV share an address", name);
+  EG_REQUIRE(K <= MAX_HEAD, EG_ERR_UNSUPPORTED, "%s: K = %ld is above the limit of %d", name, K, MAX_HEAD);
+  EG_REQUIRE(D <= MAX_HEAD, EG_ERR_UNSUPPORTED, "%s: D = %ld is above the limit of %d", name, D, MAX_HEAD);
 
   // An output that is all zeros (an empty sum) is written as zeros when its bit is clear and left alone otherwise.
   const bool acc_dq = accumulate & 1, acc_dk = accumulate & 2, acc_dv = accumulate & 4;
@@ -470,22 +516,29 @@ int attention_grad(eg_ctx* ctx, const Extents& e, float scale, const float* Q, V
   static_cast<Extents&>(pr) = e;
   pr.q = {q, aligned16(Q)}, pr.k = {k, aligned16(Kk)}, pr.v = {v, aligned16(V)}, pr.o = {o, aligned16(O)}, pr.s = {s, aligned16(Sums)};
   pr.dout = {dout, aligned16(dO)}, pr.dq = {dq, aligned16(dQ)}, pr.dk = {dk, aligned16(dK)}, pr.dv = {dv, aligned16(dV)};
+  pr.has_bias = Bias != nullptr;
+  pr.bias = {bv, aligned16(Bias)};
   pr.cus = ctx->compute_units;
   const GradPlan p = plan_attention_grad(pr);
-  EG_REQUIRE(p.supported, EG_ERR_UNSUPPORTED, "eg_attention_grad: %s", p.reason);
+  EG_REQUIRE(p.supported, EG_ERR_UNSUPPORTED, "%s: %s", name, p.reason);
 
-  GradArgs args = {};
+  GradBiasArgs args = {};
   args.q = {Q, q, p.vec_q}, args.k = {Kk, k, p.vec_k}, args.v = {V, v, p.vec_v}, args.o = {O, o, p.vec_o}, args.s = {Sums, s, p.vec_s};
   args.dout = {dO, dout, p.vec_do}, args.dq = {dQ, dq, p.vec_dq}, args.dk = {dK, dk, p.vec_dk}, args.dv = {dV, dv, p.vec_dv};
+  args.b = {Bias, bv, p.vec_b};
   args.I = I, args.J = J, args.K = (int)K, args.D = (int)D;
   args.scale = scale;
   args.acc_dq = acc_dq, args.acc_dk = acc_dk, args.acc_dv = acc_dv;
   args.put_dk = put_dk, args.put_dv = put_dv;
-  // 9 instantiations of each kernel: the padded K x the padded D
+  // 9 instantiations of each kernel: the padded K x the padded D; as many again that add the bias
   auto run = [&](bool dkv, const GradKernel& kernel) {
-    return for_each_launch("eg_attention_grad", p.items, kernel, batch1, [&](const Items& items, unsigned grid) {
+    return for_each_launch(name, p.items, kernel, batch1, [&](const Items& items, unsigned grid) {
       args.items = items;
-      return dispatch_heads(p.kp, p.dp, [&](auto KP, auto DP) { return launch<KP(), DP()>(ctx, dkv, grid, p, args); });
+      return dispatch_heads(p.kp, p.dp, [&](auto KP, auto DP) {
+        constexpr int kp = KP(), dp = DP();
+        return Bias ? launch<&attention_dq_kernel<kp, dp, true>, &attention_dkv_kernel<kp, dp, true>, GradBiasArgs, kp, dp>(ctx, dkv, grid, p, args)
+                    : launch<&attention_dq_kernel<kp, dp, false>, &attention_dkv_kernel<kp, dp, false>, GradArgs, kp, dp>(ctx, dkv, grid, p, args);
+      });
     });
   };
   if (run_dq) rc = run(false, p.dq);
@@ -510,4 +563,21 @@ extern "C" int eg_attention_grad(eg_ctx* ctx, int64_t batch0, int64_t batch1, in
                                        {ldv, stride_v0, stride_v1}, O, {ldo, stride_o0, stride_o1}, Sums, {0, stride_s0, stride_s1}, dO,
                                        {lddo, stride_do0, stride_do1}, dQ, {lddq, stride_dq0, stride_dq1}, dK, {lddk, stride_dk0, stride_dk1}, dV,
                                        {lddv, stride_dv0, stride_dv1}, accumulate);
+}
+
+extern "C" int eg_attention_bias_grad(eg_ctx* ctx, int64_t batch0, int64_t batch1, int64_t I, int64_t J, int64_t K, int64_t D, float scale,
+                                      const float* Q, int64_t ldq, int64_t stride_q0, int64_t stride_q1,
+                                      const float* Kk, int64_t ldk, int64_t stride_k0, int64_t stride_k1,
+                                      const float* V, int64_t ldv, int64_t stride_v0, int64_t stride_v1,
+                                      const float* O, int64_t ldo, int64_t stride_o0, int64_t stride_o1,
+                                      const float* Sums, int64_t stride_s0, int64_t stride_s1,
+                                      const float* dO, int64_t lddo, int64_t stride_do0, int64_t stride_do1,
+                                      float* dQ, int64_t lddq, int64_t stride_dq0, int64_t stride_dq1,
+                                      float* dK, int64_t lddk, int64_t stride_dk0, int64_t stride_dk1,
+                                      float* dV, int64_t lddv, int64_t stride_dv0, int64_t stride_dv1, int accumulate,
+                                      const float* Bias, int64_t ldb, int64_t stride_b0, int64_t stride_b1) {
+  return eg::attention::attention_grad(ctx, {batch0, batch1, I, J, K, D}, scale, Q, {ldq, stride_q0, stride_q1}, Kk, {ldk, stride_k0, stride_k1}, V,
+                                       {ldv, stride_v0, stride_v1}, O, {ldo, stride_o0, stride_o1}, Sums, {0, stride_s0, stride_s1}, dO,
+                                       {lddo, stride_do0, stride_do1}, dQ, {lddq, stride_dq0, stride_dq1}, dK, {lddk, stride_dk0, stride_dk1}, dV,
+                                       {lddv, stride_dv0, stride_dv1}, accumulate, Bias, {ldb, stride_b0, stride_b1}, "eg_attention_bias_grad");
 }

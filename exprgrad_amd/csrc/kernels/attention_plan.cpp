@@ -41,6 +41,7 @@ Plan plan_forward(const Problem& p, bool f64) {
   r.vec_q = f64 ? operand_vec16_f64(p.q) : operand_vec16(p.q);
   r.vec_k = f64 ? operand_vec16_f64(p.k) : operand_vec16(p.k);
   r.vec_v = f64 ? operand_vec16_f64(p.v) : operand_vec16(p.v);
+  r.vec_b = !f64 && p.has_bias && operand_vec16(p.bias);   // needs no LDS: lds_bytes is what it was
   r.items = p.batch0 * p.batch1;
   const Cut c = cut_items(r.items, tiles_i);
   r.tiles_i = c.tiles, r.grid = c.grid, r.items_per_launch = c.items_per_launch, r.launches = c.launches;
@@ -95,6 +96,7 @@ GradPlan plan_backward(const GradProblem& p, bool f64) {
   r.vec_q = vec(p.q), r.vec_k = vec(p.k), r.vec_v = vec(p.v), r.vec_o = vec(p.o);
   r.vec_s = vec(p.s), r.vec_do = vec(p.dout);
   r.vec_dq = vec(p.dq), r.vec_dk = vec(p.dk), r.vec_dv = vec(p.dv);
+  r.vec_b = !f64 && p.has_bias && operand_vec16(p.bias);
   r.items = p.batch0 * p.batch1;
   static_cast<Cut&>(r.dq) = cut_items(r.items, tiles_i);
   static_cast<Cut&>(r.dkv) = cut_items(r.items, tiles_j);

@@ -36,6 +36,8 @@ struct Operand : View {
 struct Problem : Extents {
   Operand q, k, v, o;
   bool sums = false;   // eg_attention_sums: the row sums are stored too, and D == 0 still has them to store
+  bool has_bias = false;   // eg_attention_bias: the additive score bias, I x J per item; its ld and strides may each be 0
+  Operand bias;
   int cus = 256;
 };
 
@@ -45,6 +47,7 @@ struct Plan {
   int tile_i = TILE_I, tile_j = TILE_J;
   int kp = 0, dp = 0;        // K and D as the kernel is instantiated: 32, 64 or 128, the rest zero-filled
   bool vec_q = false, vec_k = false, vec_v = false;   // 16-byte loads of that operand
+  bool vec_b = false;        // the bias's rows start 16-byte aligned (operand_vec16; an ld of 0 is a multiple of 4)
   long tiles_i = 0;          // blocks per item: ceil(I / 64)
   long items = 0;            // batch0 * batch1
   long grid = 0, items_per_launch = 0, launches = 0;   // with tiles_i, the plan's Cut
@@ -102,6 +105,8 @@ Plan plan_attention_f64(const Problem& p);
 // keys (dK and dV).  Both keep the block's own rows in registers and walk the other axis in tiles of 64.
 struct GradProblem : Extents {
   Operand q, k, v, o, s, dout, dq, dk, dv;   // s: the row sums
+  bool has_bias = false;                     // eg_attention_bias_grad: the forward's score bias
+  Operand bias;
   int cus = 256;
 };
 
@@ -118,6 +123,7 @@ struct GradPlan {
   int kp = 0, dp = 0;
   // 16-byte accesses per operand: loads of Q, Kk, V, O, Sums and dO, stores (and, accumulating, loads) of dQ, dK and dV
   bool vec_q = false, vec_k = false, vec_v = false, vec_o = false, vec_s = false, vec_do = false, vec_dq = false, vec_dk = false, vec_dv = false;
+  bool vec_b = false;   // 16-byte loads of the bias in the dK/dV kernel, where a lane holds four consecutive keys of a row
   long items = 0;
   GradKernel dq, dkv;
   int block = THREADS;

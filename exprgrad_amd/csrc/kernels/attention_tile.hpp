@@ -86,6 +86,48 @@ __device__ __forceinline__ void store_rows(const TileRegs<WP>& t, float* __restr
   }
 }
 
+// ---- the additive score bias (eg_attention_bias, eg_attention_bias_grad) ------------------------------------------------
+// The bias of a wave's 16 x 64 tile of scores, in the layout the accumulators have: x[nb][r] belongs to s[nb][r].  It goes
+// from global memory straight into these 16 registers of a lane, one tile ahead of its use: no LDS, no barrier.
+struct BiasTile {
+  f32x4 x[4];
+};
+
+// Forward and dQ kernels: lane (c, g) holds rows 4 g + r of the wave's 16 query rows and keys 16 nb + c of the tile; `p` is
+// the lane's element (nb, r) = (0, 0), `rows` and `keys` what the problem has left from there (either may be <= 0).  A wave's
+// load (one nb, one r) reads four row segments of 64 bytes.  ldb == 0 makes the four rows one.  Rows i >= I and keys j >= J
+// are 0 and not read.
+__device__ __forceinline__ void load_bias(BiasTile& t, const float* __restrict__ p, long ldb, long rows, long keys) {
+#pragma unroll
+  for (int nb = 0; nb < 4; ++nb) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) t.x[nb][r] = (r < rows && 16 * nb < keys) ? p[r * ldb + 16 * nb] : 0.f;
+  }
+}
+
+// dK/dV kernel, the transpose: lane (c, g) holds keys 4 g + r of the wave's 16 keys and query rows 16 nb + c of the tile, so
+// a lane's four r are four consecutive keys of one query row: one 16-byte load when `vec` (the plan's vec_b: every row of
+// every item starts 16-byte aligned, and a lane's first key is a multiple of 4) and the four keys are all inside the
+// problem, element loads otherwise.  `p` is the lane's element (0, 0), `rows` and `keys` what is left from there.
+__device__ __forceinline__ void load_bias_t(BiasTile& t, const float* __restrict__ p, long ldb, long rows, long keys, bool vec) {
+#pragma unroll
+  for (int nb = 0; nb < 4; ++nb) {
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (16 * nb < rows && keys > 0) {
+      const float* const q = p + 16 * nb * ldb;
+      if (vec && keys >= 4) {
+        v = *reinterpret_cast<const f32x4*>(q);
+      } else {
+        v[0] = q[0];
+        if (keys > 1) v[1] = q[1];
+        if (keys > 2) v[2] = q[2];
+        if (keys > 3) v[3] = q[3];
+      }
+    }
+    t.x[nb] = v;
+  }
+}
+
 // What one wave wrote to its own LDS rows becomes visible to its other lanes: no block barrier.
 __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");

@@ -92,6 +92,28 @@ def attention_grad(ctx, batch0, batch1, I, J, K, D, scale, Q, ldq, strides_q, Kk
          strides_dk[1], _p(dV), lddv, strides_dv[0], strides_dv[1], int(accumulate))
 
 
+def attention_bias(ctx, batch0, batch1, I, J, K, D, scale, Q, ldq, strides_q, Kk, ldk, strides_k, V, ldv, strides_v, O, ldo, strides_o, Sums,
+                   strides_s, Bias, ldb, strides_b, accumulate=False):
+    """`attention_sums` with an additive score bias: e_ij = exp(scale * q_i . k_j + Bias[i * ldb + j]), item (o, i1) of Bias at
+    Bias + o * strides_b[0] + i1 * strides_b[1].  Each of ldb and the two strides may be 0: the bias is then shared by the query
+    rows (a key-padding mask), over batch0 or over batch1.  -Inf masks a key; Sums = None and Bias = None are allowed."""
+    call("eg_attention_bias", ctx.handle, batch0, batch1, I, J, K, D, float(scale), _p(Q), ldq, strides_q[0], strides_q[1], _p(Kk), ldk,
+         strides_k[0], strides_k[1], _p(V), ldv, strides_v[0], strides_v[1], _p(O), ldo, strides_o[0], strides_o[1], int(accumulate), _p(Sums),
+         strides_s[0], strides_s[1], _p(Bias), ldb, strides_b[0], strides_b[1])
+
+
+def attention_bias_grad(ctx, batch0, batch1, I, J, K, D, scale, Q, ldq, strides_q, Kk, ldk, strides_k, V, ldv, strides_v, O, ldo, strides_o, Sums,
+                        strides_s, dO, lddo, strides_do, dQ, lddq, strides_dq, dK, lddk, strides_dk, dV, lddv, strides_dv, Bias, ldb, strides_b,
+                        accumulate=0):
+    """`attention_grad` for the biased forward: O and Sums from attention_bias (accumulate = False) on the same operands and the
+    same Bias; p_ij = exp(scale * q_i . k_j + bias_ij) / L_i.  No gradient of the bias is produced.  Bias = None is
+    `attention_grad`."""
+    call("eg_attention_bias_grad", ctx.handle, batch0, batch1, I, J, K, D, float(scale), _p(Q), ldq, strides_q[0], strides_q[1], _p(Kk), ldk,
+         strides_k[0], strides_k[1], _p(V), ldv, strides_v[0], strides_v[1], _p(O), ldo, strides_o[0], strides_o[1], _p(Sums), strides_s[0],
+         strides_s[1], _p(dO), lddo, strides_do[0], strides_do[1], _p(dQ), lddq, strides_dq[0], strides_dq[1], _p(dK), lddk, strides_dk[0],
+         strides_dk[1], _p(dV), lddv, strides_dv[0], strides_dv[1], int(accumulate), _p(Bias), ldb, strides_b[0], strides_b[1])
+
+
 def attention_grad_f64(ctx, batch0, batch1, I, J, K, D, scale, Q, ldq, strides_q, Kk, ldk, strides_k, V, ldv, strides_v, O, ldo, strides_o, Sums,
                        strides_s, dO, lddo, strides_do, dQ, lddq, strides_dq, dK, lddk, strides_dk, dV, lddv, strides_dv, accumulate=0):
     """The float64 form of `attention_grad`: O and Sums from attention_sums_f64 (accumulate = False), every operand in doubles

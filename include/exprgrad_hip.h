@@ -385,6 +385,64 @@ int eg_attention_grad_f64(eg_ctx* ctx, int64_t batch0, int64_t batch1, int64_t I
                           double* dK, int64_t lddk, int64_t stride_dk0, int64_t stride_dk1,
                           double* dV, int64_t lddv, int64_t stride_dv0, int64_t stride_dv1, int accumulate);
 
+/* eg_attention_sums with an additive score bias: the first 28 arguments are eg_attention_sums', and
+ *   e_ij = expf(scale * q_i . k_j + bias_ij),   L_i = sum_j e_ij,   O[i,:] (+)= (sum_j e_ij * V[j,:]) / L_i
+ * with bias_ij of item (o, i1) at Bias[o * stride_b0 + i1 * stride_b1 + i * ldb + j], i in [0, I), j in [0, J).  One operand
+ * covers a causal or key-padding mask (-Inf), an ALiBi slope and a relative-position table; nothing of size I x J but the
+ * bias itself is read, and nothing of that size is stored.  The multiplication by scale and the addition are two roundings,
+ * not a fused multiply-add: what a generated map kernel `s * scale + m[...]` computes under the library's -ffp-contract=off.
+ *   - Broadcast forms: stride_b0 == 0 shares the bias over batch0, stride_b1 == 0 over batch1 (the heads), and ldb == 0 makes
+ *     one row of J floats the bias of every query row (the key-padding mask).  Any combination is allowed; Bias may alias
+ *     itself freely, it is only read.
+ *   - EG_ERR_INVALID, with a message that names eg_attention_bias: a negative stride_b0 or stride_b1; 0 < ldb < J.
+ *   - Bias == NULL means no bias: O and Sums have the bits eg_attention_sums gives on the first 28 arguments, and ldb and
+ *     the strides of Bias are not looked at.  Sums == NULL is allowed, with or without a bias.
+ *   - Every other refusal, every empty extent, accumulate, Sums and the rules of O are eg_attention_sums', with a message
+ *     that names eg_attention_bias.
+ *   - No alignment is required of Bias.  The forward reads it element by element, a wave's load four row segments of 64 bytes
+ *     (kernels/attention_tile.hpp, load_bias), one key tile ahead of its use; it does not pass through LDS.
+ *   - Elements of Bias outside the views are never read, whatever they hold: not rows i >= I, not keys j >= J, not the
+ *     padding behind a row's J floats.
+ * Special values are those of the program as written: a bias of -Inf adds exactly 0 to both sums (the key is masked); a row
+ * whose keys are all -Inf has L_i = 0 and is 0 / 0 = NaN; a +Inf or a NaN in a row's bias makes that row NaN; the rows next
+ * to such a row are not touched.  The same kernels as eg_attention_sums with one more compile-time flag
+ * (kernels/attention_f32.hip); two calls give the same bits. */
+int eg_attention_bias(eg_ctx* ctx, int64_t batch0, int64_t batch1, int64_t I, int64_t J, int64_t K, int64_t D, float scale,
+                      const float* Q, int64_t ldq, int64_t stride_q0, int64_t stride_q1,
+                      const float* Kk, int64_t ldk, int64_t stride_k0, int64_t stride_k1,
+                      const float* V, int64_t ldv, int64_t stride_v0, int64_t stride_v1,
+                      float* O, int64_t ldo, int64_t stride_o0, int64_t stride_o1, int accumulate,
+                      float* Sums, int64_t stride_s0, int64_t stride_s1,
+                      const float* Bias, int64_t ldb, int64_t stride_b0, int64_t stride_b1);
+
+/* eg_attention_grad for the biased forward: the first 44 arguments are eg_attention_grad's, O and Sums come from
+ * eg_attention_bias (accumulate == 0) on the same operands and the same Bias, and the formulas are eg_attention_grad's with
+ *   p_ij = expf(scale * s_ij + bias_ij) / L_i,   bias_ij = Bias[o * stride_b0 + i1 * stride_b1 + i * ldb + j]
+ * — the same two roundings as the forward, so that L_i is the sum of these very terms.  No gradient of the bias is produced
+ * (it would be a tensor of size I x J).
+ *   - The three broadcast forms are eg_attention_bias': stride_b0 == 0, stride_b1 == 0 and ldb == 0, in any combination.
+ *   - EG_ERR_INVALID, with a message that names eg_attention_bias_grad: a negative stride_b0 or stride_b1; 0 < ldb < J.
+ *   - Bias == NULL means no bias: the three outputs have the bits eg_attention_grad gives on the first 44 arguments.
+ *   - Every other refusal, every empty extent and the accumulate bits are eg_attention_grad's, with a message that names
+ *     eg_attention_bias_grad.
+ *   - No alignment is required.  The dQ kernel reads the bias as the forward does.  The dK/dV kernel holds the transposed
+ *     tile, where a lane's four elements are four consecutive keys of one query row: one 16-byte load when Bias is 16-byte
+ *     aligned and ldb and both strides are multiples of 4 (0 is one), four element loads otherwise; same bits either way.
+ *   - Elements of Bias outside the views are never read, whatever they hold.
+ * A masked key (-Inf) has p_ij = 0 and gets no dK and no dV from that row.  Rows whose L_i is 0 or not finite are
+ * unspecified, as in eg_attention_grad.  Two calls give the same bits. */
+int eg_attention_bias_grad(eg_ctx* ctx, int64_t batch0, int64_t batch1, int64_t I, int64_t J, int64_t K, int64_t D, float scale,
+                           const float* Q, int64_t ldq, int64_t stride_q0, int64_t stride_q1,
+                           const float* Kk, int64_t ldk, int64_t stride_k0, int64_t stride_k1,
+                           const float* V, int64_t ldv, int64_t stride_v0, int64_t stride_v1,
+                           const float* O, int64_t ldo, int64_t stride_o0, int64_t stride_o1,
+                           const float* Sums, int64_t stride_s0, int64_t stride_s1,
+                           const float* dO, int64_t lddo, int64_t stride_do0, int64_t stride_do1,
+                           float* dQ, int64_t lddq, int64_t stride_dq0, int64_t stride_dq1,
+                           float* dK, int64_t lddk, int64_t stride_dk0, int64_t stride_dk1,
+                           float* dV, int64_t lddv, int64_t stride_dv0, int64_t stride_dv1, int accumulate,
+                           const float* Bias, int64_t ldb, int64_t stride_b0, int64_t stride_b1);
+
 /* out[y,x] (+)= bias[x]   — dense's second kernel, dnn.nim:22-24. out is [rows, cols]. */
 int eg_bias_add(eg_ctx* ctx, int64_t rows, int64_t cols, const float* bias, float* out,
                 int accumulate);
