@@ -85,6 +85,8 @@ _SIGS = {
                           [c_int, c_void_p, c_i64, c_i64] + [c_void_p, c_i64, c_i64, c_i64]),
     "eg_attention_bias_grad": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_f32] + [c_void_p, c_i64, c_i64, c_i64] * 4 +
                                [c_void_p, c_i64, c_i64] + [c_void_p, c_i64, c_i64, c_i64] * 4 + [c_int] + [c_void_p, c_i64, c_i64, c_i64]),
+    "eg_attention_bias_dbias": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_f32] + [c_void_p, c_i64, c_i64, c_i64] * 4 +
+                                [c_void_p, c_i64, c_i64] + [c_void_p, c_i64, c_i64, c_i64] * 3 + [c_int]),
     "eg_attention_f64": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_f64] + [c_void_p, c_i64, c_i64, c_i64] * 4 + [c_int]),
     "eg_attention_sums_f64": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_f64] + [c_void_p, c_i64, c_i64, c_i64] * 4 +
                               [c_int, c_void_p, c_i64, c_i64]),

@@ -28,6 +28,13 @@ int attention_grad(eg_ctx* ctx, const Extents& e, float scale, const float* Q, V
                    const float* O, View o, const float* Sums, View s, const float* dO, View dout, float* dQ, View dq, float* dK, View dk, float* dV,
                    View dv, int accumulate, const float* Bias = nullptr, View bv = {}, const char* entry = nullptr);
 
+// The gradient of that bias (attention_dbias_f32.hip): eg_attention_bias_dbias, over what attention_forward left with Sums and
+// the same Bias.  dBias (+)= the sum of p * (dP - delta) over every index whose step in `db` is 0; db.ld and both its strides
+// are 0 exactly where bv's are.
+int attention_dbias(eg_ctx* ctx, const Extents& e, float scale, const float* Q, View q, const float* Kk, View k, const float* V, View v,
+                    const float* O, View o, const float* Sums, View s, const float* dO, View dout, const float* Bias, View bv, float* dBias,
+                    View db, int accumulate);
+
 // The float64 backward (attention_grad_f64.hip): eg_attention_grad_f64, over what attention_forward_f64 left with Sums.
 int attention_grad_f64(eg_ctx* ctx, const Extents& e, double scale, const double* Q, View q, const double* Kk, View k, const double* V, View v,
                        const double* O, View o, const double* Sums, View s, const double* dO, View dout, double* dQ, View dq, double* dK, View dk,

@@ -109,5 +109,51 @@ GradPlan plan_backward(const GradProblem& p, bool f64) {
 GradPlan plan_attention_grad(const GradProblem& p) { return plan_backward(p, false); }
 GradPlan plan_attention_grad_f64(const GradProblem& p) { return plan_backward(p, true); }
 
+// The dBias kernel's plan.  Where dBias has a step of 0 the index is summed inside a block; the other batch indices span the
+// cells.  Empty I, J, K and D and an empty summed batch are plans (the block has no passes, or the kernel no tiles); an empty
+// batch extent that dBias steps over is not.
+DbiasPlan plan_attention_dbias(const DbiasProblem& p) {
+  DbiasPlan r;
+  if (p.batch0 < 0 || p.batch1 < 0 || p.I < 0 || p.J < 0 || p.K < 0 || p.D < 0) {
+    r.reason = "a negative extent";
+    return r;
+  }
+  if (p.K > MAX_HEAD) {
+    r.reason = "K above 128";
+    return r;
+  }
+  if (p.D > MAX_HEAD) {
+    r.reason = "D above 128";
+    return r;
+  }
+  r.row_fold = p.dbias.ld == 0;
+  r.cells0 = p.dbias.stride0 ? p.batch0 : 1, r.cells1 = p.dbias.stride1 ? p.batch1 : 1;
+  r.sum0 = p.dbias.stride0 ? 1 : p.batch0, r.sum1 = p.dbias.stride1 ? 1 : p.batch1;
+  if (r.cells0 < 1 || r.cells1 < 1) {
+    r.reason = "an empty batch that dBias steps over";
+    return r;
+  }
+  r.kp = padded_head(p.K);
+  r.dp = padded_head(p.D);
+  r.ahead = dbias_ahead(r.kp, r.dp);
+  r.lds_bytes = dbias_lds_bytes(r.kp, r.dp);
+  if (r.lds_bytes > LDS_LIMIT) {
+    r.reason = "the tiles exceed the LDS of a CU";
+    return r;
+  }
+  r.tiles_i = (p.I + 63) / 64, r.tiles_j = (p.J + 63) / 64;
+  if (r.tiles_i > eg::gemm::BATCHED_MAX_BLOCKS || r.tiles_j > eg::gemm::BATCHED_MAX_BLOCKS ||
+      (!r.row_fold && r.tiles_i * r.tiles_j > eg::gemm::BATCHED_MAX_BLOCKS)) {
+    r.reason = "a cell has more tiles than one launch has blocks";
+    return r;
+  }
+  r.vec_q = operand_vec16(p.q), r.vec_k = operand_vec16(p.k), r.vec_v = operand_vec16(p.v), r.vec_o = operand_vec16(p.o);
+  r.vec_s = operand_vec16(p.s), r.vec_do = operand_vec16(p.dout), r.vec_db = operand_vec16(p.dbias);
+  r.cells = r.cells0 * r.cells1;
+  r.cut = cut_items(r.cells, r.row_fold ? r.tiles_j : r.tiles_i * r.tiles_j);
+  r.supported = true;
+  return r;
+}
+
 }  // namespace attention
 }  // namespace eg

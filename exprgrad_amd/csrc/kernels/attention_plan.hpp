@@ -195,5 +195,52 @@ constexpr bool grad_dkv_ahead_f64(int kp, int dp) { return grad_dkv_regs_f64(kp,
 
 GradPlan plan_attention_grad_f64(const GradProblem& p);
 
+// ---- The gradient of the score bias (attention_dbias_f32.hip): dBias (+)= sum of p * (dP - delta) over every index whose
+// step in dBias is 0.  One block owns one 64 x 64 tile of one output cell, a cell being a pair (o', i1') of the batch indices
+// that are not summed, and adds up in a fixed order every item that maps to the cell (and, with lddb == 0, every row tile):
+// the cells are the items of the item grid.
+struct DbiasProblem : Extents {
+  Operand q, k, v, o, s, dout, bias, dbias;
+  int cus = 256;
+};
+
+struct DbiasPlan {
+  bool supported = false;
+  const char* reason = "";
+  int kp = 0, dp = 0;
+  // 16-byte accesses: loads of Q, Kk, V, O, Sums and dO, stores (and, accumulating, loads) of dBias; the bias is read element
+  // by element, straight into accumulator layout (load_bias)
+  bool vec_q = false, vec_k = false, vec_v = false, vec_o = false, vec_s = false, vec_do = false, vec_db = false;
+  bool row_fold = false;        // lddb == 0: the query rows are summed too, a cell is one row of J floats
+  long cells0 = 0, cells1 = 0;  // the cells along batch0 and batch1: the extent where dBias steps, 1 where it sums
+  long cells = 0;               // cells0 * cells1: the items of the cut
+  long sum0 = 0, sum1 = 0;      // items a block adds along batch0 and batch1: 1 where dBias steps, the extent where it sums
+  long tiles_i = 0, tiles_j = 0;
+  Cut cut;                      // tiles per cell: tiles_i * tiles_j, or tiles_j with the row fold
+  bool ahead = false;           // the next pass's tiles are loaded during this pass's MFMAs
+  int block = THREADS;
+  long lds_bytes = 0;
+};
+
+// Q tile and K tile [64][kp + 4], dO tile and V tile [64][dp + 4] (all four read NT only), 1 / L and delta of the 64 rows.  The
+// epilogue's [64][68] staging tile and the fold's [4][64] live in the first two tiles, which are at least 2 * 64 * 36 floats.
+constexpr long dbias_lds_bytes(int kp, int dp) { return 4L * (2 * 64 * (kp + GRAD_PAD_NT) + 2 * 64 * (dp + GRAD_PAD_NT) + 2 * 64); }
+
+// 32-bit registers a lane holds across a pass's MFMAs: the A operands of its Q and dO rows ((kp + dp) / 4), the running sums, S,
+// dP and the bias tile (16 each), and with `ahead` the four tiles, the O parts and the row sums of the next pass.  The
+// compiler's resource report draws the lines (profiles/attention_dbias.txt has the table, with and without the look-ahead):
+//   - with everything ahead the largest pair holds 292 of these and none of the 18 kernels has scratch, so the budget admits
+//     every pair; when the toolchain changes, regenerate the table and lower the budget if a kernel spills;
+//   - the five pairs whose LDS leaves room for one block per CU have one wave per SIMD either way: the look-ahead is free and
+//     is the only thing that covers their loads.  At the other four it costs occupancy (64 x 64: 262 registers, one wave per
+//     SIMD, against 222 and two), and the second block's waves cover the loads instead: these load at the top of each pass.
+constexpr int DBIAS_REG_BUDGET = 320;
+constexpr int dbias_regs(int kp, int dp, bool ahead) { return (kp + dp) / 4 + 64 + (ahead ? (kp + dp) / 2 + dp / 4 + 4 : 0); }
+// The kernel is instantiated on this function's value, so a plan and its kernel cannot disagree.
+constexpr bool dbias_ahead(int kp, int dp) { return 2 * dbias_lds_bytes(kp, dp) > LDS_LIMIT && dbias_regs(kp, dp, true) <= DBIAS_REG_BUDGET; }
+
+DbiasPlan plan_attention_dbias(const DbiasProblem& p);
+inline Launch plan_dbias_launch(const DbiasPlan& plan, long index) { return plan_launch(plan.cells, plan.cut, index); }
+
 }  // namespace attention
 }  // namespace eg

@@ -114,6 +114,18 @@ def attention_bias_grad(ctx, batch0, batch1, I, J, K, D, scale, Q, ldq, strides_
          strides_dk[1], _p(dV), lddv, strides_dv[0], strides_dv[1], int(accumulate), _p(Bias), ldb, strides_b[0], strides_b[1])
 
 
+def attention_bias_dbias(ctx, batch0, batch1, I, J, K, D, scale, Q, ldq, strides_q, Kk, ldk, strides_k, V, ldv, strides_v, O, ldo, strides_o, Sums,
+                         strides_s, dO, lddo, strides_do, Bias, ldb, strides_b, dBias, lddb, strides_db, accumulate=False):
+    """The gradient of `attention_bias`'s Bias, one launch that stores nothing of size I x J but dBias itself: with O and Sums
+    from attention_bias (accumulate = False) on the same operands and the same Bias, dBias (+)= the sum of p_ij * (dO_i . v_j -
+    dO_i . o_i) over every index whose step in dBias is 0.  lddb and strides_db are 0 exactly where ldb and strides_b are: the
+    gradient has the bias's broadcast form.  K and D at most 128."""
+    call("eg_attention_bias_dbias", ctx.handle, batch0, batch1, I, J, K, D, float(scale), _p(Q), ldq, strides_q[0], strides_q[1], _p(Kk), ldk,
+         strides_k[0], strides_k[1], _p(V), ldv, strides_v[0], strides_v[1], _p(O), ldo, strides_o[0], strides_o[1], _p(Sums), strides_s[0],
+         strides_s[1], _p(dO), lddo, strides_do[0], strides_do[1], _p(Bias), ldb, strides_b[0], strides_b[1], _p(dBias), lddb, strides_db[0],
+         strides_db[1], int(accumulate))
+
+
 def attention_grad_f64(ctx, batch0, batch1, I, J, K, D, scale, Q, ldq, strides_q, Kk, ldk, strides_k, V, ldv, strides_v, O, ldo, strides_o, Sums,
                        strides_s, dO, lddo, strides_do, dQ, lddq, strides_dq, dK, lddk, strides_dk, dV, lddv, strides_dv, accumulate=0):
     """The float64 form of `attention_grad`: O and Sums from attention_sums_f64 (accumulate = False), every operand in doubles

@@ -430,7 +430,7 @@ int eg_attention_bias(eg_ctx* ctx, int64_t batch0, int64_t batch1, int64_t I, in
  *     aligned and ldb and both strides are multiples of 4 (0 is one), four element loads otherwise; same bits either way.
  *   - Elements of Bias outside the views are never read, whatever they hold.
  * A masked key (-Inf) has p_ij = 0 and gets no dK and no dV from that row.  Rows whose L_i is 0 or not finite are
- * unspecified, as in eg_attention_grad.  Two calls give the same bits. */
+ * unspecified, as in eg_attention_grad.  Two calls give the same bits.  The gradient of Bias itself: eg_attention_bias_dbias. */
 int eg_attention_bias_grad(eg_ctx* ctx, int64_t batch0, int64_t batch1, int64_t I, int64_t J, int64_t K, int64_t D, float scale,
                            const float* Q, int64_t ldq, int64_t stride_q0, int64_t stride_q1,
                            const float* Kk, int64_t ldk, int64_t stride_k0, int64_t stride_k1,
@@ -442,6 +442,46 @@ int eg_attention_bias_grad(eg_ctx* ctx, int64_t batch0, int64_t batch1, int64_t 
                            float* dK, int64_t lddk, int64_t stride_dk0, int64_t stride_dk1,
                            float* dV, int64_t lddv, int64_t stride_dv0, int64_t stride_dv1, int accumulate,
                            const float* Bias, int64_t ldb, int64_t stride_b0, int64_t stride_b1);
+
+/* The gradient of eg_attention_bias' Bias, for a bias that is a parameter (a relative-position table m[h,i,j], a learned
+ * slope): the first 35 arguments are eg_attention_bias_grad's, O and Sums come from eg_attention_bias (accumulate == 0) on the
+ * same operands and the same Bias, and with p_ij = expf(scale * s_ij + bias_ij) / L_i, dP_ij = dO_i . v_j, delta_i = dO_i . o_i
+ *   g_ij = p_ij * (dP_ij - delta_i)                                  (eg_attention_grad's dS without the factor scale)
+ *   dBias[o * stride_db0 + i1 * stride_db1 + i * lddb + j] (+)= the sum of g_ij of item (o, i1)
+ * over every index whose step in dBias is 0: stride_db0 == 0 sums over batch0, stride_db1 == 0 over batch1, lddb == 0 over the
+ * query rows (one row of J floats).  The gradient has the broadcast form of the bias.
+ * One launch (kernels/attention_dbias_f32.hip).  A cell is a pair of the batch indices that are not summed; one block owns
+ * one tile of 64 query rows x 64 keys of one cell (with lddb == 0: 64 keys) and adds up, in a fixed order (batch0 outermost,
+ * then batch1, then the row tiles), every item that belongs to the cell, recomputing S and dP tile by tile on the f32 matrix
+ * instruction.  Cells x tiles blocks, split along the flattened cell range when they would exceed 2^22.  Nothing of size I x J
+ * but Bias and dBias is read or written, no atomics, no workspace; two calls give the same bits.
+ *   - Each of lddb, stride_db0 and stride_db1 must be 0 exactly where ldb, stride_b0 and stride_b1 are, else EG_ERR_INVALID:
+ *     every item a block adds then has the same bias tile, which it loads once.
+ *   - EG_ERR_INVALID, with a message that names eg_attention_bias_dbias: 0 < ldb < J or 0 < lddb < J; a negative stride;
+ *     Bias == NULL or dBias == NULL when dBias has elements; accumulate other than 0 and 1; and what eg_attention_grad refuses
+ *     of the six inputs (a NULL ctx, a NULL operand of a non-empty sum, a negative extent, a leading dimension shorter than a
+ *     row, a batch extent of 2^31 or more).
+ *   - Over its non-zero steps dBias must not alias itself: batched2_c_distinct on the cells (and I x J, or J with lddb == 0),
+ *     else EG_ERR_INVALID.  Bias may alias itself freely.  Aliasing between different operands is undefined.
+ *   - EG_ERR_UNSUPPORTED, with a message that names the limit: K > 128 or D > 128; a cell of more than 2^22 tiles.
+ *   - A zero batch extent on an index that is not summed launches nothing, as do J == 0 and, with lddb != 0, I == 0: dBias has
+ *     no elements.  I == 0 with lddb == 0, D == 0 or a zero extent on a summed index: an empty sum, the elements of dBias are
+ *     zeros when accumulate == 0 and untouched otherwise.  K == 0 computes with every score 0.
+ *   - No alignment is required.  The six inputs are read as in eg_attention_grad; Bias element by element; dBias with 16-byte
+ *     stores (and loads, accumulating) when it is 16-byte aligned and lddb and both strides are multiples of 4, element by
+ *     element otherwise; the bits are the same either way.
+ *   - Elements outside every view are never read and never written, whatever they hold.
+ * A masked key (-Inf) has p_ij = 0 and gets exactly +0 or -0.  Rows whose L_i is 0 or not finite are unspecified, as in
+ * eg_attention_grad; where an index is summed, such a row spoils the same (i, j) of every item that shares it. */
+int eg_attention_bias_dbias(eg_ctx* ctx, int64_t batch0, int64_t batch1, int64_t I, int64_t J, int64_t K, int64_t D, float scale,
+                            const float* Q, int64_t ldq, int64_t stride_q0, int64_t stride_q1,
+                            const float* Kk, int64_t ldk, int64_t stride_k0, int64_t stride_k1,
+                            const float* V, int64_t ldv, int64_t stride_v0, int64_t stride_v1,
+                            const float* O, int64_t ldo, int64_t stride_o0, int64_t stride_o1,
+                            const float* Sums, int64_t stride_s0, int64_t stride_s1,
+                            const float* dO, int64_t lddo, int64_t stride_do0, int64_t stride_do1,
+                            const float* Bias, int64_t ldb, int64_t stride_b0, int64_t stride_b1,
+                            float* dBias, int64_t lddb, int64_t stride_db0, int64_t stride_db1, int accumulate);
 
 /* out[y,x] (+)= bias[x]   — dense's second kernel, dnn.nim:22-24. out is [rows, cols]. */
 int eg_bias_add(eg_ctx* ctx, int64_t rows, int64_t cols, const float* bias, float* out,
