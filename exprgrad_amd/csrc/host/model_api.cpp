@@ -833,6 +833,18 @@ int eg_model_fuse_attention_f64(eg_model* m, int on) try {
 }
 EG_CATCH_ALL
 
+int eg_model_fuse_attention_stable(eg_model* m, int on) try {
+  EG_REQUIRE(m, EG_ERR_INVALID, "eg_model_fuse_attention_stable: NULL model");
+  EG_REQUIRE(!m->f64, EG_ERR_INVALID, "eg_model_fuse_attention_stable: a float64 model (the kernel with a row maximum is float32)");
+  if (m->fuse_attention_stable != (on != 0)) {
+    m->fuse_attention_stable = on != 0;
+    m->inputs_gen++;  // the plan key changes: the next run looks its plan up again
+    describe(m);      // eg_model_plan_text names the launches the setting asks for
+  }
+  return EG_OK;
+}
+EG_CATCH_ALL
+
 // Lowering decides which kernels are library launches, and producer inlining depends on that (a map is never recomputed
 // inside a library launch): the setting lowers every target again from its kernels as compiled.  The plans made so far
 // point into the old lowering and go, with the captured training graph that replays their launches and with the old

@@ -213,6 +213,7 @@ std::string shape_key(eg_model* m) {
   if (m->fuse_attention_fit) os << "a";
   if (m->batched2_f64) os << "d";
   if (m->fuse_attention_f64) os << "f";
+  if (m->fuse_attention_stable) os << "s";
   return os.str();
 }
 

@@ -141,6 +141,11 @@ int issue_attention(eg_model* m, TargetState& ts, Plan& plan, const Launch& L) {
                                                 L.accumulate, dp(A.sums), A.sums.view);
   }
   auto ptr = [&](const Launch::Attn::Operand& x) -> float* { return x.tensor ? tensor_ptr(m, ts, plan, x.tensor) : nullptr; };
+  // eg_model_fuse_attention_stable: a forward group's launch keeps a running row maximum.  A fit group's forward (the one
+  // with a sums tensor) stays as written: its backward launch reads the as-written row sums.
+  if (L.kind == StepKind::Attention && m->fuse_attention_stable && !A.sums.tensor)
+    return eg::attention::attention_stable(m->ctx, A.e, A.scale, ptr(A.q), A.q.view, ptr(A.k), A.k.view, ptr(A.v), A.v.view, ptr(A.o), A.o.view,
+                                           L.accumulate, nullptr, {}, ptr(A.bias), A.bias.view);
   if (L.kind == StepKind::Attention)   // a fit group's forward has the row sums to store for the backward launch
     return eg::attention::attention_forward(m->ctx, A.e, A.scale, ptr(A.q), A.q.view, ptr(A.k), A.k.view, ptr(A.v), A.v.view, ptr(A.o), A.o.view,
                                             L.accumulate, ptr(A.sums), A.sums.view, ptr(A.bias), A.bias.view);

@@ -26,7 +26,14 @@ int attention_forward_f64(eg_ctx* ctx, const Extents& e, double scale, const dou
 // (eg_attention_bias_grad) the probabilities are those of the biased forward; no gradient of the bias is produced.
 int attention_grad(eg_ctx* ctx, const Extents& e, float scale, const float* Q, View q, const float* Kk, View k, const float* V, View v,
                    const float* O, View o, const float* Sums, View s, const float* dO, View dout, float* dQ, View dq, float* dK, View dk, float* dV,
-                   View dv, int accumulate, const float* Bias = nullptr, View bv = {}, const char* entry = nullptr);
+                   View dv, int accumulate, const float* Bias = nullptr, View bv = {}, const char* entry = nullptr, bool stable = false);
+
+// The forward with a running row maximum (attention_stable_f32.hip): eg_attention_stable and a model's forward attention
+// launches under eg_model_fuse_attention_stable.  e_ij = expf(x_ij - m_i); Stats, when not NULL, takes two rows of I floats per
+// item, st.ld apart: the maxima m and the sums L.  Its backward is attention_grad with `stable`, Sums that Stats and s its view
+// (s.ld the step between the two rows): p_ij = expf(x_ij - m_i) / L_i, the STABLE kernels of attention_grad_stable_f32.hip.
+int attention_stable(eg_ctx* ctx, const Extents& e, float scale, const float* Q, View q, const float* Kk, View k, const float* V, View v, float* O,
+                     View o, int accumulate, float* Stats = nullptr, View st = {}, const float* Bias = nullptr, View bv = {});
 
 // The gradient of that bias (attention_dbias_f32.hip): eg_attention_bias_dbias, over what attention_forward left with Sums and
 // the same Bias.  dBias (+)= the sum of p * (dP - delta) over every index whose step in `db` is 0; db.ld and both its strides

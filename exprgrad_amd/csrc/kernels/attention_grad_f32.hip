@@ -25,345 +25,19 @@
 // spread out.  A stride = 4 (mod 32), the forward's, is as good as an aligned stride gets for NT (c and c + 8 share a bank)
 // and poor for NN (rows g and g + 1 overlap in 12 of 16 banks); = 20 (mod 32) keeps NT where it was and leaves NN four
 // shared banks.  Tiles read both ways have rows of width + 20 floats, tiles read NT only of width + 4.
+//
+// The kernels themselves are templates in attention_grad_f32.hpp; this file instantiates them for eg_attention_grad and
+// eg_attention_bias_grad, and attention_grad_stable_f32.hip for eg_attention_stable_grad.
 #include "gemm_plan.hpp"        // batched2_c_distinct
 #include "attention.hpp"        // the internal entry
-#include "attention_tile.hpp"   // kernel operands, tiles, the MFMA loops, the launcher
-#include "attention_grad_tile.hpp"   // O parts, delta, 1 / L, the accumulators' way out
-
-#include <cmath>
-
-namespace {
-
-using eg::gemm::f32x4;
-using namespace eg::attention;
-
-struct GradArgs {
-  In q, k, v, o, s, dout;
-  Out dq, dk, dv;
-  long I, J;
-  int K, D;
-  float scale;
-  int acc_dq, acc_dk, acc_dv;          // that output is added to
-  int put_dk, put_dv;                  // the dK/dV kernel stores that output
-  Items items;
-};
-
-// eg_attention_bias_grad: the forward's score bias.  Arguments of their own for the BIAS kernels, so that the others take the
-// arguments they took.
-struct GradBiasArgs : GradArgs {
-  In b;
-};
-template <bool BIAS>
-using ArgsOf = std::conditional_t<BIAS, GradBiasArgs, GradArgs>;
-
-constexpr int TILE = 64;
-
-// BIAS (both kernels): p_ij = expf(scale * s_ij + bias_ij) / L_i, the bias an operand with a view of its own whose ld and
-// strides may each be 0; a compile-time flag, and the instantiations without it are the kernels they were.  One
-// multiplication, one addition, not fused: what the forward computes, so that L is the sum of these very terms.  The dQ kernel
-// holds the wave's 16 x 64 bias tile in accumulator layout, as the forward does; the dK/dV kernel holds its transpose, where
-// a lane's four elements are four consecutive keys of one query row: one 16-byte load per nb when the plan's vec_b allows it.
-// Both load a tile ahead, with the other operands' next tiles, straight into registers: no LDS.  No gradient of the bias.
-template <int KP, int DP, bool BIAS>
-__global__ __launch_bounds__(THREADS) void attention_dq_kernel(ArgsOf<BIAS> a) {
-  constexpr int KS = KP + GRAD_PAD_BOTH, VS = DP + GRAD_PAD_NT;
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  float* const Ks = lds;                  // [64][KS]: the Q tile first, dQ last
-  float* const Vs = Ks + TILE * KS;       // [64][VS]: the dO tile first
-  float* const Es = Vs + TILE * VS;       // [4][16][ES]
-  float* const St = Es + 4 * 16 * ES;     // [64][2]: 1 / L, delta
-
-  const BlockItem b = block_item(a.items);
-  const long i0 = (long)b.tile * TILE;
-  const long rows = a.I - i0;
-  const long read_rows = a.J > 0 ? rows : 0;   // without keys nothing is read: dQ is zeros
-  const long ldk = a.k.v.ld, ldv = a.v.v.ld;
-  const float* const Q = item_base(a.q, b.outer, b.inner) + i0 * a.q.v.ld;
-  const float* const dO = item_base(a.dout, b.outer, b.inner) + i0 * a.dout.v.ld;
-  const float* const O = item_base(a.o, b.outer, b.inner) + i0 * a.o.v.ld;
-  const float* const S = item_base(a.s, b.outer, b.inner) + i0;
-  const float* const Kk = item_base(a.k, b.outer, b.inner);
-  const float* const V = item_base(a.v, b.outer, b.inner);
-  float* const dQ = item_base(a.dq, b.outer, b.inner) + i0 * a.dq.v.ld;
-
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, c = lane & 15, g = lane >> 4;
-  float* const Ew = Es + w * 16 * ES;
-
-  TileRegs<KP> tk;
-  TileRegs<DP> tv;
-  // the wave's Q rows and dO rows as A operands for the whole loop; 1 / L and delta of its accumulator rows
-  float q[KP / 4], dout[DP / 4], inv[4], delta[4];
-  {
-    OPart<DP> po;
-    load_rows<KP>(tk, Q, a.q.v.ld, read_rows, a.K, a.q.vec != 0, tid);
-    load_rows<DP>(tv, dO, a.dout.v.ld, read_rows, a.D, a.dout.vec != 0, tid);
-    load_o_part<DP>(po, O, a.o.v.ld, read_rows, a.D, a.o.vec != 0, tid);
-    const f32x4 sums = load_sums(S, read_rows, a.s.vec != 0, tid);
-    store_rows<KP, KS>(tk, Ks, tid);
-    store_rows<DP, VS>(tv, Vs, tid);
-    store_inverse_sums(sums, St, rows, tid);
-    __syncthreads();
-    read_a_rows<KP, KS>(Ks, w, c, g, q);
-    read_a_rows<DP, VS>(Vs, w, c, g, dout);
-    const float d = row_delta<DP>(Vs, VS, po, tid);
-    if ((tid & 3) == 0) St[2 * (tid >> 2) + 1] = d;
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      inv[r] = St[2 * (w * 16 + 4 * g + r)];
-      delta[r] = St[2 * (w * 16 + 4 * g + r) + 1];
-    }
-  }
-
-  f32x4 dq[KP / 16];
-#pragma unroll
-  for (int nb = 0; nb < KP / 16; ++nb) dq[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  // the lane's bias: rows 4 g + r of the wave's, keys c + 16 nb of a tile; `next` is a tile ahead
-  [[maybe_unused]] BiasTile bias, bias_next;
-  [[maybe_unused]] const long bias_rows = rows - w * 16 - 4 * g;
-  [[maybe_unused]] long ldb = 0;
-  [[maybe_unused]] const float* Bl = nullptr;
-  if constexpr (BIAS) {
-    ldb = a.b.v.ld;
-    Bl = item_base(a.b, b.outer, b.inner) + (i0 + w * 16 + 4 * g) * ldb + c;
-  }
-  const long nt = (a.J + TILE - 1) / TILE;
-  if (nt > 0) {
-    load_rows<KP>(tk, Kk, ldk, a.J, a.K, a.k.vec != 0, tid);
-    load_rows<DP>(tv, V, ldv, a.J, a.D, a.v.vec != 0, tid);
-    if constexpr (BIAS) load_bias(bias_next, Bl, ldb, bias_rows, a.J - c);
-  }
-  for (long t = 0; t < nt; ++t) {
-    const long j0 = t * TILE;
-    __syncthreads();   // every wave is done with the tiles in LDS (the first time: with the Q and dO tiles)
-    store_rows<KP, KS>(tk, Ks, tid);
-    store_rows<DP, VS>(tv, Vs, tid);
-    __syncthreads();
-    if constexpr (BIAS) bias = bias_next;
-    if (t + 1 < nt) {   // in flight during this tile's MFMAs
-      load_rows<KP>(tk, Kk + (j0 + TILE) * ldk, ldk, a.J - j0 - TILE, a.K, a.k.vec != 0, tid);
-      load_rows<DP>(tv, V + (j0 + TILE) * ldv, ldv, a.J - j0 - TILE, a.D, a.v.vec != 0, tid);
-      if constexpr (BIAS) load_bias(bias_next, Bl + j0 + TILE, ldb, bias_rows, a.J - j0 - TILE - c);
-    }
-
-    f32x4 s[4], dp[4];
-#pragma unroll
-    for (int nb = 0; nb < 4; ++nb) s[nb] = dp[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int kk = 0; kk < KP / 4; ++kk) {
-#pragma unroll
-      for (int nb = 0; nb < 4; ++nb) s[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(q[kk], Ks[(nb * 16 + c) * KS + 4 * kk + g], s[nb], 0, 0, 0);
-    }
-#pragma unroll
-    for (int dd = 0; dd < DP / 4; ++dd) {
-#pragma unroll
-      for (int nb = 0; nb < 4; ++nb) dp[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(dout[dd], Vs[(nb * 16 + c) * VS + 4 * dd + g], dp[nb], 0, 0, 0);
-    }
-
-#pragma unroll
-    for (int nb = 0; nb < 4; ++nb) {
-      const bool live = j0 + nb * 16 + c < a.J;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float x = s[nb][r] * a.scale;
-        if constexpr (BIAS) x = x + bias.x[nb][r];
-        const float p = expf(x) * inv[r];
-        const float ds = (a.scale * p) * (dp[nb][r] - delta[r]);
-        Ew[(4 * g + r) * ES + nb * 16 + c] = live ? ds : 0.f;   // a select: a key outside the problem adds exactly 0
-      }
-    }
-    wave_sync();
-
-#pragma unroll
-    for (int jj = 0; jj < TILE / 4; ++jj) {
-      const float e = Ew[c * ES + 4 * jj + g];
-#pragma unroll
-      for (int nb = 0; nb < KP / 16; ++nb) dq[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(e, Ks[(4 * jj + g) * KS + nb * 16 + c], dq[nb], 0, 0, 0);
-    }
-    wave_sync();   // the wave's rows are read before its next tile overwrites them
-  }
-
-  __syncthreads();   // every wave is done with the K tile
-  stage_acc<KP, KS>(dq, Ks, w, c, g);
-  __syncthreads();
-  store_out<KP, KS>(Ks, dQ, a.dq.v.ld, rows, a.K, a.dq.vec != 0, a.acc_dq != 0, tid);
-}
-
-template <int KP, int DP, bool BIAS>
-__global__ __launch_bounds__(THREADS) void attention_dkv_kernel(ArgsOf<BIAS> a) {
-  constexpr int QS = KP + GRAD_PAD_BOTH, DS = DP + GRAD_PAD_BOTH;
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  float* const Qs = lds;                  // [64][QS]: the K tile first, dK last
-  float* const Ds = Qs + TILE * QS;       // [64][DS]: the V tile first, dV last
-  float* const Es = Ds + TILE * DS;       // [4][16][ES]
-  float* const St = Es + 4 * 16 * ES;     // [64][2]: 1 / L, delta of the query tile's rows
-
-  const BlockItem b = block_item(a.items);
-  const long j0 = (long)b.tile * TILE;
-  const long keys = a.J - j0;
-  const long read_keys = a.I > 0 ? keys : 0;   // without query rows nothing is read: dK and dV are zeros
-  const long ldq = a.q.v.ld, lddo = a.dout.v.ld, ldo = a.o.v.ld;
-  const float* const Q = item_base(a.q, b.outer, b.inner);
-  const float* const dO = item_base(a.dout, b.outer, b.inner);
-  const float* const O = item_base(a.o, b.outer, b.inner);
-  const float* const S = item_base(a.s, b.outer, b.inner);
-  const float* const Kk = item_base(a.k, b.outer, b.inner) + j0 * a.k.v.ld;
-  const float* const V = item_base(a.v, b.outer, b.inner) + j0 * a.v.v.ld;
-  float* const dK = item_base(a.dk, b.outer, b.inner) + j0 * a.dk.v.ld;
-  float* const dV = item_base(a.dv, b.outer, b.inner) + j0 * a.dv.v.ld;
-
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, c = lane & 15, g = lane >> 4;
-  float* const Ew = Es + w * 16 * ES;
-
-  TileRegs<KP> tq;
-  TileRegs<DP> td;
-  OPart<DP> po;
-  f32x4 sums = {1.f, 1.f, 1.f, 1.f};
-  // the wave's K rows and V rows as A operands for the whole loop
-  float kreg[KP / 4], vreg[DP / 4];
-  load_rows<KP>(tq, Kk, a.k.v.ld, read_keys, a.K, a.k.vec != 0, tid);
-  load_rows<DP>(td, V, a.v.v.ld, read_keys, a.D, a.v.vec != 0, tid);
-  store_rows<KP, QS>(tq, Qs, tid);
-  store_rows<DP, DS>(td, Ds, tid);
-  __syncthreads();
-  read_a_rows<KP, QS>(Qs, w, c, g, kreg);
-  read_a_rows<DP, DS>(Ds, w, c, g, vreg);
-
-  f32x4 dk[KP / 16], dv[DP / 16];
-#pragma unroll
-  for (int nb = 0; nb < KP / 16; ++nb) dk[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int nb = 0; nb < DP / 16; ++nb) dv[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
-  bool klive[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) klive[r] = w * 16 + 4 * g + r < keys;
-
-  // the lane's bias, transposed: keys 4 g + r of the wave's, query rows c + 16 nb of a tile; `next` is a tile ahead
-  [[maybe_unused]] BiasTile bias, bias_next;
-  [[maybe_unused]] const long bias_keys = keys - w * 16 - 4 * g;
-  [[maybe_unused]] long ldb = 0;
-  [[maybe_unused]] const float* Bl = nullptr;
-  [[maybe_unused]] bool vec_b = false;
-  if constexpr (BIAS) {
-    ldb = a.b.v.ld, vec_b = a.b.vec != 0;
-    Bl = item_base(a.b, b.outer, b.inner) + c * ldb + j0 + w * 16 + 4 * g;
-  }
-  const long nt = (a.I + TILE - 1) / TILE;
-  if (nt > 0) {
-    load_rows<KP>(tq, Q, ldq, a.I, a.K, a.q.vec != 0, tid);
-    load_rows<DP>(td, dO, lddo, a.I, a.D, a.dout.vec != 0, tid);
-    load_o_part<DP>(po, O, ldo, a.I, a.D, a.o.vec != 0, tid);
-    sums = load_sums(S, a.I, a.s.vec != 0, tid);
-    if constexpr (BIAS) load_bias_t(bias_next, Bl, ldb, a.I - c, bias_keys, vec_b);
-  }
-  for (long t = 0; t < nt; ++t) {
-    const long i0 = t * TILE;
-    __syncthreads();   // every wave is done with the tiles in LDS (the first time: with the K and V tiles)
-    store_rows<KP, QS>(tq, Qs, tid);
-    store_rows<DP, DS>(td, Ds, tid);
-    store_inverse_sums(sums, St, a.I - i0, tid);
-    __syncthreads();
-    {
-      const float d = row_delta<DP>(Ds, DS, po, tid);
-      if ((tid & 3) == 0) St[2 * (tid >> 2) + 1] = d;
-    }
-    if constexpr (BIAS) bias = bias_next;
-    if (t + 1 < nt) {   // in flight during this tile's MFMAs
-      const long n0 = i0 + TILE;
-      load_rows<KP>(tq, Q + n0 * ldq, ldq, a.I - n0, a.K, a.q.vec != 0, tid);
-      load_rows<DP>(td, dO + n0 * lddo, lddo, a.I - n0, a.D, a.dout.vec != 0, tid);
-      load_o_part<DP>(po, O + n0 * ldo, ldo, a.I - n0, a.D, a.o.vec != 0, tid);
-      sums = load_sums(S + n0, a.I - n0, a.s.vec != 0, tid);
-      if constexpr (BIAS) load_bias_t(bias_next, Bl + n0 * ldb, ldb, a.I - n0 - c, bias_keys, vec_b);
-    }
-    __syncthreads();   // delta of every row is in St
-
-    // S^T and dP^T: rows are the wave's keys, columns the tile's query rows
-    f32x4 s[4], dp[4];
-#pragma unroll
-    for (int nb = 0; nb < 4; ++nb) s[nb] = dp[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int kk = 0; kk < KP / 4; ++kk) {
-#pragma unroll
-      for (int nb = 0; nb < 4; ++nb) s[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(kreg[kk], Qs[(nb * 16 + c) * QS + 4 * kk + g], s[nb], 0, 0, 0);
-    }
-#pragma unroll
-    for (int dd = 0; dd < DP / 4; ++dd) {
-#pragma unroll
-      for (int nb = 0; nb < 4; ++nb) dp[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(vreg[dd], Ds[(nb * 16 + c) * DS + 4 * dd + g], dp[nb], 0, 0, 0);
-    }
-
-    // p^T to the wave's rows, dS^T kept in s for the second pass; a row outside the problem or a key outside it is exactly
-    // 0 by a select
-#pragma unroll
-    for (int nb = 0; nb < 4; ++nb) {
-      const int col = nb * 16 + c;
-      const bool qlive = i0 + col < a.I;
-      const float inv = St[2 * col], delta = St[2 * col + 1];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const bool live = qlive && klive[r];
-        float x = s[nb][r] * a.scale;
-        if constexpr (BIAS) x = x + bias.x[nb][r];
-        const float p = expf(x) * inv;
-        const float ds = (a.scale * p) * (dp[nb][r] - delta);
-        Ew[(4 * g + r) * ES + col] = live ? p : 0.f;
-        s[nb][r] = live ? ds : 0.f;
-      }
-    }
-    wave_sync();
-#pragma unroll
-    for (int ii = 0; ii < TILE / 4; ++ii) {
-      const float e = Ew[c * ES + 4 * ii + g];
-#pragma unroll
-      for (int nb = 0; nb < DP / 16; ++nb) dv[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(e, Ds[(4 * ii + g) * DS + nb * 16 + c], dv[nb], 0, 0, 0);
-    }
-    wave_sync();   // p^T is read before dS^T takes its place
-#pragma unroll
-    for (int nb = 0; nb < 4; ++nb) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) Ew[(4 * g + r) * ES + nb * 16 + c] = s[nb][r];
-    }
-    wave_sync();
-#pragma unroll
-    for (int ii = 0; ii < TILE / 4; ++ii) {
-      const float e = Ew[c * ES + 4 * ii + g];
-#pragma unroll
-      for (int nb = 0; nb < KP / 16; ++nb) dk[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(e, Qs[(4 * ii + g) * QS + nb * 16 + c], dk[nb], 0, 0, 0);
-    }
-    wave_sync();
-  }
-
-  __syncthreads();   // every wave is done with the Q and dO tiles
-  stage_acc<KP, QS>(dk, Qs, w, c, g);
-  stage_acc<DP, DS>(dv, Ds, w, c, g);
-  __syncthreads();
-  if (a.put_dk) store_out<KP, QS>(Qs, dK, a.dk.v.ld, keys, a.K, a.dk.vec != 0, a.acc_dk != 0, tid);
-  if (a.put_dv) store_out<DP, DS>(Ds, dV, a.dv.v.ld, keys, a.D, a.dv.vec != 0, a.acc_dv != 0, tid);
-}
-
-// One launch of one of the two kernels; the attributes of both are set together, once per device and instantiation.
-template <auto DQ_KERNEL, auto DKV_KERNEL, class Args, int KP, int DP>
-int launch(eg_ctx* ctx, bool dkv, unsigned grid, const GradPlan& p, const Args& args) {
-  const int rc = dynamic_lds_once<DQ_KERNEL, DKV_KERNEL>(ctx, {grad_dq_lds_bytes(KP, DP), grad_dkv_lds_bytes(KP, DP)});
-  if (rc) return rc;
-  if (dkv)
-    hipLaunchKernelGGL(DKV_KERNEL, dim3(grid), dim3(p.block), (size_t)p.dkv.lds_bytes, ctx->stream, args);
-  else
-    hipLaunchKernelGGL(DQ_KERNEL, dim3(grid), dim3(p.block), (size_t)p.dq.lds_bytes, ctx->stream, args);
-  EG_HIP_CHECK(hipGetLastError());
-  return EG_OK;
-}
-
-}  // namespace
+#include "attention_grad_f32.hpp"   // the two kernels and their launch
 
 namespace eg {
 namespace attention {
 
 int attention_grad(eg_ctx* ctx, const Extents& e, float scale, const float* Q, View q, const float* Kk, View k, const float* V, View v,
                    const float* O, View o, const float* Sums, View s, const float* dO, View dout, float* dQ, View dq, float* dK, View dk, float* dV,
-                   View dv, int accumulate, const float* Bias, View bv, const char* entry) {
+                   View dv, int accumulate, const float* Bias, View bv, const char* entry, bool stable) {
   const char* const name = entry ? entry : "eg_attention_grad";   // the entry the messages speak of
   const long batch0 = e.batch0, batch1 = e.batch1, I = e.I, J = e.J, K = e.K, D = e.D;
   EG_REQUIRE(ctx, EG_ERR_INVALID, "%s: ctx is NULL", name);
@@ -374,13 +48,17 @@ int attention_grad(eg_ctx* ctx, const Extents& e, float scale, const float* Q, V
              EG_ERR_INVALID, "%s: negative stride", name);
   EG_REQUIRE(!Bias || (bv.stride0 >= 0 && bv.stride1 >= 0), EG_ERR_INVALID, "%s: negative stride of Bias", name);
   EG_REQUIRE(!Bias || bv.ld == 0 || bv.ld >= J, EG_ERR_INVALID, "%s: ldb is neither 0 nor at least J", name);
+  // eg_attention_stable_grad: s is the view of the forward's Stats, two rows of I floats, s.ld apart
+  EG_REQUIRE(!stable || s.ld >= I, EG_ERR_INVALID, "%s: lds is smaller than I", name);
+  EG_REQUIRE(!stable || eg::gemm::batched2_c_distinct(batch0, s.stride0, batch1, s.stride1, 2, s.ld, I), EG_ERR_INVALID,
+             "%s: lds, stride_s0 and stride_s1 make elements of Stats share an address", name);
   EG_REQUIRE((accumulate & ~7) == 0, EG_ERR_INVALID, "%s: accumulate has bits other than 1 (dQ), 2 (dK) and 4 (dV)", name);
   if (batch0 == 0 || batch1 == 0) return EG_OK;
   const bool want_dq = I > 0 && K > 0, want_dk = J > 0 && K > 0, want_dv = J > 0 && D > 0;   // the outputs that have elements
   if (!want_dq && !want_dk && !want_dv) return EG_OK;
   EG_REQUIRE((!want_dq || dQ) && (!want_dk || dK) && (!want_dv || dV), EG_ERR_INVALID, "%s: NULL output", name);
   if (I > 0 && J > 0) {
-    EG_REQUIRE(Sums, EG_ERR_INVALID, "%s: NULL operand (Sums)", name);
+    EG_REQUIRE(Sums, EG_ERR_INVALID, "%s: NULL operand (%s)", name, stable ? "Stats" : "Sums");
     EG_REQUIRE(K == 0 || (Q && Kk), EG_ERR_INVALID, "%s: NULL operand (Q or Kk)", name);
     EG_REQUIRE(D == 0 || (V && O && dO), EG_ERR_INVALID, "%s: NULL operand (V, O or dO)", name);
   }
@@ -410,6 +88,7 @@ int attention_grad(eg_ctx* ctx, const Extents& e, float scale, const float* Q, V
   pr.dout = {dout, aligned16(dO)}, pr.dq = {dq, aligned16(dQ)}, pr.dk = {dk, aligned16(dK)}, pr.dv = {dv, aligned16(dV)};
   pr.has_bias = Bias != nullptr;
   pr.bias = {bv, aligned16(Bias)};
+  pr.stable = stable;
   pr.cus = ctx->compute_units;
   const GradPlan p = plan_attention_grad(pr);
   EG_REQUIRE(p.supported, EG_ERR_UNSUPPORTED, "%s: %s", name, p.reason);
@@ -428,6 +107,7 @@ int attention_grad(eg_ctx* ctx, const Extents& e, float scale, const float* Q, V
       args.items = items;
       return dispatch_heads(p.kp, p.dp, [&](auto KP, auto DP) {
         constexpr int kp = KP(), dp = DP();
+        if (stable) return launch_grad_stable(ctx, dkv, grid, p, args);
         return Bias ? launch<&attention_dq_kernel<kp, dp, true>, &attention_dkv_kernel<kp, dp, true>, GradBiasArgs, kp, dp>(ctx, dkv, grid, p, args)
                     : launch<&attention_dq_kernel<kp, dp, false>, &attention_dkv_kernel<kp, dp, false>, GradArgs, kp, dp>(ctx, dkv, grid, p, args);
       });
@@ -472,4 +152,22 @@ extern "C" int eg_attention_bias_grad(eg_ctx* ctx, int64_t batch0, int64_t batch
                                        {ldv, stride_v0, stride_v1}, O, {ldo, stride_o0, stride_o1}, Sums, {0, stride_s0, stride_s1}, dO,
                                        {lddo, stride_do0, stride_do1}, dQ, {lddq, stride_dq0, stride_dq1}, dK, {lddk, stride_dk0, stride_dk1}, dV,
                                        {lddv, stride_dv0, stride_dv1}, accumulate, Bias, {ldb, stride_b0, stride_b1}, "eg_attention_bias_grad");
+}
+
+extern "C" int eg_attention_stable_grad(eg_ctx* ctx, int64_t batch0, int64_t batch1, int64_t I, int64_t J, int64_t K, int64_t D, float scale,
+                                        const float* Q, int64_t ldq, int64_t stride_q0, int64_t stride_q1,
+                                        const float* Kk, int64_t ldk, int64_t stride_k0, int64_t stride_k1,
+                                        const float* V, int64_t ldv, int64_t stride_v0, int64_t stride_v1,
+                                        const float* O, int64_t ldo, int64_t stride_o0, int64_t stride_o1,
+                                        const float* Stats, int64_t lds, int64_t stride_s0, int64_t stride_s1,
+                                        const float* dO, int64_t lddo, int64_t stride_do0, int64_t stride_do1,
+                                        float* dQ, int64_t lddq, int64_t stride_dq0, int64_t stride_dq1,
+                                        float* dK, int64_t lddk, int64_t stride_dk0, int64_t stride_dk1,
+                                        float* dV, int64_t lddv, int64_t stride_dv0, int64_t stride_dv1, int accumulate,
+                                        const float* Bias, int64_t ldb, int64_t stride_b0, int64_t stride_b1) {
+  return eg::attention::attention_grad(ctx, {batch0, batch1, I, J, K, D}, scale, Q, {ldq, stride_q0, stride_q1}, Kk, {ldk, stride_k0, stride_k1}, V,
+                                       {ldv, stride_v0, stride_v1}, O, {ldo, stride_o0, stride_o1}, Stats, {lds, stride_s0, stride_s1}, dO,
+                                       {lddo, stride_do0, stride_do1}, dQ, {lddq, stride_dq0, stride_dq1}, dK, {lddk, stride_dk0, stride_dk1}, dV,
+                                       {lddv, stride_dv0, stride_dv1}, accumulate, Bias, {ldb, stride_b0, stride_b1}, "eg_attention_stable_grad",
+                                       true);
 }

@@ -72,11 +72,22 @@ __device__ __forceinline__ f32x4 load_sums(const float* __restrict__ S, long row
   return v;
 }
 
-// St[2 * row] = 1 / L of the tile's rows, 0 for rows outside the problem
+// St[SW * row] = 1 / L of the tile's rows, 0 for rows outside the problem; SW the floats St holds per row
+template <int SW = 2>
 __device__ __forceinline__ void store_inverse_sums(const f32x4& v, float* __restrict__ St, long rows, int tid) {
   if (tid < 16) {
 #pragma unroll
-    for (int e = 0; e < 4; ++e) St[2 * (4 * tid + e)] = 4 * tid + e < rows ? 1.f / v[e] : 0.f;
+    for (int e = 0; e < 4; ++e) St[SW * (4 * tid + e)] = 4 * tid + e < rows ? 1.f / v[e] : 0.f;
+  }
+}
+
+// St[SW * row + 2] = the row maximum of the tile's rows (eg_attention_stable_grad), loaded as load_sums loads: a row outside
+// the problem holds 1, and its 1 / L of 0 makes its terms 0
+template <int SW>
+__device__ __forceinline__ void store_maxima(const f32x4& v, float* __restrict__ St, int tid) {
+  if (tid < 16) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) St[SW * (4 * tid + e) + 2] = v[e];
   }
 }
 

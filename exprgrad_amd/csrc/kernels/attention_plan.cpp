@@ -80,8 +80,8 @@ GradPlan plan_backward(const GradProblem& p, bool f64) {
     r.dq.lds_bytes = grad_dq_lds_bytes_f64(r.kp, r.dp, r.dq.step);
     r.dkv.lds_bytes = grad_dkv_lds_bytes_f64(r.kp, r.dp, r.dkv.step);
   } else {
-    r.dq.lds_bytes = grad_dq_lds_bytes(r.kp, r.dp);
-    r.dkv.lds_bytes = grad_dkv_lds_bytes(r.kp, r.dp);
+    r.dq.lds_bytes = grad_dq_lds_bytes(r.kp, r.dp, p.stable);
+    r.dkv.lds_bytes = grad_dkv_lds_bytes(r.kp, r.dp, p.stable);
   }
   if (r.dq.step == 0 || r.dkv.step == 0 || r.dq.lds_bytes > LDS_LIMIT || r.dkv.lds_bytes > LDS_LIMIT) {
     r.reason = "the tiles exceed the LDS of a CU";

@@ -107,6 +107,7 @@ struct GradProblem : Extents {
   Operand q, k, v, o, s, dout, dq, dk, dv;   // s: the row sums
   bool has_bias = false;                     // eg_attention_bias_grad: the forward's score bias
   Operand bias;
+  bool stable = false;                       // eg_attention_stable_grad: s is the forward's Stats, two rows of I floats s.ld apart
   int cus = 256;
 };
 
@@ -134,10 +135,15 @@ struct GradPlan {
 constexpr int GRAD_PAD_BOTH = 20, GRAD_PAD_NT = 4;
 
 // dQ kernel: K tile [64][kp + 20] (NT for the scores, NN for dS * K), V tile [64][dp + 4] (NT only), the waves' dS rows
-// [4][16][68], and 1 / L and delta of the block's 64 rows.
-inline long grad_dq_lds_bytes(int kp, int dp) { return 4L * (64 * (kp + GRAD_PAD_BOTH) + 64 * (dp + GRAD_PAD_NT) + 4 * 16 * 68 + 2 * 64); }
-// dK/dV kernel: Q tile [64][kp + 20] and dO tile [64][dp + 20] (both read both ways), the waves' rows, 1 / L and delta.
-inline long grad_dkv_lds_bytes(int kp, int dp) { return 4L * (64 * (kp + GRAD_PAD_BOTH) + 64 * (dp + GRAD_PAD_BOTH) + 4 * 16 * 68 + 2 * 64); }
+// [4][16][68], and 1 / L and delta of the block's 64 rows; `stable`: their maxima too, 256 bytes more.
+inline long grad_dq_lds_bytes(int kp, int dp, bool stable = false) {
+  return 4L * (64 * (kp + GRAD_PAD_BOTH) + 64 * (dp + GRAD_PAD_NT) + 4 * 16 * 68 + (stable ? 3 : 2) * 64);
+}
+// dK/dV kernel: Q tile [64][kp + 20] and dO tile [64][dp + 20] (both read both ways), the waves' rows, 1 / L and delta (and the
+// maxima).
+inline long grad_dkv_lds_bytes(int kp, int dp, bool stable = false) {
+  return 4L * (64 * (kp + GRAD_PAD_BOTH) + 64 * (dp + GRAD_PAD_BOTH) + 4 * 16 * 68 + (stable ? 3 : 2) * 64);
+}
 
 GradPlan plan_attention_grad(const GradProblem& p);
 // Launch `index` of one of a plan's kernels, index in [0, kernel.launches): the cut's again.

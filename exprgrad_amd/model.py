@@ -149,6 +149,13 @@ class Model:
             self.batched2_f64(True)
         call("eg_model_fuse_attention_f64", self.handle, 1 if on else 0)
 
+    def fuse_attention_stable(self, on=True):
+        """A float32 model's forward attention launches (eg_attn, with or without a bias input) keep a running row maximum
+        (eg_attention_stable's kernel): finite where the program's exp without a maximum is NaN — a score above about 88.7,
+        or only scores below about -103 — and equal to it to rounding, not to the bit, elsewhere.  A fit group's forward and
+        backward launches (`fuse_attention_fit`) keep the as-written kernels.  Off by default; part of the plan key."""
+        call("eg_model_fuse_attention_stable", self.handle, 1 if on else 0)
+
     def set_seed(self, seed):
         """Seed of the model's random tensors (`rand`, dropout masks); the reference uses Nim's global
         generator (`randomize(seed)`)."""

@@ -126,6 +126,28 @@ def attention_bias_dbias(ctx, batch0, batch1, I, J, K, D, scale, Q, ldq, strides
          strides_db[1], int(accumulate))
 
 
+def attention_stable(ctx, batch0, batch1, I, J, K, D, scale, Q, ldq, strides_q, Kk, ldk, strides_k, V, ldv, strides_v, O, ldo, strides_o,
+                     Stats=None, lds=0, strides_s=(0, 0), Bias=None, ldb=0, strides_b=(0, 0), accumulate=False):
+    """Attention with a running row maximum: e_ij = exp(x_ij - max_j x_ij), x_ij = scale * q_i . k_j (+ Bias[i * ldb + j]), finite
+    for finite scores of any magnitude where `attention` and `attention_bias` compute exp(x_ij) as written.  Item (o, i1) writes
+    two rows of I floats at Stats + o * strides_s[0] + i1 * strides_s[1]: the maxima, and lds floats on the sums, which
+    attention_stable_grad needs.  Stats = None and Bias = None are allowed; the bias has attention_bias's broadcast forms."""
+    call("eg_attention_stable", ctx.handle, batch0, batch1, I, J, K, D, float(scale), _p(Q), ldq, strides_q[0], strides_q[1], _p(Kk), ldk,
+         strides_k[0], strides_k[1], _p(V), ldv, strides_v[0], strides_v[1], _p(O), ldo, strides_o[0], strides_o[1], int(accumulate), _p(Stats),
+         lds, strides_s[0], strides_s[1], _p(Bias), ldb, strides_b[0], strides_b[1])
+
+
+def attention_stable_grad(ctx, batch0, batch1, I, J, K, D, scale, Q, ldq, strides_q, Kk, ldk, strides_k, V, ldv, strides_v, O, ldo, strides_o,
+                          Stats, lds, strides_s, dO, lddo, strides_do, dQ, lddq, strides_dq, dK, lddk, strides_dk, dV, lddv, strides_dv,
+                          Bias=None, ldb=0, strides_b=(0, 0), accumulate=0):
+    """`attention_bias_grad` for the forward with a row maximum: O and Stats from attention_stable (accumulate = False) on the same
+    operands and the same Bias; p_ij = exp(x_ij - max_i) / L_i.  accumulate bit 0 adds to dQ, bit 1 to dK, bit 2 to dV."""
+    call("eg_attention_stable_grad", ctx.handle, batch0, batch1, I, J, K, D, float(scale), _p(Q), ldq, strides_q[0], strides_q[1], _p(Kk), ldk,
+         strides_k[0], strides_k[1], _p(V), ldv, strides_v[0], strides_v[1], _p(O), ldo, strides_o[0], strides_o[1], _p(Stats), lds,
+         strides_s[0], strides_s[1], _p(dO), lddo, strides_do[0], strides_do[1], _p(dQ), lddq, strides_dq[0], strides_dq[1], _p(dK), lddk,
+         strides_dk[0], strides_dk[1], _p(dV), lddv, strides_dv[0], strides_dv[1], int(accumulate), _p(Bias), ldb, strides_b[0], strides_b[1])
+
+
 def attention_grad_f64(ctx, batch0, batch1, I, J, K, D, scale, Q, ldq, strides_q, Kk, ldk, strides_k, V, ldv, strides_v, O, ldo, strides_o, Sums,
                        strides_s, dO, lddo, strides_do, dQ, lddq, strides_dq, dK, lddk, strides_dk, dV, lddv, strides_dv, accumulate=0):
     """The float64 form of `attention_grad`: O and Sums from attention_sums_f64 (accumulate = False), every operand in doubles

@@ -483,6 +483,60 @@ int eg_attention_bias_dbias(eg_ctx* ctx, int64_t batch0, int64_t batch1, int64_t
                             const float* Bias, int64_t ldb, int64_t stride_b0, int64_t stride_b1,
                             float* dBias, int64_t lddb, int64_t stride_db0, int64_t stride_db1, int accumulate);
 
+/* Attention with a running row maximum — the softmax a library user expects, finite for finite scores of any magnitude:
+ *   x_ij = scale * q_i . k_j (+ bias_ij),   m_i = max_j x_ij,   L_i = sum_j expf(x_ij - m_i),
+ *   O[i,:] (+)= (sum_j expf(x_ij - m_i) * V[j,:]) / L_i
+ * The first 25 arguments are eg_attention's and the last four eg_attention_bias' (Bias == NULL: no bias; the same broadcast
+ * forms; the scale and the bias are two roundings).  The other entries compute expf(x_ij) as the program writes it and are
+ * NaN when a row has a score above about 88.7 or only scores below about -103; this one is not.  A kernel of its own
+ * (kernels/attention_stable_f32.hip) on eg_attention's tiles: when a key tile raises a row's maximum the running sums are
+ * multiplied by expf(m_old - m_new), a step that a wave skips, with the same bits, while none of its 16 rows moves.
+ *   - Stats, when not NULL, takes two rows of I floats per item: Stats[o * stride_s0 + i1 * stride_s1 + i] = m_i and
+ *     Stats[o * stride_s0 + i1 * stride_s1 + lds + i] = L_i, what eg_attention_stable_grad needs.  Always overwritten
+ *     (accumulate concerns O only), also when D == 0.  O has the same bits with and without Stats.
+ *   - EG_ERR_INVALID, with a message that names eg_attention_stable: lds < I; a negative stride_s0 or stride_s1; lds and the
+ *     strides making elements of Stats share an address (batched2_c_distinct(batch0, stride_s0, batch1, stride_s1, 2, lds, I));
+ *     a negative stride_b0 or stride_b1; 0 < ldb < J; and everything eg_attention refuses of its 25 arguments.
+ *   - EG_ERR_UNSUPPORTED, with a message that names eg_attention_stable and the limit: K > 128 or D > 128.
+ *   - Empty extents, accumulate, alignment and what is never read or written are eg_attention_bias'.
+ * Special values: a row with only finite scores has a finite O (when V is finite) and L_i >= 1; a -Inf score adds exactly 0;
+ * a row whose keys are all -Inf has m_i = -Inf, L_i = 0 and O = 0 / 0 = NaN; a NaN score makes O and L_i NaN (m_i is then
+ * unspecified); a +Inf score makes O and L_i NaN and m_i = +Inf; J == 0 gives O = 0 (untouched when accumulating), L_i = 0,
+ * m_i = -Inf.  L_i <= J cannot overflow.  Within eg_attention_bias' window the two entries agree to rounding, not to the bit.
+ * Two calls give the same bits. */
+int eg_attention_stable(eg_ctx* ctx, int64_t batch0, int64_t batch1, int64_t I, int64_t J, int64_t K, int64_t D, float scale,
+                        const float* Q, int64_t ldq, int64_t stride_q0, int64_t stride_q1,
+                        const float* Kk, int64_t ldk, int64_t stride_k0, int64_t stride_k1,
+                        const float* V, int64_t ldv, int64_t stride_v0, int64_t stride_v1,
+                        float* O, int64_t ldo, int64_t stride_o0, int64_t stride_o1, int accumulate,
+                        float* Stats, int64_t lds, int64_t stride_s0, int64_t stride_s1,
+                        const float* Bias, int64_t ldb, int64_t stride_b0, int64_t stride_b1);
+
+/* The backward of eg_attention_stable: the operands of eg_attention_bias_grad with Stats, lds and its strides in place of
+ * Sums and its strides; O and Stats come from eg_attention_stable (accumulate == 0) on the same operands and the same Bias.
+ * The formulas are eg_attention_grad's with p_ij = expf(x_ij - m_i) / L_i.  eg_attention_grad's two kernels with one more
+ * compile-time flag (kernels/attention_grad_stable_f32.hip): the maximum rides with 1 / L and delta, the exponent gets one
+ * subtraction.
+ *   - Stats is required when I > 0 and J > 0.  EG_ERR_INVALID, with a message that names eg_attention_stable_grad: lds < I;
+ *     a negative stride_s0 or stride_s1; Stats sharing addresses (as above); a negative stride_b0 or stride_b1; 0 < ldb < J.
+ *   - EG_ERR_UNSUPPORTED, naming eg_attention_stable_grad and the limit: K > 128 or D > 128.
+ *   - Every other refusal, every empty extent and the accumulate bits are eg_attention_bias_grad's.  Stats is read with
+ *     16-byte loads when it is 16-byte aligned and lds and both strides are multiples of 4; same bits either way.
+ * A masked key (-Inf) has p_ij = 0.  A row whose L_i is 0 (every key masked) or whose stats are not finite is NaN in dQ and
+ * makes dK and dV NaN, as in eg_attention_bias_grad.  No gradient of the bias: eg_attention_bias_dbias reads the as-written
+ * sums, not these stats.  Two calls give the same bits. */
+int eg_attention_stable_grad(eg_ctx* ctx, int64_t batch0, int64_t batch1, int64_t I, int64_t J, int64_t K, int64_t D, float scale,
+                             const float* Q, int64_t ldq, int64_t stride_q0, int64_t stride_q1,
+                             const float* Kk, int64_t ldk, int64_t stride_k0, int64_t stride_k1,
+                             const float* V, int64_t ldv, int64_t stride_v0, int64_t stride_v1,
+                             const float* O, int64_t ldo, int64_t stride_o0, int64_t stride_o1,
+                             const float* Stats, int64_t lds, int64_t stride_s0, int64_t stride_s1,
+                             const float* dO, int64_t lddo, int64_t stride_do0, int64_t stride_do1,
+                             float* dQ, int64_t lddq, int64_t stride_dq0, int64_t stride_dq1,
+                             float* dK, int64_t lddk, int64_t stride_dk0, int64_t stride_dk1,
+                             float* dV, int64_t lddv, int64_t stride_dv0, int64_t stride_dv1, int accumulate,
+                             const float* Bias, int64_t ldb, int64_t stride_b0, int64_t stride_b1);
+
 /* out[y,x] (+)= bias[x]   — dense's second kernel, dnn.nim:22-24. out is [rows, cols]. */
 int eg_bias_add(eg_ctx* ctx, int64_t rows, int64_t cols, const float* bias, float* out,
                 int accumulate);
@@ -767,6 +821,16 @@ int eg_model_batched2_f64(eg_model* model, int on);
  * EG_ERR_INVALID: a NULL model, a float32 model (its chains take the route already).  The setting is part of the plan key;
  * the default is off, and with it off every plan, launch and bit is what it was. */
 int eg_model_fuse_attention_f64(eg_model* model, int on);
+/* The forward attention chains of a float32 model on the kernel with a running row maximum.  on != 0: from the next run on,
+ * every eg_attn launch of a forward group (with or without a bias input) goes to eg_attention_stable's kernel instead of
+ * eg_attention's.  The groups that form, and the launch lists, are the same.
+ * THE SWITCH TRADES THE PROGRAM'S SPECIAL VALUES FOR FINITE RESULTS: the program computes exp(x) without a maximum and is NaN
+ * for a row with a score above about 88.7 or with only scores below about -103; under the switch such rows are finite, and
+ * within the window the results agree with the program's to rounding, not to the bit.
+ * What keeps the as-written kernels: the forward launch of a fit group (eg_model_fuse_attention_fit), which stores the row
+ * sums its backward launch reads, and that backward launch.  EG_ERR_INVALID: a NULL model, a float64 model.  The setting is
+ * part of the plan key; the default is off, and with it off every plan, launch and bit is what it was. */
+int eg_model_fuse_attention_stable(eg_model* model, int on);
 
 /* Model.epoch (model.nim:39, bumped by fit at model.nim:436). */
 int eg_model_set_epoch(eg_model* model, int64_t epoch);
