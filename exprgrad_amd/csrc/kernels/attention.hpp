@@ -33,7 +33,17 @@ int attention_grad(eg_ctx* ctx, const Extents& e, float scale, const float* Q, V
 // item, st.ld apart: the maxima m and the sums L.  Its backward is attention_grad with `stable`, Sums that Stats and s its view
 // (s.ld the step between the two rows): p_ij = expf(x_ij - m_i) / L_i, the STABLE kernels of attention_grad_stable_f32.hip.
 int attention_stable(eg_ctx* ctx, const Extents& e, float scale, const float* Q, View q, const float* Kk, View k, const float* V, View v, float* O,
-                     View o, int accumulate, float* Stats = nullptr, View st = {}, const float* Bias = nullptr, View bv = {});
+                     View o, int accumulate, float* Stats = nullptr, View st = {}, const float* Bias = nullptr, View bv = {},
+                     const char* entry = nullptr);
+// What that entry refuses, under the name `name`; *nothing: valid, and nothing to compute or store.
+int attention_stable_check(eg_ctx* ctx, const Extents& e, const float* Q, View q, const float* Kk, View k, const float* V, View v, float* O, View o,
+                           int accumulate, float* Stats, View st, const float* Bias, View bv, const char* name, bool* nothing);
+
+// The same forward split over the keys (attention_split_f32.hip, eg_attention_stable_split): `splits` blocks per item and row
+// tile leave partial results in the context's workspace and one more launch combines them; up to 16 query rows the four waves
+// of a block split the keys of a tile.  splits == 0: plan_attention_split chooses.  Stats serve attention_grad with `stable`.
+int attention_stable_split(eg_ctx* ctx, const Extents& e, float scale, const float* Q, View q, const float* Kk, View k, const float* V, View v,
+                           float* O, View o, int accumulate, float* Stats, View st, const float* Bias, View bv, int splits);
 
 // The gradient of that bias (attention_dbias_f32.hip): eg_attention_bias_dbias, over what attention_forward left with Sums and
 // the same Bias.  dBias (+)= the sum of p * (dP - delta) over every index whose step in `db` is 0; db.ld and both its strides

@@ -54,6 +54,47 @@ Plan plan_forward(const Problem& p, bool f64) {
 Plan plan_attention(const Problem& p) { return plan_forward(p, false); }
 Plan plan_attention_f64(const Problem& p) { return plan_forward(p, true); }
 
+// The forward split over the keys.  The auto rule splits only a launch that leaves CUs without a block, and then into as many
+// ranges as give every CU the blocks it can hold at once (split_blocks_per_cu), none shorter than SPLIT_MIN_TILES key tiles.
+SplitPlan plan_attention_split(const Problem& p, int splits) {
+  SplitPlan r;
+  if (splits < 0) {
+    r.reason = "a negative number of splits";
+    return r;
+  }
+  r.base = plan_forward(p, false);
+  if (!r.base.supported) {
+    r.reason = r.base.reason;
+    return r;
+  }
+  const Plan& b = r.base;
+  r.rows16 = p.I <= SPLIT_ROWS16;
+  r.nt = (p.J + TILE_J - 1) / TILE_J;
+  const long most = std::max(1L, r.nt);
+  if (splits == 0) {
+    const long blocks = b.items * b.tiles_i, target = split_blocks_per_cu(b.kp, b.dp) * p.cus;
+    r.splits = 1;
+    if (blocks < p.cus && r.nt >= 2) r.splits = (int)std::max(1L, std::min(target / blocks, r.nt / SPLIT_MIN_TILES));
+  } else {
+    r.splits = (int)std::min((long)splits, most);
+  }
+  r.forward = p.J == 0 || p.D == 0 || (!r.rows16 && r.splits == 1);
+  if (b.tiles_i * r.splits > eg::gemm::BATCHED_MAX_BLOCKS) {
+    r.reason = "an item has more row tiles times splits than one launch has blocks";
+    return r;
+  }
+  r.rows_pad = r.rows16 ? SPLIT_ROWS16 : TILE_I * b.tiles_i;
+  r.stats_offset = b.items * r.splits * r.rows_pad * b.dp;
+  r.workspace_bytes = r.forward ? 0 : 4L * (r.stats_offset + b.items * r.splits * 2 * r.rows_pad);
+  r.partial = cut_items(b.items, b.tiles_i * r.splits);
+  r.combine_rows = b.items * r.rows_pad;
+  r.combine_rows_per_block = 4 * THREADS / b.dp;
+  r.combine_grid = std::min(eg::gemm::BATCHED_MAX_BLOCKS, (r.combine_rows + r.combine_rows_per_block - 1) / r.combine_rows_per_block);
+  r.lds_bytes = r.rows16 ? split16_lds_bytes(b.kp, b.dp) : b.lds_bytes;
+  r.supported = true;
+  return r;
+}
+
 namespace {
 
 // The backward's plan in either scalar type: the two differ in the steps, the LDS rows and the 16-byte rule.  Empty I, J, K

@@ -72,6 +72,67 @@ Plan plan_attention(const Problem& p);
 // Launch `index` of a plan, index in [0, plan.launches): the cut's, for a caller that holds the plan.
 inline Launch plan_launch(const Plan& plan, long index) { return plan_launch(plan.items, plan.cut(), index); }
 
+// ---- The forward split over the keys (attention_split_f32.hip, eg_attention_stable_split): `splits` blocks per item and row
+// tile, each over a contiguous range of key tiles, leave partial results (unnormalised O rows, maximum, sum) in the context's
+// workspace; one more launch combines them.  Two modes of the partial kernel: above 16 query rows the block of plan_attention
+// (four waves of 16 rows each); up to 16 rows the four waves hold the same 16 rows and each takes 16 keys of every 64-key tile.
+constexpr int SPLIT_ROWS16 = 16;   // I up to here: the waves split the keys, not the rows
+
+// The auto rule (splits == 0): split only when items * tiles_i is below the CU count and there are two key tiles or more; then
+// splits = min(blocks_per_cu * cus / blocks, nt / SPLIT_MIN_TILES), at least 1.  Its constants, from profiles/attention_split.txt
+// section 2 (one MI355X, 256 CUs; microseconds per call, median of three fresh processes, every spread at most 1.7 us and at
+// most 0.8 us at the best counts; heads x I x J x K=D; `stable` is eg_attention_stable):
+//   shape            stable  splits 1      2      4      8     16     32     64    128    256   auto picks
+//   32x1x8192x128     833.9     387.4  200.1  106.8   64.7   72.6   86.7  114.8  173.6            8
+//   32x16x8192x128    841.2     398.1  207.0  110.3   66.9   75.7   90.3  126.9  193.4            8
+//   8x128x16384x64   1008.2    1008.7  519.4  268.3  141.1   80.3   75.7   94.3  128.0  199.5    32
+//   128x512x512x64    110.5     111.0  125.0  136.4  165.5                                        1 (blocks >= CUs)
+//   4x16x2048x128     215.5     106.5   58.0   34.1   23.3   20.1   22.5                         16
+//   2x128x2048x64     131.5     131.5   71.9   40.8   27.0   22.8   27.1                         16
+//  - blocks per CU: the best count makes 256 blocks at K = D = 128 (32 x 8) and 512 at K = D = 64 (16 x 32): as many as run at
+//    once.  By the resource table (section 1) the kernels with kp + dp >= 192 have one wave per SIMD by registers, one block
+//    per CU, and those below two or more; no count beyond two per CU measured faster, so the rule stops at two.  With one per CU
+//    at 8x128x16384x64 the rule picked 16 (80.5 us against 76.2 at 32: outside the spread; section 3 keeps that run).
+//  - SPLIT_MIN_TILES: on the two shapes whose blocks stay below the CUs at every count, 16 splits of two tiles beat 32 of one
+//    (20.1 / 22.5 and 22.8 / 27.1) and 8 of four (23.3, 27.0).
+// At every measured shape auto's count is the best measured one (the difference is within the spread), and where auto does not
+// split no count measured faster than one.  Not measured: other head sizes, a bias, more than one launch.
+constexpr long SPLIT_MIN_TILES = 2;
+constexpr long split_blocks_per_cu(int kp, int dp) { return kp + dp >= 192 ? 1 : 2; }
+
+struct SplitPlan {
+  bool supported = false;
+  const char* reason = "";
+  Plan base;                 // plan_attention's: padded heads, load widths, tiles_i, items
+  bool rows16 = false;       // the mode
+  bool forward = false;      // nothing to split (J == 0, D == 0, or the 64-row mode with one split): eg_attention_stable, the same bits
+  long nt = 0;               // key tiles of 64
+  int splits = 0;            // effective: 1 .. max(nt, 1)
+  long rows_pad = 0;         // rows of an item in the workspace: 16, or 64 * tiles_i
+  // The workspace: O parts [items][splits][rows_pad][dp] floats, then maxima and sums [items][splits][2][rows_pad].
+  long stats_offset = 0;     // in floats
+  long workspace_bytes = 0;
+  Cut partial;               // tiles_i * splits blocks per item
+  long combine_rows = 0;     // items * rows_pad
+  int combine_rows_per_block = 0;   // 256 threads, one per four columns of a row: 1024 / dp
+  long combine_grid = 0;     // one launch; a block walks rows combine_rows_per_block * grid apart
+  int block = THREADS;
+  long lds_bytes = 0;        // of the partial kernel
+};
+
+// Floats per row of a wave's own E rows in the 16-row mode, [16][16 + 4]: attention_split_f32.hip has the bank arithmetic.
+constexpr int SPLIT_ES16 = 16 + 4;
+// 16-row mode: K tile [64][kp + 4], V tile [64][dp + 16], E rows [4 waves][16][20]; the merge of the four waves lives in the
+// K and V tiles.
+inline long split16_lds_bytes(int kp, int dp) { return 4L * (TILE_J * (kp + 4) + TILE_J * (dp + 16) + 4 * 16 * SPLIT_ES16); }
+
+// Split s of `splits` over nt key tiles takes tiles [split_first(nt, splits, s), split_first(nt, splits, s + 1)): non-empty for
+// splits <= nt, and together [0, nt).  constexpr: the kernels call it too.
+constexpr long split_first(long nt, int splits, int s) { return (long)s * nt / splits; }
+
+// splits: 0 the auto rule, n >= 1 that many, clamped to the key tiles (negative: not supported).
+SplitPlan plan_attention_split(const Problem& p, int splits);
+
 // ---- The float64 forward (attention_f64.hip): the same tile of 64 query rows and the same padded head dimensions on
 // v_mfma_f64_16x16x4_f64.  Problem and Plan are the ones above; what differs is decided here, not in the kernel: the key tile
 // (Plan::tile_j, 64 or 32 keys), the LDS rows in doubles, and 16-byte loads that hold two elements.

@@ -57,27 +57,6 @@ struct StableBiasArgs : StableArgs {
   In b;
 };
 
-// The value of the lane N places on in its DPP row of 16, wrapping round (row_ror:N); through the LDS crossbar where the
-// compiler has no DPP builtin.
-template <int N>
-__device__ __forceinline__ float row_rotate(float v) {
-#if __has_builtin(__builtin_amdgcn_update_dpp)
-  const int b = __builtin_bit_cast(int, v);
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(b, b, 0x120 + N, 0xF, 0xF, false));
-#else
-  return __shfl_xor(v, N);   // another partner, the same maximum after the four steps
-#endif
-}
-
-// The maximum over the 16 lanes of a DPP row, in every one of them.
-__device__ __forceinline__ float row_max16(float v) {
-  v = fmaxf(v, row_rotate<8>(v));
-  v = fmaxf(v, row_rotate<4>(v));
-  v = fmaxf(v, row_rotate<2>(v));
-  v = fmaxf(v, row_rotate<1>(v));
-  return v;
-}
-
 template <int KP, int DP, bool BIAS>
 __global__ __launch_bounds__(THREADS) void attention_stable_f32_kernel(std::conditional_t<BIAS, StableBiasArgs, StableArgs> a) {
   constexpr int KS = KP + 4, VS = DP + 16;
@@ -249,9 +228,9 @@ int launch(eg_ctx* ctx, unsigned grid, const Plan& p, const Args& args) {
 namespace eg {
 namespace attention {
 
-int attention_stable(eg_ctx* ctx, const Extents& e, float scale, const float* Q, View q, const float* Kk, View k, const float* V, View v, float* O,
-                     View o, int accumulate, float* Stats, View st, const float* Bias, View bv) {
-  const char* const name = "eg_attention_stable";
+int attention_stable_check(eg_ctx* ctx, const Extents& e, const float* Q, View q, const float* Kk, View k, const float* V, View v, float* O, View o,
+                           int accumulate, float* Stats, View st, const float* Bias, View bv, const char* name, bool* nothing) {
+  *nothing = true;
   const long batch0 = e.batch0, batch1 = e.batch1, I = e.I, J = e.J, K = e.K, D = e.D;
   EG_REQUIRE(ctx, EG_ERR_INVALID, "%s: ctx is NULL", name);
   EG_REQUIRE(batch0 >= 0 && batch1 >= 0 && I >= 0 && J >= 0 && K >= 0 && D >= 0, EG_ERR_INVALID, "%s: negative extent", name);
@@ -275,7 +254,18 @@ int attention_stable(eg_ctx* ctx, const Extents& e, float scale, const float* Q,
   EG_REQUIRE(K <= MAX_HEAD, EG_ERR_UNSUPPORTED, "%s: K = %ld is above the limit of %d", name, K, MAX_HEAD);
   EG_REQUIRE(D <= MAX_HEAD, EG_ERR_UNSUPPORTED, "%s: D = %ld is above the limit of %d", name, D, MAX_HEAD);
   if (J == 0 && accumulate && !Stats) return EG_OK;   // an empty sum adds nothing
-  const int rc = eg::set_device(ctx);
+  *nothing = false;
+  return EG_OK;
+}
+
+int attention_stable(eg_ctx* ctx, const Extents& e, float scale, const float* Q, View q, const float* Kk, View k, const float* V, View v, float* O,
+                     View o, int accumulate, float* Stats, View st, const float* Bias, View bv, const char* entry) {
+  const char* const name = entry ? entry : "eg_attention_stable";
+  const long batch1 = e.batch1, I = e.I, J = e.J, K = e.K, D = e.D;
+  bool nothing = false;
+  int rc = attention_stable_check(ctx, e, Q, q, Kk, k, V, v, O, o, accumulate, Stats, st, Bias, bv, name, &nothing);
+  if (rc || nothing) return rc;
+  rc = eg::set_device(ctx);
   if (rc) return rc;
 
   Problem pr;

@@ -135,6 +135,28 @@ __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// ---- a row maximum over a DPP row (the kernels with a running maximum: attention_stable_f32.hip, attention_split_f32.hip) ----
+// The value of the lane N places on in its DPP row of 16, wrapping round (row_ror:N); through the LDS crossbar where the
+// compiler has no DPP builtin.
+template <int N>
+__device__ __forceinline__ float row_rotate(float v) {
+#if __has_builtin(__builtin_amdgcn_update_dpp)
+  const int b = __builtin_bit_cast(int, v);
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(b, b, 0x120 + N, 0xF, 0xF, false));
+#else
+  return __shfl_xor(v, N);   // another partner, the same maximum after the four steps
+#endif
+}
+
+// The maximum over the 16 lanes of a DPP row, in every one of them.
+__device__ __forceinline__ float row_max16(float v) {
+  v = fmaxf(v, row_rotate<8>(v));
+  v = fmaxf(v, row_rotate<4>(v));
+  v = fmaxf(v, row_rotate<2>(v));
+  v = fmaxf(v, row_rotate<1>(v));
+  return v;
+}
+
 // ---- the products, on v_mfma_f32_16x16x4_f32 ----------------------------------------------------------------------------
 // Lane (c, g) = (lane & 15, lane >> 4) gives A[row c][k = g] and B[k = g][col c] and receives D[row 4 g + r][col c] in
 // element r.  Each loop has the k step outside and the column block inside: an accumulator sees its additions in k order.

@@ -137,6 +137,17 @@ def attention_stable(ctx, batch0, batch1, I, J, K, D, scale, Q, ldq, strides_q, 
          lds, strides_s[0], strides_s[1], _p(Bias), ldb, strides_b[0], strides_b[1])
 
 
+def attention_stable_split(ctx, batch0, batch1, I, J, K, D, scale, Q, ldq, strides_q, Kk, ldk, strides_k, V, ldv, strides_v, O, ldo, strides_o,
+                           Stats=None, lds=0, strides_s=(0, 0), Bias=None, ldb=0, strides_b=(0, 0), accumulate=False, splits=0):
+    """`attention_stable` with every item's keys split into `splits` ranges of 64-key tiles (0: the library chooses; more than
+    there are tiles: one per tile): one block per item, row tile and range, and one launch that combines them.  For few query
+    rows against many keys, where `attention_stable` leaves most of the device idle; up to 16 rows the four waves of a block
+    share the keys of a tile.  The same result to rounding, not to the bit; Stats serve attention_stable_grad."""
+    call("eg_attention_stable_split", ctx.handle, batch0, batch1, I, J, K, D, float(scale), _p(Q), ldq, strides_q[0], strides_q[1], _p(Kk), ldk,
+         strides_k[0], strides_k[1], _p(V), ldv, strides_v[0], strides_v[1], _p(O), ldo, strides_o[0], strides_o[1], int(accumulate), _p(Stats),
+         lds, strides_s[0], strides_s[1], _p(Bias), ldb, strides_b[0], strides_b[1], int(splits))
+
+
 def attention_stable_grad(ctx, batch0, batch1, I, J, K, D, scale, Q, ldq, strides_q, Kk, ldk, strides_k, V, ldv, strides_v, O, ldo, strides_o,
                           Stats, lds, strides_s, dO, lddo, strides_do, dQ, lddq, strides_dq, dK, lddk, strides_dk, dV, lddv, strides_dv,
                           Bias=None, ldb=0, strides_b=(0, 0), accumulate=0):

@@ -512,6 +512,35 @@ int eg_attention_stable(eg_ctx* ctx, int64_t batch0, int64_t batch1, int64_t I, 
                         float* Stats, int64_t lds, int64_t stride_s0, int64_t stride_s1,
                         const float* Bias, int64_t ldb, int64_t stride_b0, int64_t stride_b1);
 
+/* eg_attention_stable with every item's keys split into ranges: for launches whose batch0 * batch1 * ceil(I / 64) blocks leave
+ * most of the device idle — one long sequence, or a few query rows against a key/value cache.  The first 33 arguments and
+ * their contract are eg_attention_stable's (its table of special values included); the refusals name
+ * eg_attention_stable_split.
+ *   splits == 0: the planner chooses (plan_attention_split: it splits only when the blocks are fewer than the compute units
+ *                and there are at least two 64-key tiles, into about compute units / blocks ranges, none below a measured
+ *                minimum of tiles; kernels/attention_plan.hpp has the rule and the measurements it came from);
+ *   splits >= 1: that many ranges, clamped to the number of 64-key tiles (at least 1);
+ *   splits <  0: EG_ERR_INVALID.
+ * Split s of S takes key tiles [s * nt / S, (s + 1) * nt / S).  Two launches (kernels/attention_split_f32.hip): one block per
+ * item, row tile and split leaves the row maxima, the sums relative to them and the unnormalised O rows of its range in the
+ * context's workspace; a second kernel combines them with weights expf(m_s - M), s ascending, divides, and stores O and Stats.
+ * With I <= 16 the four waves of a block hold the same rows and each takes 16 keys of every 64-key tile (they would otherwise
+ * multiply zero rows); this mode runs its pair of kernels also with one split.
+ *   - The same mathematical result as eg_attention_stable; the bits differ, because the sums are taken in another, fixed
+ *     order.  No atomics: two calls give the same bits, and any splits above the number of key tiles give the bits of that
+ *     number.  J == 0, D == 0, and I > 16 with one effective split are eg_attention_stable's launch, with its bits.
+ *   - Stats (the true row maximum and the sum relative to it) are valid input to eg_attention_stable_grad.
+ *   - EG_ERR_UNSUPPORTED also when ceil(I / 64) * splits exceeds 2^22, the blocks of one launch.
+ *   - The workspace grows to batch0 * batch1 * splits * rows * (Dp + 2) floats, rows = 16 or 64 * ceil(I / 64) and Dp = D padded
+ *     to 32, 64 or 128; like every entry that uses the workspace, calls on one context must not run concurrently. */
+int eg_attention_stable_split(eg_ctx* ctx, int64_t batch0, int64_t batch1, int64_t I, int64_t J, int64_t K, int64_t D, float scale,
+                              const float* Q, int64_t ldq, int64_t stride_q0, int64_t stride_q1,
+                              const float* Kk, int64_t ldk, int64_t stride_k0, int64_t stride_k1,
+                              const float* V, int64_t ldv, int64_t stride_v0, int64_t stride_v1,
+                              float* O, int64_t ldo, int64_t stride_o0, int64_t stride_o1, int accumulate,
+                              float* Stats, int64_t lds, int64_t stride_s0, int64_t stride_s1,
+                              const float* Bias, int64_t ldb, int64_t stride_b0, int64_t stride_b1, int splits);
+
 /* The backward of eg_attention_stable: the operands of eg_attention_bias_grad with Stats, lds and its strides in place of
  * Sums and its strides; O and Stats come from eg_attention_stable (accumulate == 0) on the same operands and the same Bias.
  * The formulas are eg_attention_grad's with p_ij = expf(x_ij - m_i) / L_i.  eg_attention_grad's two kernels with one more
