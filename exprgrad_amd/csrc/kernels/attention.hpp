@@ -26,15 +26,18 @@ int attention_forward_f64(eg_ctx* ctx, const Extents& e, double scale, const dou
 // (eg_attention_bias_grad) the probabilities are those of the biased forward; no gradient of the bias is produced.
 int attention_grad(eg_ctx* ctx, const Extents& e, float scale, const float* Q, View q, const float* Kk, View k, const float* V, View v,
                    const float* O, View o, const float* Sums, View s, const float* dO, View dout, float* dQ, View dq, float* dK, View dk, float* dV,
-                   View dv, int accumulate, const float* Bias = nullptr, View bv = {}, const char* entry = nullptr, bool stable = false);
+                   View dv, int accumulate, const float* Bias = nullptr, View bv = {}, const char* entry = nullptr, bool stable = false,
+                   long causal_offset = -1);
 
 // The forward with a running row maximum (attention_stable_f32.hip): eg_attention_stable and a model's forward attention
 // launches under eg_model_fuse_attention_stable.  e_ij = expf(x_ij - m_i); Stats, when not NULL, takes two rows of I floats per
 // item, st.ld apart: the maxima m and the sums L.  Its backward is attention_grad with `stable`, Sums that Stats and s its view
 // (s.ld the step between the two rows): p_ij = expf(x_ij - m_i) / L_i, the STABLE kernels of attention_grad_stable_f32.hip.
+// causal_offset >= 0 (eg_attention_causal, attention_causal_f32.hip): key j is visible to row i iff j <= i + causal_offset, and
+// key tiles without a visible key are not visited; the same bits as a Bias of -Inf there.  attention_grad takes the same offset.
 int attention_stable(eg_ctx* ctx, const Extents& e, float scale, const float* Q, View q, const float* Kk, View k, const float* V, View v, float* O,
                      View o, int accumulate, float* Stats = nullptr, View st = {}, const float* Bias = nullptr, View bv = {},
-                     const char* entry = nullptr);
+                     const char* entry = nullptr, long causal_offset = -1);
 // What that entry refuses, under the name `name`; *nothing: valid, and nothing to compute or store.
 int attention_stable_check(eg_ctx* ctx, const Extents& e, const float* Q, View q, const float* Kk, View k, const float* V, View v, float* O, View o,
                            int accumulate, float* Stats, View st, const float* Bias, View bv, const char* name, bool* nothing);

@@ -27,7 +27,8 @@
 // shared banks.  Tiles read both ways have rows of width + 20 floats, tiles read NT only of width + 4.
 //
 // The kernels themselves are templates in attention_grad_f32.hpp; this file instantiates them for eg_attention_grad and
-// eg_attention_bias_grad, and attention_grad_stable_f32.hip for eg_attention_stable_grad.
+// eg_attention_bias_grad, attention_grad_stable_f32.hip for eg_attention_stable_grad, and attention_grad_causal_f32.hip and
+// attention_grad_causal_bias_f32.hip for eg_attention_causal_grad.
 #include "gemm_plan.hpp"        // batched2_c_distinct
 #include "attention.hpp"        // the internal entry
 #include "attention_grad_f32.hpp"   // the two kernels and their launch
@@ -37,7 +38,8 @@ namespace attention {
 
 int attention_grad(eg_ctx* ctx, const Extents& e, float scale, const float* Q, View q, const float* Kk, View k, const float* V, View v,
                    const float* O, View o, const float* Sums, View s, const float* dO, View dout, float* dQ, View dq, float* dK, View dk, float* dV,
-                   View dv, int accumulate, const float* Bias, View bv, const char* entry, bool stable) {
+                   View dv, int accumulate, const float* Bias, View bv, const char* entry, bool stable, long causal_offset) {
+  const bool causal = causal_offset >= 0;   // eg_attention_causal_grad, which is `stable` too
   const char* const name = entry ? entry : "eg_attention_grad";   // the entry the messages speak of
   const long batch0 = e.batch0, batch1 = e.batch1, I = e.I, J = e.J, K = e.K, D = e.D;
   EG_REQUIRE(ctx, EG_ERR_INVALID, "%s: ctx is NULL", name);
@@ -93,7 +95,8 @@ int attention_grad(eg_ctx* ctx, const Extents& e, float scale, const float* Q, V
   const GradPlan p = plan_attention_grad(pr);
   EG_REQUIRE(p.supported, EG_ERR_UNSUPPORTED, "%s: %s", name, p.reason);
 
-  GradBiasArgs args = {};
+  GradCausalArgs args = {};
+  args.offset = causal_offset < J ? causal_offset : J;   // an offset of J - 1 or more masks nothing
   args.q = {Q, q, p.vec_q}, args.k = {Kk, k, p.vec_k}, args.v = {V, v, p.vec_v}, args.o = {O, o, p.vec_o}, args.s = {Sums, s, p.vec_s};
   args.dout = {dO, dout, p.vec_do}, args.dq = {dQ, dq, p.vec_dq}, args.dk = {dK, dk, p.vec_dk}, args.dv = {dV, dv, p.vec_dv};
   args.b = {Bias, bv, p.vec_b};
@@ -107,6 +110,7 @@ int attention_grad(eg_ctx* ctx, const Extents& e, float scale, const float* Q, V
       args.items = items;
       return dispatch_heads(p.kp, p.dp, [&](auto KP, auto DP) {
         constexpr int kp = KP(), dp = DP();
+        if (causal) return Bias ? launch_grad_causal_bias(ctx, dkv, grid, p, args) : launch_grad_causal(ctx, dkv, grid, p, args);
         if (stable) return launch_grad_stable(ctx, dkv, grid, p, args);
         return Bias ? launch<&attention_dq_kernel<kp, dp, true>, &attention_dkv_kernel<kp, dp, true>, GradBiasArgs, kp, dp>(ctx, dkv, grid, p, args)
                     : launch<&attention_dq_kernel<kp, dp, false>, &attention_dkv_kernel<kp, dp, false>, GradArgs, kp, dp>(ctx, dkv, grid, p, args);
@@ -170,4 +174,23 @@ extern "C" int eg_attention_stable_grad(eg_ctx* ctx, int64_t batch0, int64_t bat
                                        {lddo, stride_do0, stride_do1}, dQ, {lddq, stride_dq0, stride_dq1}, dK, {lddk, stride_dk0, stride_dk1}, dV,
                                        {lddv, stride_dv0, stride_dv1}, accumulate, Bias, {ldb, stride_b0, stride_b1}, "eg_attention_stable_grad",
                                        true);
+}
+
+extern "C" int eg_attention_causal_grad(eg_ctx* ctx, int64_t batch0, int64_t batch1, int64_t I, int64_t J, int64_t K, int64_t D, float scale,
+                                        const float* Q, int64_t ldq, int64_t stride_q0, int64_t stride_q1,
+                                        const float* Kk, int64_t ldk, int64_t stride_k0, int64_t stride_k1,
+                                        const float* V, int64_t ldv, int64_t stride_v0, int64_t stride_v1,
+                                        const float* O, int64_t ldo, int64_t stride_o0, int64_t stride_o1,
+                                        const float* Stats, int64_t lds, int64_t stride_s0, int64_t stride_s1,
+                                        const float* dO, int64_t lddo, int64_t stride_do0, int64_t stride_do1,
+                                        float* dQ, int64_t lddq, int64_t stride_dq0, int64_t stride_dq1,
+                                        float* dK, int64_t lddk, int64_t stride_dk0, int64_t stride_dk1,
+                                        float* dV, int64_t lddv, int64_t stride_dv0, int64_t stride_dv1, int accumulate,
+                                        const float* Bias, int64_t ldb, int64_t stride_b0, int64_t stride_b1, int64_t offset) {
+  EG_REQUIRE(offset >= 0, EG_ERR_INVALID, "eg_attention_causal_grad: offset is negative: the first rows would see no key");
+  return eg::attention::attention_grad(ctx, {batch0, batch1, I, J, K, D}, scale, Q, {ldq, stride_q0, stride_q1}, Kk, {ldk, stride_k0, stride_k1}, V,
+                                       {ldv, stride_v0, stride_v1}, O, {ldo, stride_o0, stride_o1}, Stats, {lds, stride_s0, stride_s1}, dO,
+                                       {lddo, stride_do0, stride_do1}, dQ, {lddq, stride_dq0, stride_dq1}, dK, {lddk, stride_dk0, stride_dk1}, dV,
+                                       {lddv, stride_dv0, stride_dv1}, accumulate, Bias, {ldb, stride_b0, stride_b1}, "eg_attention_causal_grad",
+                                       true, offset);
 }

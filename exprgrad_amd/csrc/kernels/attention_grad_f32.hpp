@@ -1,6 +1,7 @@
 // The two kernels of the fused float32 attention backward and their launch, as templates: attention_grad_f32.hip has the
 // formulas, the LDS rows and the instantiations of eg_attention_grad and eg_attention_bias_grad, attention_grad_stable_f32.hip
-// those of eg_attention_stable_grad (STABLE), a translation unit of its own so that the two sets compile side by side.
+// those of eg_attention_stable_grad (STABLE), a translation unit of its own so that the two sets compile side by side, and
+// attention_grad_causal_f32.hip and attention_grad_causal_bias_f32.hip those of eg_attention_causal_grad (STABLE and CAUSAL).
 #pragma once
 
 #include "attention_tile.hpp"        // kernel operands, tiles, the MFMA loops, the launcher
@@ -29,11 +30,19 @@ struct GradBiasArgs : GradArgs {
 };
 // The STABLE kernels (eg_attention_stable_grad) take GradBiasArgs with or without BIAS: `s` is the forward's Stats, row 0
 // the maxima and row 1, s.v.ld floats on, the sums.
-template <bool BIAS, bool STABLE>
-using ArgsOf = std::conditional_t<BIAS || STABLE, GradBiasArgs, GradArgs>;
+// The CAUSAL kernels (eg_attention_causal_grad; STABLE too) take these with or without BIAS: key j is visible to row i iff
+// j <= i + offset, 0 <= offset <= J.
+struct GradCausalArgs : GradBiasArgs {
+  long offset;
+};
+template <bool BIAS, bool STABLE, bool CAUSAL = false>
+using ArgsOf = std::conditional_t<CAUSAL, GradCausalArgs, std::conditional_t<BIAS || STABLE, GradBiasArgs, GradArgs>>;
 
 // One launch of the STABLE dQ kernel or dK/dV kernel (attention_grad_stable_f32.hip), BIAS where args.b.p is not NULL.
 int launch_grad_stable(eg_ctx* ctx, bool dkv, unsigned grid, const GradPlan& p, const GradBiasArgs& args);
+// The same of the CAUSAL kernels: without a bias (attention_grad_causal_f32.hip) and with one (attention_grad_causal_bias_f32.hip).
+int launch_grad_causal(eg_ctx* ctx, bool dkv, unsigned grid, const GradPlan& p, const GradCausalArgs& args);
+int launch_grad_causal_bias(eg_ctx* ctx, bool dkv, unsigned grid, const GradPlan& p, const GradCausalArgs& args);
 
 }  // namespace attention
 }  // namespace eg
@@ -54,8 +63,18 @@ constexpr int TILE = 64;
 // STABLE (both kernels): p_ij = expf(x_ij - m_i) / L_i with m and L from eg_attention_stable's Stats: the rows' small LDS array
 // holds the maximum as a third column and the exponent gets one subtraction.  Again a compile-time flag: every line of it is
 // under `if constexpr`, and the instantiations without it are the kernels they were.
-template <int KP, int DP, bool BIAS, bool STABLE = false>
-__global__ __launch_bounds__(THREADS) void attention_dq_kernel(ArgsOf<BIAS, STABLE> a) {
+// CAUSAL (both kernels, with STABLE): which tiles of the other axis a block visits, and the cut of the diagonal; the third
+// compile-time flag of the same kind (attention_plan.hpp has the bounds).  A masked pair's x is -Inf by a select where the bias
+// is added, so p and dS are the zeros that a Bias of -Inf gives, and the tiles that are not visited would have added zeros.
+//   dQ     the row tile is tiles - 1 - b.tile (the longest loops first); the loop over key tiles and its prefetch stop at
+//          causal_key_tiles, and no key at or beyond causal_visible_keys is loaded; on a cut tile lim[r] is the last visible key
+//          of the lane's row r, relative to j0; a wave whose 16 rows all lie above a cut tile skips its three products;
+//   dK/dV  the loop over row tiles and its prefetch start at causal_first_row_tile; the layout is the transpose, a lane's four
+//          r are four consecutive keys of one row, so on a cut tile first[r] is the first row that sees the lane's key r,
+//          relative to i0.
+template <int KP, int DP, bool BIAS, bool STABLE = false, bool CAUSAL = false>
+__global__ __launch_bounds__(THREADS) void attention_dq_kernel(ArgsOf<BIAS, STABLE, CAUSAL> a) {
+  static_assert(STABLE || !CAUSAL, "the causal kernels read the stable forward's Stats");
   constexpr int KS = KP + GRAD_PAD_BOTH, VS = DP + GRAD_PAD_NT, SW = STABLE ? 3 : 2;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float* const Ks = lds;                  // [64][KS]: the Q tile first, dQ last
@@ -63,7 +82,7 @@ __global__ __launch_bounds__(THREADS) void attention_dq_kernel(ArgsOf<BIAS, STAB
   float* const Es = Vs + TILE * VS;       // [4][16][ES]
   float* const St = Es + 4 * 16 * ES;     // [64][SW]: 1 / L, delta, and under STABLE the maximum
 
-  const BlockItem b = block_item(a.items);
+  const BlockItem b = causal_block_item<CAUSAL>(a.items);
   const long i0 = (long)b.tile * TILE;
   const long rows = a.I - i0;
   const long read_rows = a.J > 0 ? rows : 0;   // without keys nothing is read: dQ is zeros
@@ -122,11 +141,13 @@ __global__ __launch_bounds__(THREADS) void attention_dq_kernel(ArgsOf<BIAS, STAB
     ldb = a.b.v.ld;
     Bl = item_base(a.b, b.outer, b.inner) + (i0 + w * 16 + 4 * g) * ldb + c;
   }
-  const long nt = (a.J + TILE - 1) / TILE;
+  // the keys that are loaded, and the tiles that hold those the block's rows see
+  const long keys = causal_loaded_keys<CAUSAL>(a);
+  const long nt = causal_loop_tiles<CAUSAL>(a, i0, keys);
   if (nt > 0) {
-    load_rows<KP>(tk, Kk, ldk, a.J, a.K, a.k.vec != 0, tid);
-    load_rows<DP>(tv, V, ldv, a.J, a.D, a.v.vec != 0, tid);
-    if constexpr (BIAS) load_bias(bias_next, Bl, ldb, bias_rows, a.J - c);
+    load_rows<KP>(tk, Kk, ldk, keys, a.K, a.k.vec != 0, tid);
+    load_rows<DP>(tv, V, ldv, keys, a.D, a.v.vec != 0, tid);
+    if constexpr (BIAS) load_bias(bias_next, Bl, ldb, bias_rows, keys - c);
   }
   for (long t = 0; t < nt; ++t) {
     const long j0 = t * TILE;
@@ -136,9 +157,18 @@ __global__ __launch_bounds__(THREADS) void attention_dq_kernel(ArgsOf<BIAS, STAB
     __syncthreads();
     if constexpr (BIAS) bias = bias_next;
     if (t + 1 < nt) {   // in flight during this tile's MFMAs
-      load_rows<KP>(tk, Kk + (j0 + TILE) * ldk, ldk, a.J - j0 - TILE, a.K, a.k.vec != 0, tid);
-      load_rows<DP>(tv, V + (j0 + TILE) * ldv, ldv, a.J - j0 - TILE, a.D, a.v.vec != 0, tid);
-      if constexpr (BIAS) load_bias(bias_next, Bl + j0 + TILE, ldb, bias_rows, a.J - j0 - TILE - c);
+      load_rows<KP>(tk, Kk + (j0 + TILE) * ldk, ldk, keys - j0 - TILE, a.K, a.k.vec != 0, tid);
+      load_rows<DP>(tv, V + (j0 + TILE) * ldv, ldv, keys - j0 - TILE, a.D, a.v.vec != 0, tid);
+      if constexpr (BIAS) load_bias(bias_next, Bl + j0 + TILE, ldb, bias_rows, keys - j0 - TILE - c);
+    }
+
+    [[maybe_unused]] int lim[4];
+    if constexpr (CAUSAL) {
+      // row i0 against key j0: above -64 on a visited tile and below 63 on a cut one
+      const int d0 = causal_tile_cut(i0, j0, a.offset, a.J) ? (int)(i0 + a.offset - j0) : 2 * TILE;
+      if (d0 + __builtin_amdgcn_readfirstlane(w) * 16 + 15 < 0) continue;   // the wave's last row does not see key j0
+#pragma unroll
+      for (int r = 0; r < 4; ++r) lim[r] = d0 + w * 16 + 4 * g + r;
     }
 
     f32x4 s[4], dp[4];
@@ -162,6 +192,7 @@ __global__ __launch_bounds__(THREADS) void attention_dq_kernel(ArgsOf<BIAS, STAB
       for (int r = 0; r < 4; ++r) {
         float x = s[nb][r] * a.scale;
         if constexpr (BIAS) x = x + bias.x[nb][r];
+        if constexpr (CAUSAL) x = nb * 16 + c <= lim[r] ? x : -INFINITY;
         if constexpr (STABLE) x = x - mx[r];
         const float p = expf(x) * inv[r];
         const float ds = (a.scale * p) * (dp[nb][r] - delta[r]);
@@ -185,8 +216,9 @@ __global__ __launch_bounds__(THREADS) void attention_dq_kernel(ArgsOf<BIAS, STAB
   store_out<KP, KS>(Ks, dQ, a.dq.v.ld, rows, a.K, a.dq.vec != 0, a.acc_dq != 0, tid);
 }
 
-template <int KP, int DP, bool BIAS, bool STABLE = false>
-__global__ __launch_bounds__(THREADS) void attention_dkv_kernel(ArgsOf<BIAS, STABLE> a) {
+template <int KP, int DP, bool BIAS, bool STABLE = false, bool CAUSAL = false>
+__global__ __launch_bounds__(THREADS) void attention_dkv_kernel(ArgsOf<BIAS, STABLE, CAUSAL> a) {
+  static_assert(STABLE || !CAUSAL, "the causal kernels read the stable forward's Stats");
   constexpr int QS = KP + GRAD_PAD_BOTH, DS = DP + GRAD_PAD_BOTH, SW = STABLE ? 3 : 2;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float* const Qs = lds;                  // [64][QS]: the K tile first, dK last
@@ -247,15 +279,17 @@ __global__ __launch_bounds__(THREADS) void attention_dkv_kernel(ArgsOf<BIAS, STA
     Bl = item_base(a.b, b.outer, b.inner) + c * ldb + j0 + w * 16 + 4 * g;
   }
   const long nt = (a.I + TILE - 1) / TILE;
-  if (nt > 0) {
-    load_rows<KP>(tq, Q, ldq, a.I, a.K, a.q.vec != 0, tid);
-    load_rows<DP>(td, dO, lddo, a.I, a.D, a.dout.vec != 0, tid);
-    load_o_part<DP>(po, O, ldo, a.I, a.D, a.o.vec != 0, tid);
-    sums = load_sums(S, a.I, a.s.vec != 0, tid);
-    if constexpr (STABLE) maxs = load_sums(M, a.I, a.s.vec != 0, tid);
-    if constexpr (BIAS) load_bias_t(bias_next, Bl, ldb, a.I - c, bias_keys, vec_b);
+  const long t0 = causal_loop_start<CAUSAL>(a, j0, nt);   // the first row tile with a row that sees key j0
+  if (t0 < nt) {
+    const long f0 = t0 * TILE;
+    load_rows<KP>(tq, Q + f0 * ldq, ldq, a.I - f0, a.K, a.q.vec != 0, tid);
+    load_rows<DP>(td, dO + f0 * lddo, lddo, a.I - f0, a.D, a.dout.vec != 0, tid);
+    load_o_part<DP>(po, O + f0 * ldo, ldo, a.I - f0, a.D, a.o.vec != 0, tid);
+    sums = load_sums(S + f0, a.I - f0, a.s.vec != 0, tid);
+    if constexpr (STABLE) maxs = load_sums(M + f0, a.I - f0, a.s.vec != 0, tid);
+    if constexpr (BIAS) load_bias_t(bias_next, Bl + f0 * ldb, ldb, a.I - f0 - c, bias_keys, vec_b);
   }
-  for (long t = 0; t < nt; ++t) {
+  for (long t = t0; t < nt; ++t) {
     const long i0 = t * TILE;
     __syncthreads();   // every wave is done with the tiles in LDS (the first time: with the K and V tiles)
     store_rows<KP, QS>(tq, Qs, tid);
@@ -278,6 +312,14 @@ __global__ __launch_bounds__(THREADS) void attention_dkv_kernel(ArgsOf<BIAS, STA
       if constexpr (BIAS) load_bias_t(bias_next, Bl + n0 * ldb, ldb, a.I - n0 - c, bias_keys, vec_b);
     }
     __syncthreads();   // delta of every row is in St
+
+    [[maybe_unused]] int first[4];
+    if constexpr (CAUSAL) {
+      // key j0 against row i0: at most 63 on a visited tile and above -63 on a cut one
+      const int d0 = causal_tile_cut(i0, j0, a.offset, a.J) ? (int)(j0 - a.offset - i0) : -2 * TILE;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) first[r] = d0 + w * 16 + 4 * g + r;
+    }
 
     // S^T and dP^T: rows are the wave's keys, columns the tile's query rows
     f32x4 s[4], dp[4];
@@ -308,6 +350,7 @@ __global__ __launch_bounds__(THREADS) void attention_dkv_kernel(ArgsOf<BIAS, STA
         const bool live = qlive && klive[r];
         float x = s[nb][r] * a.scale;
         if constexpr (BIAS) x = x + bias.x[nb][r];
+        if constexpr (CAUSAL) x = col >= first[r] ? x : -INFINITY;
         if constexpr (STABLE) x = x - mx;
         const float p = expf(x) * inv;
         const float ds = (a.scale * p) * (dp[nb][r] - delta);

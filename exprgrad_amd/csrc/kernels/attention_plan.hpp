@@ -133,6 +133,33 @@ constexpr long split_first(long nt, int splits, int s) { return (long)s * nt / s
 // splits: 0 the auto rule, n >= 1 that many, clamped to the key tiles (negative: not supported).
 SplitPlan plan_attention_split(const Problem& p, int splits);
 
+// ---- The causal kernels (attention_causal_f32.hip, attention_grad_causal_f32.hip; eg_attention_causal and its grad): key j
+// is visible to query row i iff j <= i + offset, offset >= 0, so every row sees key 0.  The tiles of 64 rows and 64 keys, the
+// padded heads, the load widths, the cut and the LDS are plan_attention's and plan_attention_grad's; these functions say which
+// tiles a block visits.  constexpr: the kernels call them too, so a plan and its kernel cannot disagree.
+
+// The keys that some row of an item can see: keys [0, causal_visible_keys).  Nothing at or beyond it is ever loaded.  The
+// entries clamp the offset to J (any offset >= J - 1 masks nothing), so I + offset cannot overflow.
+constexpr long causal_visible_keys(long I, long offset, long J) { return I <= 0 ? 0 : (J < I + offset ? J : I + offset); }
+
+// Forward and dQ: the block of rows [i0, i0 + 64) walks key tiles [0, causal_key_tiles): the last one holds key
+// min(J - 1, i0 + 63 + offset).  With J the item's causal_visible_keys a ragged last row tile stops at its last row's keys.
+constexpr long causal_key_tiles(long i0, long offset, long J) {
+  const long last = J - 1 < i0 + (TILE_I - 1) + offset ? J - 1 : i0 + (TILE_I - 1) + offset;
+  return J <= 0 ? 0 : last / TILE_J + 1;
+}
+
+// dK/dV: the block of keys [j0, j0 + 64) starts at the row tile that holds row max(0, j0 - offset), the first that sees key j0.
+// A block with j0 at or beyond the item's causal_visible_keys has no such row, and its loop is empty.
+constexpr long causal_first_row_tile(long j0, long offset) { return j0 > offset ? (j0 - offset) / TILE_I : 0; }
+
+// Whether the tile of rows [i0, i0 + 64) and keys [j0, j0 + 64), one that is visited, holds a masked pair and needs the select:
+// its first row does not see its last key inside the problem.  Otherwise the tile is interior: the unmasked kernel's path.
+constexpr bool causal_tile_cut(long i0, long j0, long offset, long J) {
+  const long last = J - 1 < j0 + (TILE_J - 1) ? J - 1 : j0 + (TILE_J - 1);
+  return last > i0 + offset;
+}
+
 // ---- The float64 forward (attention_f64.hip): the same tile of 64 query rows and the same padded head dimensions on
 // v_mfma_f64_16x16x4_f64.  Problem and Plan are the ones above; what differs is decided here, not in the kernel: the key tile
 // (Plan::tile_j, 64 or 32 keys), the LDS rows in doubles, and 16-byte loads that hold two elements.

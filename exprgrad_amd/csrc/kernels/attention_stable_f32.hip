@@ -33,197 +33,7 @@
 // No atomics, no workspace: two runs give the same bits.
 #include "gemm_plan.hpp"        // batched2_c_distinct
 #include "attention.hpp"        // the internal entry
-#include "attention_tile.hpp"   // kernel operands, tiles, the MFMA loops, the launcher
-
-#include <cmath>
-
-namespace {
-
-using eg::gemm::f32x4;
-using namespace eg::attention;
-
-struct StableArgs {
-  In q, k, v;
-  Out o;
-  Out st;      // Stats: row 0 the maxima, row 1 (st.v.ld floats on) the sums; p may be NULL
-  long I, J;
-  int K, D;
-  float scale;
-  int accumulate;
-  Items items;
-};
-
-struct StableBiasArgs : StableArgs {
-  In b;
-};
-
-template <int KP, int DP, bool BIAS>
-__global__ __launch_bounds__(THREADS) void attention_stable_f32_kernel(std::conditional_t<BIAS, StableBiasArgs, StableArgs> a) {
-  constexpr int KS = KP + 4, VS = DP + 16;
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  float* const Ks = lds;                      // [64][KS]; the Q tile first
-  float* const Vs = Ks + TILE_J * KS;         // [64][VS]
-  float* const Es = Vs + TILE_J * VS;         // [4][16][ES]
-
-  const BlockItem b = block_item(a.items);
-  const long i0 = (long)b.tile * TILE_I;
-  const long ldq = a.q.v.ld, ldk = a.k.v.ld, ldv = a.v.v.ld;
-  const float* const Q = item_base(a.q, b.outer, b.inner) + i0 * ldq;
-  const float* const Kk = item_base(a.k, b.outer, b.inner);
-  const float* const V = item_base(a.v, b.outer, b.inner);
-  float* const O = item_base(a.o, b.outer, b.inner);
-
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, c = lane & 15, g = lane >> 4;
-  float* const Ew = Es + w * 16 * ES;
-
-  // Q rows of the wave as A operands of every k step, for the whole loop
-  float q[KP / 4];
-  {
-    TileRegs<KP> tq;
-    load_rows<KP>(tq, Q, ldq, a.I - i0, a.K, a.q.vec != 0, tid);
-    store_rows<KP, KS>(tq, Ks, tid);
-    __syncthreads();
-    read_a_rows<KP, KS>(Ks, w, c, g, q);
-  }
-
-  f32x4 o[DP / 16];
-#pragma unroll
-  for (int nb = 0; nb < DP / 16; ++nb) o[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
-  float sum[4] = {0.f, 0.f, 0.f, 0.f};
-  float m[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};   // the same value in the 16 lanes of a row
-
-  TileRegs<KP> tk;
-  TileRegs<DP> tv;
-  // the lane's bias: rows 4 g + r of the wave's, keys c + 16 nb of a tile; `next` is a tile ahead
-  [[maybe_unused]] BiasTile bias, bias_next;
-  [[maybe_unused]] const long bias_rows = a.I - i0 - w * 16 - 4 * g;
-  [[maybe_unused]] long ldb = 0;
-  [[maybe_unused]] const float* Bl = nullptr;
-  if constexpr (BIAS) {
-    ldb = a.b.v.ld;
-    Bl = item_base(a.b, b.outer, b.inner) + (i0 + w * 16 + 4 * g) * ldb + c;
-  }
-  const long nt = (a.J + TILE_J - 1) / TILE_J;
-  if (nt > 0) {
-    load_rows<KP>(tk, Kk, ldk, a.J, a.K, a.k.vec != 0, tid);
-    load_rows<DP>(tv, V, ldv, a.J, a.D, a.v.vec != 0, tid);
-    if constexpr (BIAS) load_bias(bias_next, Bl, ldb, bias_rows, a.J - c);
-  }
-  for (long t = 0; t < nt; ++t) {
-    const long j0 = t * TILE_J;
-    __syncthreads();   // every wave is done with the tiles in LDS (the first time: with the Q tile)
-    store_rows<KP, KS>(tk, Ks, tid);
-    store_rows<DP, VS>(tv, Vs, tid);
-    __syncthreads();
-    if constexpr (BIAS) bias = bias_next;
-    if (t + 1 < nt) {   // in flight during this tile's MFMAs
-      load_rows<KP>(tk, Kk + (j0 + TILE_J) * ldk, ldk, a.J - j0 - TILE_J, a.K, a.k.vec != 0, tid);
-      load_rows<DP>(tv, V + (j0 + TILE_J) * ldv, ldv, a.J - j0 - TILE_J, a.D, a.v.vec != 0, tid);
-      if constexpr (BIAS) load_bias(bias_next, Bl + j0 + TILE_J, ldb, bias_rows, a.J - j0 - TILE_J - c);
-    }
-
-    f32x4 s[4];
-#pragma unroll
-    for (int nb = 0; nb < 4; ++nb) s[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
-    mma_nt<KP, KS>(q, Ks, c, g, s);
-
-    // the scores, in place; a key outside the problem is -Inf by a select, whatever its score: its term is exactly 0
-#pragma unroll
-    for (int nb = 0; nb < 4; ++nb) {
-      const bool live = j0 + nb * 16 + c < a.J;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float x = s[nb][r] * a.scale;
-        if constexpr (BIAS) x = x + bias.x[nb][r];
-        s[nb][r] = live ? x : -INFINITY;
-      }
-    }
-
-    // the running maximum and the subtrahend of each of the lane's four rows
-    float m_new[4], sub[4];
-    bool raised = false;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const float tile_max = row_max16(fmaxf(fmaxf(s[0][r], s[1][r]), fmaxf(s[2][r], s[3][r])));
-      m_new[r] = fmaxf(m[r], tile_max);   // never NaN: m starts at -Inf and fmaxf drops a NaN operand
-      sub[r] = m_new[r] == -INFINITY ? 0.f : m_new[r];
-      raised |= m_new[r] > m[r];
-    }
-    if (__any(raised)) {   // wave-uniform; a row that did not move would be multiplied by 1.0f
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float alpha = expf(m[r] - sub[r]);
-        sum[r] *= alpha;
-#pragma unroll
-        for (int nb = 0; nb < DP / 16; ++nb) o[nb][r] *= alpha;
-        m[r] = m_new[r];   // equal to m[r] wherever nothing was raised
-      }
-    }
-
-#pragma unroll
-    for (int nb = 0; nb < 4; ++nb) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float e = expf(s[nb][r] - sub[r]);
-        sum[r] += e;
-        Ew[(4 * g + r) * ES + nb * 16 + c] = e;
-      }
-    }
-    wave_sync();
-
-    mma_nn<DP, VS, ES>(Ew, Vs, c, g, o);
-    wave_sync();   // the wave's E rows are read before its next tile overwrites them
-  }
-
-  // Row sums: the 16 lanes of a group hold the columns = c (mod 16) of rows 4g + r.  L <= J: no overflow to look for.
-  const bool empty = a.J == 0;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    float t = sum[r];
-    t += __shfl_xor(t, 1);
-    t += __shfl_xor(t, 2);
-    t += __shfl_xor(t, 4);
-    t += __shfl_xor(t, 8);
-    sum[r] = t;
-  }
-  if (a.st.p) {
-    // from the lane that holds column 0 of its group's rows; without keys the maximum is -Inf and the sum 0
-    float* const St = item_base(a.st, b.outer, b.inner);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const long row = i0 + w * 16 + 4 * g + r;
-      if (c == 0 && row < a.I) {
-        St[row] = m[r];
-        St[a.st.v.ld + row] = sum[r];
-      }
-    }
-  }
-  if (empty && a.accumulate) return;   // an empty sum adds nothing to O
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const long row = i0 + w * 16 + 4 * g + r;
-    if (row >= a.I) continue;
-#pragma unroll
-    for (int nb = 0; nb < DP / 16; ++nb) {
-      const int col = nb * 16 + c;
-      if (col >= a.D) continue;
-      const float v = empty ? 0.f : o[nb][r] / sum[r];
-      float* const p = O + row * a.o.v.ld + col;
-      *p = a.accumulate ? *p + v : v;
-    }
-  }
-}
-
-template <auto KERNEL, class Args, int KP, int DP>
-int launch(eg_ctx* ctx, unsigned grid, const Plan& p, const Args& args) {
-  const int rc = dynamic_lds_once<KERNEL>(ctx, {lds_bytes_for(KP, DP)});
-  if (rc) return rc;
-  hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(p.block), (size_t)p.lds_bytes, ctx->stream, args);
-  EG_HIP_CHECK(hipGetLastError());
-  return EG_OK;
-}
-
-}  // namespace
+#include "attention_stable_f32.hpp"   // the kernel template and its launch
 
 namespace eg {
 namespace attention {
@@ -259,8 +69,9 @@ int attention_stable_check(eg_ctx* ctx, const Extents& e, const float* Q, View q
 }
 
 int attention_stable(eg_ctx* ctx, const Extents& e, float scale, const float* Q, View q, const float* Kk, View k, const float* V, View v, float* O,
-                     View o, int accumulate, float* Stats, View st, const float* Bias, View bv, const char* entry) {
+                     View o, int accumulate, float* Stats, View st, const float* Bias, View bv, const char* entry, long causal_offset) {
   const char* const name = entry ? entry : "eg_attention_stable";
+  const bool causal = causal_offset >= 0;
   const long batch1 = e.batch1, I = e.I, J = e.J, K = e.K, D = e.D;
   bool nothing = false;
   int rc = attention_stable_check(ctx, e, Q, q, Kk, k, V, v, O, o, accumulate, Stats, st, Bias, bv, name, &nothing);
@@ -278,15 +89,17 @@ int attention_stable(eg_ctx* ctx, const Extents& e, float scale, const float* Q,
   const Plan p = plan_attention(pr);
   EG_REQUIRE(p.supported, EG_ERR_UNSUPPORTED, "%s: %s", name, p.reason);
 
-  StableBiasArgs args = {};
+  StableCausalArgs args = {};
+  args.offset = causal_offset < J ? causal_offset : J;   // an offset of J - 1 or more masks nothing
   args.q = {Q, q, p.vec_q}, args.k = {Kk, k, p.vec_k}, args.v = {V, v, p.vec_v};
   args.o = {O, o, 0}, args.st = {Stats, st, 0}, args.b = {Bias, bv, p.vec_b};
   args.I = I, args.J = J, args.K = (int)K, args.D = (int)D;
   args.scale = scale;
   args.accumulate = accumulate;
-  // 18 kernels: the padded K x the padded D, with and without a bias
+  // 18 kernels: the padded K x the padded D, with and without a bias; 18 more that are CAUSAL
   return for_each_launch(name, p.items, p.cut(), batch1, [&](const Items& items, unsigned grid) {
     args.items = items;
+    if (causal) return launch_stable_causal(ctx, grid, p, args);
     return dispatch_heads(p.kp, p.dp, [&](auto KP, auto DP) {
       constexpr int kp = KP(), dp = DP();
       return Bias ? launch<&attention_stable_f32_kernel<kp, dp, true>, StableBiasArgs, kp, dp>(ctx, grid, p, args)

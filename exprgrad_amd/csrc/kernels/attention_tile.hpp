@@ -128,6 +128,44 @@ __device__ __forceinline__ void load_bias_t(BiasTile& t, const float* __restrict
   }
 }
 
+// ---- what the CAUSAL kernels visit (eg_attention_causal, eg_attention_causal_grad; attention_plan.hpp has the bounds) ------------
+// Each is the unmasked kernel's value without CAUSAL, and `a` has an offset only with it.
+// The block's item and row tile: the forward and dQ blocks of a causal item take the row tiles in descending order, because a
+// late row tile walks up to tiles times the key tiles of the first and the longest loops should be issued first.
+template <bool CAUSAL>
+__device__ __forceinline__ BlockItem causal_block_item(const Items& it) {
+  BlockItem b = block_item(it);
+#ifndef EG_ATTENTION_CAUSAL_NATURAL_ORDER   // the other order, for tools/bench_attention_causal.py
+  if constexpr (CAUSAL) b.tile = it.tiles - 1 - b.tile;
+#endif
+  return b;
+}
+
+// Forward and dQ: the keys that are loaded, and the key tiles of the loop of the block of rows [i0, i0 + 64).
+template <bool CAUSAL, class Args>
+__device__ __forceinline__ long causal_loaded_keys(const Args& a) {
+  if constexpr (CAUSAL)
+    return causal_visible_keys(a.I, a.offset, a.J);
+  else
+    return a.J;
+}
+template <bool CAUSAL, class Args>
+__device__ __forceinline__ long causal_loop_tiles(const Args& a, long i0, long keys) {
+  if constexpr (CAUSAL)
+    return causal_key_tiles(i0, a.offset, keys);
+  else
+    return (a.J + TILE_J - 1) / TILE_J;
+}
+
+// dK/dV: the first row tile of the loop of the block of keys [j0, j0 + 64); nt, an empty loop, when no row sees them.
+template <bool CAUSAL, class Args>
+__device__ __forceinline__ long causal_loop_start(const Args& a, long j0, long nt) {
+  if constexpr (CAUSAL)
+    return j0 < causal_visible_keys(a.I, a.offset, a.J) ? causal_first_row_tile(j0, a.offset) : nt;
+  else
+    return 0;
+}
+
 // What one wave wrote to its own LDS rows becomes visible to its other lanes: no block barrier.
 __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");

@@ -159,6 +159,28 @@ def attention_stable_grad(ctx, batch0, batch1, I, J, K, D, scale, Q, ldq, stride
          strides_dk[0], strides_dk[1], _p(dV), lddv, strides_dv[0], strides_dv[1], int(accumulate), _p(Bias), ldb, strides_b[0], strides_b[1])
 
 
+def attention_causal(ctx, batch0, batch1, I, J, K, D, scale, Q, ldq, strides_q, Kk, ldk, strides_k, V, ldv, strides_v, O, ldo, strides_o,
+                     Stats=None, lds=0, strides_s=(0, 0), Bias=None, ldb=0, strides_b=(0, 0), accumulate=False, offset=0):
+    """`attention_stable` under a causal mask: key j is visible to query row i iff j <= i + offset (0: the diagonal of
+    self-attention; J - I: a step against a key/value cache; negative: refused).  Key tiles without a visible key are never
+    loaded or computed; O and Stats have the bits of `attention_stable` with a Bias of -inf at the masked pairs."""
+    call("eg_attention_causal", ctx.handle, batch0, batch1, I, J, K, D, float(scale), _p(Q), ldq, strides_q[0], strides_q[1], _p(Kk), ldk,
+         strides_k[0], strides_k[1], _p(V), ldv, strides_v[0], strides_v[1], _p(O), ldo, strides_o[0], strides_o[1], int(accumulate), _p(Stats),
+         lds, strides_s[0], strides_s[1], _p(Bias), ldb, strides_b[0], strides_b[1], int(offset))
+
+
+def attention_causal_grad(ctx, batch0, batch1, I, J, K, D, scale, Q, ldq, strides_q, Kk, ldk, strides_k, V, ldv, strides_v, O, ldo, strides_o,
+                          Stats, lds, strides_s, dO, lddo, strides_do, dQ, lddq, strides_dq, dK, lddk, strides_dk, dV, lddv, strides_dv,
+                          Bias=None, ldb=0, strides_b=(0, 0), accumulate=0, offset=0):
+    """`attention_stable_grad` for `attention_causal`: O and Stats from it (accumulate = False) on the same operands, the same Bias
+    and the same offset.  accumulate bit 0 adds to dQ, bit 1 to dK, bit 2 to dV."""
+    call("eg_attention_causal_grad", ctx.handle, batch0, batch1, I, J, K, D, float(scale), _p(Q), ldq, strides_q[0], strides_q[1], _p(Kk), ldk,
+         strides_k[0], strides_k[1], _p(V), ldv, strides_v[0], strides_v[1], _p(O), ldo, strides_o[0], strides_o[1], _p(Stats), lds,
+         strides_s[0], strides_s[1], _p(dO), lddo, strides_do[0], strides_do[1], _p(dQ), lddq, strides_dq[0], strides_dq[1], _p(dK), lddk,
+         strides_dk[0], strides_dk[1], _p(dV), lddv, strides_dv[0], strides_dv[1], int(accumulate), _p(Bias), ldb, strides_b[0], strides_b[1],
+         int(offset))
+
+
 def attention_grad_f64(ctx, batch0, batch1, I, J, K, D, scale, Q, ldq, strides_q, Kk, ldk, strides_k, V, ldv, strides_v, O, ldo, strides_o, Sums,
                        strides_s, dO, lddo, strides_do, dQ, lddq, strides_dq, dK, lddk, strides_dk, dV, lddv, strides_dv, accumulate=0):
     """The float64 form of `attention_grad`: O and Sums from attention_sums_f64 (accumulate = False), every operand in doubles

@@ -566,7 +566,55 @@ int eg_attention_stable_grad(eg_ctx* ctx, int64_t batch0, int64_t batch1, int64_
                              float* dV, int64_t lddv, int64_t stride_dv0, int64_t stride_dv1, int accumulate,
                              const float* Bias, int64_t ldb, int64_t stride_b0, int64_t stride_b1);
 
-/* out[y,x] (+)= bias[x]   — dense's second kernel, dnn.nim:22-24. out is [rows, cols]. */
+/* eg_attention_stable under a causal mask that is not a table: key j is visible to query row i iff j <= i + offset, and key
+ * tiles without a visible key are never loaded or computed.  The first 33 arguments and their contract are
+ * eg_attention_stable's (views, accumulate, the optional Stats and Bias, empty extents, the table of special values); the
+ * refusals name eg_attention_causal.
+ *   offset == 0:     the diagonal mask of self-attention;
+ *   offset == J - I: the bottom-right alignment of a step against a key/value cache;
+ *   offset >= J - 1: nothing is masked;
+ *   offset <  0:     EG_ERR_INVALID, with a message that names eg_attention_causal: the first rows would see no key.  So every
+ *                    row sees key 0.
+ * The same kernel with one more compile-time flag (kernels/attention_causal_f32.hip): the block of rows [i0, i0 + 64) walks
+ * the key tiles up to the one that holds key min(J - 1, i0 + 63 + offset), in ascending order; tiles whose last key is
+ * <= i0 + offset take the unmasked path, and the one or two tiles on the diagonal are cut by a lane-local select.  With I == J
+ * and offset == 0 that is T (T + 1) / 2 of T * T tile visits, T = ceil(I / 64).
+ *   - O and Stats have the bits of eg_attention_stable on the same operands with a bias of -Inf where j > i + offset and the
+ *     given Bias (or +0) elsewhere, the sign of a zero aside, whenever Q, Kk and V are finite: a masked term is exactly 0 and a
+ *     skipped tile adds zeros.  Stats are valid input to eg_attention_causal_grad with the same offset.
+ *   - Keys j >= I + offset, which no row sees, are never read: neither Kk, V nor Bias there.
+ * Two calls give the same bits. */
+int eg_attention_causal(eg_ctx* ctx, int64_t batch0, int64_t batch1, int64_t I, int64_t J, int64_t K, int64_t D, float scale,
+                        const float* Q, int64_t ldq, int64_t stride_q0, int64_t stride_q1,
+                        const float* Kk, int64_t ldk, int64_t stride_k0, int64_t stride_k1,
+                        const float* V, int64_t ldv, int64_t stride_v0, int64_t stride_v1,
+                        float* O, int64_t ldo, int64_t stride_o0, int64_t stride_o1, int accumulate,
+                        float* Stats, int64_t lds, int64_t stride_s0, int64_t stride_s1,
+                        const float* Bias, int64_t ldb, int64_t stride_b0, int64_t stride_b1, int64_t offset);
+
+/* The backward of eg_attention_causal: the arguments and the contract of eg_attention_stable_grad and the forward's offset;
+ * O and Stats come from eg_attention_causal (accumulate == 0) on the same operands, the same Bias and the same offset.  The
+ * refusals name eg_attention_causal_grad; offset < 0 is EG_ERR_INVALID.  eg_attention_stable_grad's two kernels with one more
+ * compile-time flag (kernels/attention_grad_causal_f32.hip, attention_grad_causal_bias_f32.hip): the dQ kernel walks the key
+ * tiles the forward walked, the dK/dV kernel of keys [j0, j0 + 64) starts at the row tile that holds row max(0, j0 - offset),
+ * both in ascending order, and both cut the diagonal tiles by a select before the exponential.
+ *   - dQ, dK and dV have the bits of eg_attention_stable_grad with a bias of -Inf where j > i + offset and the given Bias (or
+ *     +0) elsewhere, the sign of a zero aside, whenever the inputs are finite.  dK and dV of keys that no row sees get zeros
+ *     (zeros are added when accumulating).
+ * Two calls give the same bits. */
+int eg_attention_causal_grad(eg_ctx* ctx, int64_t batch0, int64_t batch1, int64_t I, int64_t J, int64_t K, int64_t D, float scale,
+                             const float* Q, int64_t ldq, int64_t stride_q0, int64_t stride_q1,
+                             const float* Kk, int64_t ldk, int64_t stride_k0, int64_t stride_k1,
+                             const float* V, int64_t ldv, int64_t stride_v0, int64_t stride_v1,
+                             const float* O, int64_t ldo, int64_t stride_o0, int64_t stride_o1,
+                             const float* Stats, int64_t lds, int64_t stride_s0, int64_t stride_s1,
+                             const float* dO, int64_t lddo, int64_t stride_do0, int64_t stride_do1,
+                             float* dQ, int64_t lddq, int64_t stride_dq0, int64_t stride_dq1,
+                             float* dK, int64_t lddk, int64_t stride_dk0, int64_t stride_dk1,
+                             float* dV, int64_t lddv, int64_t stride_dv0, int64_t stride_dv1, int accumulate,
+                             const float* Bias, int64_t ldb, int64_t stride_b0, int64_t stride_b1, int64_t offset);
+
+/* out[y,x] (+)= bias[x]  — dense's second kernel, dnn.nim:22-24. out is [rows, cols]. */
 int eg_bias_add(eg_ctx* ctx, int64_t rows, int64_t cols, const float* bias, float* out,
                 int accumulate);
 /* out[x] (+)= sum_y in[y,x]  — derived bias gradient (Appendix A.1 G5/G2 of SURVEY.md). */
