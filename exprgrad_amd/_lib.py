@@ -95,6 +95,8 @@ _SIGS = {
                                  [c_int] + [c_void_p, c_i64, c_i64, c_i64]),
     "eg_attention_causal": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_f32] + [c_void_p, c_i64, c_i64, c_i64] * 4 +
                             [c_int] + [c_void_p, c_i64, c_i64, c_i64] * 2 + [c_i64]),
+    "eg_attention_causal_split": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_f32] + [c_void_p, c_i64, c_i64, c_i64] * 4 +
+                                  [c_int] + [c_void_p, c_i64, c_i64, c_i64] * 2 + [c_i64, c_int]),
     "eg_attention_causal_grad": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_f32] + [c_void_p, c_i64, c_i64, c_i64] * 9 +
                                  [c_int] + [c_void_p, c_i64, c_i64, c_i64] + [c_i64]),
     "eg_attention_f64": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_f64] + [c_void_p, c_i64, c_i64, c_i64] * 4 + [c_int]),

@@ -48,6 +48,12 @@ int attention_stable_check(eg_ctx* ctx, const Extents& e, const float* Q, View q
 int attention_stable_split(eg_ctx* ctx, const Extents& e, float scale, const float* Q, View q, const float* Kk, View k, const float* V, View v,
                            float* O, View o, int accumulate, float* Stats, View st, const float* Bias, View bv, int splits);
 
+// The causal forward cut into chunks of key tiles (attention_causal_split_f32.hip, eg_attention_causal_split): every 64-row tile's
+// visible key tiles go to ceil(n / chunk) blocks; a row tile with one piece is finished by its block with attention_stable's
+// causal bits, the others through the workspace and a combine launch.  chunk == 0: plan_attention_causal_split chooses.
+int attention_causal_split(eg_ctx* ctx, const Extents& e, float scale, const float* Q, View q, const float* Kk, View k, const float* V, View v,
+                           float* O, View o, int accumulate, float* Stats, View st, const float* Bias, View bv, long offset, int chunk);
+
 // The gradient of that bias (attention_dbias_f32.hip): eg_attention_bias_dbias, over what attention_forward left with Sums and
 // the same Bias.  dBias (+)= the sum of p * (dP - delta) over every index whose step in `db` is 0; db.ld and both its strides
 // are 0 exactly where bv's are.

@@ -95,6 +95,85 @@ SplitPlan plan_attention_split(const Problem& p, int splits) {
   return r;
 }
 
+// The causal forward in chunks of key tiles.  The auto rule (chunk == 0), with visits = the key-tile visits of the whole call
+// and blocks = items x row tiles, the blocks of eg_attention_causal:
+//   - blocks below split_blocks_per_cu x CUs (a launch that leaves block slots idle): chunk = visits / (split_blocks_per_cu x
+//     CUs), rounded up: about as many pieces as run at once, the split's rule;
+//   - a full launch whose items have more row tiles than there are items: nothing is cut.  Its blocks are issued item by item,
+//     longest first, so with few items of many row tiles the whole launch is nearly longest-first already;
+//   - any other full launch: chunk = visits / CUs / CAUSAL_SPLIT_FULL_PIECES, pieces of a sixteenth of a CU's share of the work,
+//     which bounds what the last block of the launch can add to its time;
+//   - never below CAUSAL_SPLIT_MIN_TILES; a chunk at or above the longest row tile cuts nothing: eg_attention_causal.
+// The rows these came from, profiles/attention_causal_split.txt section 2 (one MI355X, 256 CUs; microseconds per call, median
+// of three fresh processes, spread at most 5.5 us below 2 ms and 22.4 us above; heads x I x J x K=D, offset):
+//   shape                     causal  chunk 1      2      4      8     16     32     64    128    256   auto picks
+//   128x512x512x64, 0          111.1    115.9  100.2  102.0  111.0                                       2
+//   128x2048x2048x64, 0        983.9   1678.6 1254.2 1092.0 1011.8  972.6  981.7                         16
+//   32x128x8192x128, 8064      872.0    512.9  379.3  298.4  263.3  245.1  234.4  449.1  873.1           32
+//   32x16x8192x128, 8176       861.6    205.1  133.1   94.0   77.5   68.3  112.1  208.2  400.7           16
+//   32x1x8192x128, 8191        853.9    187.3  123.2   91.2   74.8   65.9  108.4  201.5  389.0           16
+//   8x16384x16384x64, 0       3190.1   6567.4 4852.1 4059.3 3641.4 3427.3 3332.4 3278.1 3212.9 3178.4    256 (eg_attention_causal)
+//  - the three cache shapes have their best time where the pieces are 256, one per CU at K = D = 128: the split's constant;
+//  - CAUSAL_SPLIT_FULL_PIECES = 16 and CAUSAL_SPLIT_MIN_TILES = 2 are fitted to the first two rows (a CU's share is 18 and 264
+//    visits: chunks 2 and 16), and the row-tiles-against-items test to the last, where no chunk measured faster than
+//    eg_attention_causal.  Three rows do not make a model: full launches of other shapes are not measured.
+CausalSplitPlan plan_attention_causal_split(const Problem& p, long offset, int chunk) {
+  CausalSplitPlan r;
+  if (chunk < 0) {
+    r.reason = "a negative chunk";
+    return r;
+  }
+  if (offset < 0) {
+    r.reason = "a negative offset";
+    return r;
+  }
+  r.base = plan_forward(p, false);
+  if (!r.base.supported) {
+    r.reason = r.base.reason;
+    return r;
+  }
+  const Plan& b = r.base;
+  if (p.J >= (1L << 36)) {
+    r.reason = "J of 2^36 or more";
+    return r;
+  }
+  offset = std::min(offset, p.J);
+  r.rows16 = p.I <= SPLIT_ROWS16;
+  r.rows = r.rows16 ? SPLIT_ROWS16 : TILE_I;
+  if (chunk == 0) {
+    const CausalPieces whole = causal_pieces(p.I, p.J, offset, 1, r.rows16);
+    const long visits = b.items * causal_pieces_before(whole, whole.tiles);   // with chunk 1 a piece is a tile visit
+    const long target = split_blocks_per_cu(b.kp, b.dp) * p.cus;
+    long auto_chunk = whole.nv;   // nothing is cut
+    if (b.items * whole.tiles < target)
+      auto_chunk = (visits + target - 1) / target;
+    else if (whole.tiles <= b.items)
+      auto_chunk = visits / p.cus / CAUSAL_SPLIT_FULL_PIECES;
+    r.pieces = causal_pieces(p.I, p.J, offset, std::max(CAUSAL_SPLIT_MIN_TILES, auto_chunk), r.rows16);
+  } else {
+    r.pieces = causal_pieces(p.I, p.J, offset, chunk, r.rows16);
+  }
+  const CausalPieces& c = r.pieces;
+  r.first_cut = causal_first_cut_tile(c);
+  r.pieces_per_item = causal_pieces_before(c, c.tiles);
+  r.slots = r.pieces_per_item - causal_pieces_before(c, r.first_cut);
+  r.forward = p.J == 0 || p.D == 0 || (!r.rows16 && r.first_cut == c.tiles);
+  if (r.pieces_per_item > eg::gemm::BATCHED_MAX_BLOCKS) {
+    r.reason = "an item has more pieces than one launch has blocks";
+    return r;
+  }
+  r.stats_offset = b.items * r.slots * r.rows * b.dp;
+  r.workspace_bytes = r.forward ? 0 : 4L * (r.stats_offset + b.items * r.slots * 2 * r.rows);
+  r.partial = cut_items(b.items, r.pieces_per_item);
+  r.combine_rows_per_item = r.rows * (c.tiles - r.first_cut);
+  r.combine_rows = b.items * r.combine_rows_per_item;
+  const long rows_per_block = 4 * THREADS / b.dp;
+  r.combine_grid = std::min(eg::gemm::BATCHED_MAX_BLOCKS, (r.combine_rows + rows_per_block - 1) / rows_per_block);
+  r.lds_bytes = r.rows16 ? split16_lds_bytes(b.kp, b.dp) : b.lds_bytes;
+  r.supported = true;
+  return r;
+}
+
 namespace {
 
 // The backward's plan in either scalar type: the two differ in the steps, the LDS rows and the 16-byte rule.  Empty I, J, K

@@ -160,6 +160,111 @@ constexpr bool causal_tile_cut(long i0, long j0, long offset, long J) {
   return last > i0 + offset;
 }
 
+// ---- The causal forward cut into chunks of key tiles (attention_causal_split_f32.hip, eg_attention_causal_split): row tile t of
+// an item has n_t = causal_key_tiles(64 t, offset, visible) key tiles and is walked by P_t = ceil(n_t / chunk) blocks, piece p of
+// them over tiles [split_first(n_t, P_t, p), split_first(n_t, P_t, p + 1)).  A row tile with one piece is finished by its block
+// (the bits of eg_attention_causal); the pieces of a cut row tile (P_t >= 2) leave partials in the workspace and a combine launch
+// merges them.  Up to 16 query rows the block is the 16-row mode's and every piece goes through the workspace.
+//
+// TILE_I == TILE_J, so n_t = min(nv, t + c0): nv the tiles of the visible keys, c0 the key tiles of row tile 0 without that
+// bound.  n_t does not fall with t: the cut row tiles are [causal_first_cut_tile, tiles), and the pieces before row tile t have
+// a closed form.  These functions are the only place where a block's index becomes (row tile, piece) and a partial's slot.
+struct CausalPieces {
+  long nv = 0;      // key tiles that hold a visible key
+  long c0 = 0;      // (63 + offset) / 64 + 1
+  long tiles = 0;   // row tiles of an item: ceil(I / 64), or 1 in the 16-row mode
+  long chunk = 1;   // key tiles of a piece at the most: 1 .. max(nv, 1)
+  bool rows16 = false;   // every piece leaves a partial, also a row tile's only one
+};
+static_assert(TILE_I == TILE_J, "n_t = min(nv, t + c0)");
+
+// offset already clamped to [0, J]; rows16: I <= 16, one row tile that sees every visible key.
+constexpr CausalPieces causal_pieces(long I, long J, long offset, long chunk, bool rows16) {
+  const long nv = (causal_visible_keys(I, offset, J) + TILE_J - 1) / TILE_J;
+  const long most = nv < 1 ? 1 : nv;
+  return {nv, rows16 ? nv : (TILE_I - 1 + offset) / TILE_J + 1, rows16 ? 1 : (I + TILE_I - 1) / TILE_I, chunk < most ? chunk : most, rows16};
+}
+constexpr long causal_row_key_tiles(const CausalPieces& c, long t) { return c.nv < t + c.c0 ? c.nv : t + c.c0; }
+constexpr long causal_piece_count(long n, long chunk) { return (n + chunk - 1) / chunk; }
+// The sum of ceil(x / chunk) over x in [0, y).  The operands of both divisions are below 2^31 (the plan refuses nv above
+// that), so they are 32-bit divisions on the device.
+constexpr long causal_ceil_sum(long y, long chunk) {
+  if (y <= 1) return 0;
+  const unsigned m = (unsigned)(y - 1), c = (unsigned)chunk;
+  const long full = m / c, rem = m % c;
+  return chunk * (full * (full + 1) / 2) + rem * (full + 1);
+}
+// Pieces of row tiles [0, t), t in [0, tiles]: the row tiles below nv - c0 grow by one key tile each, the others have nv.
+constexpr long causal_pieces_before(const CausalPieces& c, long t) {
+  const long rising = c.nv - c.c0 < 0 ? 0 : (c.nv - c.c0 < t ? c.nv - c.c0 : t);
+  return causal_ceil_sum(c.c0 + rising, c.chunk) - causal_ceil_sum(c.c0, c.chunk) + (t - rising) * causal_piece_count(c.nv, c.chunk);
+}
+// The first row tile whose pieces leave partials, those with two pieces or more: `tiles` when there is none.
+constexpr long causal_first_cut_tile(const CausalPieces& c) {
+  if (c.rows16) return 0;
+  if (c.nv <= c.chunk) return c.tiles;
+  const long t = c.chunk + 1 - c.c0 < 0 ? 0 : c.chunk + 1 - c.c0;
+  return t < c.tiles ? t : c.tiles;
+}
+// A block's index x in [0, causal_pieces_before(c, tiles)) within its item -> (row tile, piece).  The order is the reverse of
+// (row tile, piece) ascending: the row tiles with the most key tiles are issued first, as in the causal kernels.  A binary
+// search over the row tiles on the closed form: ceil(log2(tiles)) steps, no table.
+struct CausalPiece {
+  long tile = 0;
+  int piece = 0, pieces = 1;
+  long t0 = 0, t1 = 0;   // its key tiles [t0, t1)
+  long slot = 0;         // of a cut row tile: its partial's place among the item's partials
+};
+constexpr CausalPiece causal_piece_decode(const CausalPieces& c, long x) {
+  const long y = causal_pieces_before(c, c.tiles) - 1 - x;
+  long lo = 0, hi = c.tiles - 1;   // the last row tile with pieces_before <= y
+  while (lo < hi) {
+    const long mid = (lo + hi + 1) / 2;
+    if (causal_pieces_before(c, mid) <= y)
+      lo = mid;
+    else
+      hi = mid - 1;
+  }
+  CausalPiece r;
+  const long before = causal_pieces_before(c, lo), n = causal_row_key_tiles(c, lo);
+  r.tile = lo;
+  r.piece = (int)(y - before);
+  r.pieces = (int)causal_piece_count(n, c.chunk);
+  r.t0 = split_first(n, r.pieces, r.piece), r.t1 = split_first(n, r.pieces, r.piece + 1);
+  r.slot = before - causal_pieces_before(c, causal_first_cut_tile(c)) + r.piece;
+  return r;
+}
+
+struct CausalSplitPlan {
+  bool supported = false;
+  const char* reason = "";
+  Plan base;                 // plan_attention's: padded heads, load widths, tiles_i, items
+  bool rows16 = false;       // the mode
+  bool forward = false;      // nothing is cut (J == 0, D == 0, or the 64-row mode without a cut row tile): eg_attention_causal, the same bits
+  CausalPieces pieces;       // with the effective chunk
+  long pieces_per_item = 0;  // blocks of an item in the partial launch
+  long first_cut = 0;        // causal_first_cut_tile
+  long slots = 0;            // partials of an item: the pieces of its cut row tiles (16-row mode: of its one row tile)
+  int rows = TILE_I;         // rows of a partial: 64 or 16
+  // The workspace: O parts [items][slots][rows][dp] floats, then maxima and sums [items][slots][2][rows].
+  long stats_offset = 0;     // in floats
+  long workspace_bytes = 0;
+  Cut partial;               // pieces_per_item blocks per item
+  long combine_rows_per_item = 0;   // rows * the cut row tiles
+  long combine_rows = 0;     // items * combine_rows_per_item
+  long combine_grid = 0;     // one launch of blocks of 1024 / dp rows; a block walks rows 1024 / dp * grid apart
+  int block = THREADS;
+  long lds_bytes = 0;        // of the partial kernel
+};
+
+// The auto rule's constants (chunk == 0): the rule and the rows of profiles/attention_causal_split.txt they came from are beside
+// plan_attention_causal_split in attention_plan.cpp.
+constexpr long CAUSAL_SPLIT_MIN_TILES = 2;      // key tiles of a piece at the least
+constexpr long CAUSAL_SPLIT_FULL_PIECES = 16;   // a full launch: pieces per CU's share of the key-tile visits
+
+// chunk: 0 the auto rule, n >= 1 key tiles per piece at the most (negative: not supported).  offset as the entry clamps it.
+CausalSplitPlan plan_attention_causal_split(const Problem& p, long offset, int chunk);
+
 // ---- The float64 forward (attention_f64.hip): the same tile of 64 query rows and the same padded head dimensions on
 // v_mfma_f64_16x16x4_f64.  Problem and Plan are the ones above; what differs is decided here, not in the kernel: the key tile
 // (Plan::tile_j, 64 or 32 keys), the LDS rows in doubles, and 16-byte loads that hold two elements.

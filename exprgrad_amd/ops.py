@@ -169,6 +169,16 @@ def attention_causal(ctx, batch0, batch1, I, J, K, D, scale, Q, ldq, strides_q, 
          lds, strides_s[0], strides_s[1], _p(Bias), ldb, strides_b[0], strides_b[1], int(offset))
 
 
+def attention_causal_split(ctx, batch0, batch1, I, J, K, D, scale, Q, ldq, strides_q, Kk, ldk, strides_k, V, ldv, strides_v, O, ldo, strides_o,
+                           Stats=None, lds=0, strides_s=(0, 0), Bias=None, ldb=0, strides_b=(0, 0), accumulate=False, offset=0, chunk=0):
+    """`attention_causal` with every 64-row tile's visible key tiles cut into pieces of at most `chunk` tiles (0: the library
+    chooses), one block per piece, and one launch that combines the rows of the cut row tiles.  For a chunk of query rows or a
+    decode step against a long key/value cache, or one long sequence; Stats serve `attention_causal_grad`."""
+    call("eg_attention_causal_split", ctx.handle, batch0, batch1, I, J, K, D, float(scale), _p(Q), ldq, strides_q[0], strides_q[1], _p(Kk), ldk,
+         strides_k[0], strides_k[1], _p(V), ldv, strides_v[0], strides_v[1], _p(O), ldo, strides_o[0], strides_o[1], int(accumulate), _p(Stats),
+         lds, strides_s[0], strides_s[1], _p(Bias), ldb, strides_b[0], strides_b[1], int(offset), int(chunk))
+
+
 def attention_causal_grad(ctx, batch0, batch1, I, J, K, D, scale, Q, ldq, strides_q, Kk, ldk, strides_k, V, ldv, strides_v, O, ldo, strides_o,
                           Stats, lds, strides_s, dO, lddo, strides_do, dQ, lddq, strides_dq, dK, lddk, strides_dk, dV, lddv, strides_dv,
                           Bias=None, ldb=0, strides_b=(0, 0), accumulate=0, offset=0):

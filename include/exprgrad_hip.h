@@ -592,6 +592,40 @@ int eg_attention_causal(eg_ctx* ctx, int64_t batch0, int64_t batch1, int64_t I, 
                         float* Stats, int64_t lds, int64_t stride_s0, int64_t stride_s1,
                         const float* Bias, int64_t ldb, int64_t stride_b0, int64_t stride_b1, int64_t offset);
 
+/* eg_attention_causal with the key range of every 64-row tile cut into pieces of at most `chunk` 64-key tiles, each piece a
+ * block of its own: for launches whose blocks are few or uneven — a chunk of query rows or a decode step against a long
+ * key/value cache (offset == J - I), one long sequence.  The first 34 arguments and their contract are eg_attention_causal's
+ * (the offset and its clamp, views, accumulate, the optional Stats and Bias, empty extents, the table of special values); the
+ * refusals name eg_attention_causal_split.
+ *   chunk == 0: the planner chooses (plan_attention_causal_split: a launch that leaves the device partly idle gets pieces
+ *               sized so that about as many blocks as run at once exist, a full one pieces of a sixteenth of a compute
+ *               unit's share of the key-tile visits, none below two tiles; where that cuts no row tile the call is
+ *               eg_attention_causal's; kernels/attention_plan.cpp has the rule and the measurements it came from);
+ *   chunk >= 1: row tile t, with n_t visible key tiles, is walked by P_t = ceil(n_t / chunk) blocks; piece p takes key tiles
+ *               [p * n_t / P_t, (p + 1) * n_t / P_t): balanced, never empty;
+ *   chunk <  0: EG_ERR_INVALID.
+ * Two launches (kernels/attention_causal_split_f32.hip).  A block whose row tile has one piece finishes it: those rows have
+ * the bits of eg_attention_causal and never touch the workspace.  The blocks of a cut row tile (P_t >= 2) leave the row
+ * maxima, the sums relative to them and the unnormalised O rows of their pieces in the context's workspace, and a second
+ * kernel, over the rows of cut row tiles only, combines them with weights expf(m_p - M), p ascending, divides, and stores O
+ * and Stats.  Masked key tiles are in no piece; keys j >= I + offset are never read.  With I <= 16 the four waves of a block
+ * hold the same rows and each takes 16 keys of every tile; this mode sends every piece through the workspace.
+ *   - The same mathematical result as eg_attention_causal; on cut row tiles the bits differ, because the sums are taken in
+ *     another, fixed order.  No atomics: two calls give the same bits.  J == 0, D == 0, and I > 16 with no cut row tile (any
+ *     chunk at or above the longest row tile's key tiles) are eg_attention_causal's launch, with its bits.
+ *   - Stats (the true row maximum and the sum relative to it) are valid input to eg_attention_causal_grad with the same offset.
+ *   - EG_ERR_UNSUPPORTED also when the pieces of one item exceed 2^22, the blocks of one launch, or J >= 2^36.
+ *   - The workspace grows to batch0 * batch1 * S * R * (Dp + 2) floats: S the pieces of one item's cut row tiles (I <= 16: of its
+ *     one row tile), R = 64 (16) rows each, Dp = D padded to 32, 64 or 128; like every entry that uses the workspace, calls on
+ *     one context must not run concurrently. */
+int eg_attention_causal_split(eg_ctx* ctx, int64_t batch0, int64_t batch1, int64_t I, int64_t J, int64_t K, int64_t D, float scale,
+                              const float* Q, int64_t ldq, int64_t stride_q0, int64_t stride_q1,
+                              const float* Kk, int64_t ldk, int64_t stride_k0, int64_t stride_k1,
+                              const float* V, int64_t ldv, int64_t stride_v0, int64_t stride_v1,
+                              float* O, int64_t ldo, int64_t stride_o0, int64_t stride_o1, int accumulate,
+                              float* Stats, int64_t lds, int64_t stride_s0, int64_t stride_s1,
+                              const float* Bias, int64_t ldb, int64_t stride_b0, int64_t stride_b1, int64_t offset, int chunk);
+
 /* The backward of eg_attention_causal: the arguments and the contract of eg_attention_stable_grad and the forward's offset;
  * O and Stats come from eg_attention_causal (accumulate == 0) on the same operands, the same Bias and the same offset.  The
  * refusals name eg_attention_causal_grad; offset < 0 is EG_ERR_INVALID.  eg_attention_stable_grad's two kernels with one more
